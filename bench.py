@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- ensemble-site-timesteps/s of the batched SIPNET step loop on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+  higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step).  --dump-outputs DIR: rank 0
+  writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).  --full: everything
+  else the line reports -- CPU baseline, roofline (kernel / setup / plan timings, fill probe, end to end),
+  the N > 1 gather legs, the oracle parity check -- measured in the same process after the timed steps.
   N>1: one rank per GPU under torch.distributed.run -- started by the driver, or, when the command is given
   without a launcher (no WORLD_SIZE in the environment), by bench.py itself as a child process (launch_ranks).  One "step" = one pass
   of the hot path over the whole batch: per-member setup + the time-fused step kernel
@@ -27,7 +32,7 @@ Workloads (BASELINE.json configs):
         optional-physics instantiation of the cooperative kernel (not a BASELINE config)
 Per-GPU work is fixed as N grows ("scaling": "weak").
 
-What the JSON line says about the kernel (the `roofline` object):
+What the JSON line says about the kernel (the `roofline` object, --full only):
   frac               SURVEY 8(d)'s contract number: 344 B (172 B fp32) of ALGORITHMIC state traffic
                      per member-step x units per launch / kernel time / 8 TB/s.  It is a normalised
                      throughput: the time-fused kernel keeps state in registers and LDS, so ...
@@ -63,6 +68,8 @@ sys.path.insert(0, REPO)
 ALGO_BYTES = {"f64": 344.0, "f32": 172.0}   # bytes per member-timestep
 HBM_PEAK_GBPS = 8000.0                       # MI355X_MICROARCH.md: HBM3E 8 TB/s
 SCLK_PEAK_HZ = 2.4e9                         # MI355X_MICROARCH.md: max clock 2400 MHz
+DUMP_BYTES = 60_000_000                      # --dump-outputs: all arrays together stay under 64 MB
+DUMP_SEED = 20261016                         # ... and larger outputs are cut to this seeded sample
 
 WORKLOADS = {
     "c10k": dict(sites=1, members=10240, prec="f64", steps=17520),
@@ -242,6 +249,26 @@ def fill_probe(sa, synth, flags, base, prec_name, device):
             "kernel_ms": min(ms), "waves_per_simd": li["waves_per_simd"]}
 
 
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: write each (name, tensor, axis) of `outputs` as out_dir/<name>.npy, float32 / float64 as
+    computed (integer outputs widened to float64).  Every array gets an equal share of DUMP_BYTES; one larger
+    than its share keeps a sorted sample of indices along `axis` (the member columns of the planes, the steps of
+    a statistics block), drawn with DUMP_SEED from the axis length alone -- the same indices on every run."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outputs))
+    for name, x, axis in outputs:
+        if not x.is_floating_point():
+            x = x.to(torch.float64)
+        n = x.shape[axis]
+        per_index = x.element_size() * (x.numel() // max(1, n))
+        keep = min(n, max(1, share // max(1, per_index)))
+        if keep < n:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+            x = x.index_select(axis, torch.from_numpy(idx).to(x.device))
+        np.save(os.path.join(out_dir, name + ".npy"), x.cpu().numpy())
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher in front: start the N ranks ourselves, exactly as the driver's
     N > 1 command does (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -311,7 +338,16 @@ def main():
     ap.add_argument("--launch-probe", action="store_true",
                     help="development / CPU test: only check that the N ranks come up and can talk (gloo, no GPU "
                          "touched): rank 0 prints {\"launch_probe\": true, \"ranks_seen\": N}")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (NEE / GPP / ET planes, and the gathered block or "
+                         "the filter's ancestors where the timed path returns them) as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything else the line can report: CPU baseline "
+                         "(--no-cpu-baseline), roofline with kernel / setup / plan times, fill probe (--no-fill-probe) and end "
+                         "to end (--no-end-to-end), the N > 1 gather legs, the particle filter's analysis time, oracle parity")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as plain `python bench.py --gpus N`: be our own launcher
@@ -365,7 +401,7 @@ def main():
     members = synth.perturbed_params(base, M * world, seed=synth.SEED_PARAMS)[rank * M:(rank + 1) * M]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # before any HIP initialisation in this process: the workers are plain children
         cpu = cpu_baseline(flags, synth.perturbed_params(base, max(M, 64), seed=synth.SEED_PARAMS),
                            {k: v[:T] for k, v in raws[0].items()}, param_name=param_name)
@@ -462,7 +498,7 @@ def main():
         b.run(0, T, planes=planes)
         # the parity sample is taken from this first forecast: later cycles run RESAMPLED
         # parameter sets (particles carry their parameters), member k is no longer draw k
-        pf_first = planes[:, :, :min(8, M)].double().cpu().numpy()
+        pf_first = planes[:, :, :min(8, M)].double().cpu().numpy() if args.full else None
         tot = planes[0].double().sum(0)
         if distd:
             tot = sd._gather0(tot, world, None).reshape(-1)
@@ -513,6 +549,7 @@ def main():
                 else "torch.distributed process group (direct communicator failed: %s)" % why
     pf_totals = torch.ones(max(args.steps + args.warmup + 1, 1), dtype=torch.int64, device=b.device)
     pf_cycle = [0]
+    pf_ancestors = [None]           # the last analysis' ancestors (--dump-outputs)
 
     def one_pass(record, plain=False):
         """plain: the pass of a single-GPU run (no exchange path at all) -- what --force-dist
@@ -555,14 +592,15 @@ def main():
             slot = pf_totals[pf_cycle[0] % len(pf_totals):][:1]
             pf_cycle[0] += 1
             if distd and not plain and pf_exchange == "peer":
-                _, info = sd.pf_analysis_peers(b, planes[0], pf_obs_k[k], pf_sigma_k[k], 0.5, rank=rank, world=world,
-                                               total_out=slot, collectives=True, diagnostics=record, pretend_world=pretend, comm=pf_comm)
+                pf_ancestors[0], info = sd.pf_analysis_peers(b, planes[0], pf_obs_k[k], pf_sigma_k[k], 0.5, rank=rank, world=world,
+                                                             total_out=slot, collectives=True, diagnostics=record, pretend_world=pretend,
+                                                             comm=pf_comm)
                 if record:
                     pf_info.update(info)
                 return
-            _, info = sd.pf_analysis(b, planes[0], pf_obs_k[k], pf_sigma_k[k], u0=0.5, rank=rank, world=world,
-                                     with_params=True, diagnostics=record, total_out=slot,
-                                     collectives=distd and not plain)
+            pf_ancestors[0], info = sd.pf_analysis(b, planes[0], pf_obs_k[k], pf_sigma_k[k], u0=0.5, rank=rank, world=world,
+                                                   with_params=True, diagnostics=record, total_out=slot,
+                                                   collectives=distd and not plain)
             pf_info.update(info)
             return
         b.setup()                       # setupModel() for every member
@@ -581,7 +619,7 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        one_pass(True)
+        one_pass(args.full)         # (--full: the warm-up passes also record the filter's diagnostics)
     barrier()
     # (one more untimed pass behind the first synchronisation: whatever the process has deferred until then -- the
     # allocator's pending frees of the pre-passes' temporaries were seen to hold the first launch after it back by
@@ -608,6 +646,28 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.rehearse else b.device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if pf:
+        pf_info["exchange"] = pf_exchange
+        pf_info["collective"] = pf_collective
+
+    # --dump-outputs: what a caller of the timed path holds after its last step, before anything below reuses the buffers
+    if args.dump_outputs and rank == 0:
+        if overlap:
+            last = bufs[(npass[0] - 1) & 1]
+            if args.gather == "sums":       # every rank's member sums [world][3][groups][ncol]; no planes were written
+                outs = [(v + "_sums", last["gathered"][:, i], 2) for i, v in enumerate(("nee", "gpp", "et"))]
+            else:                           # this rank's planes + the whole ensemble's statistics block (as --dump-stats)
+                g = last["gathered"]
+                total = g.sum(0) if S == 1 else torch.cat([g[r] for r in range(world)], dim=2)
+                outs = [(v, last["planes"][i], 1) for i, v in enumerate(("nee", "gpp", "et"))] + [("stats", total, 1)]
+        elif distd and args.gather == "full" and not pf:     # every rank's planes [world][T][ncol]
+            outs = [(v, gathered_full[:, i], 2) for i, v in enumerate(("nee", "gpp", "et"))]
+        else:
+            outs = [(v, planes[i], 1) for i, v in enumerate(("nee", "gpp", "et"))]
+            if pf:
+                outs.append(("ancestors", pf_ancestors[0], 0))
+        dump_outputs(args.dump_outputs, outs)
+
     # --force-dist: the same K passes without the exchange path, and the difference per pass
     dist_overhead = None
     if args.force_dist:
@@ -635,32 +695,34 @@ def main():
                                     else f"gather={args.gather} in line")
                                  + ") against K plain passes; the link time of a real N-rank exchange is not in it"}
 
-    # dominant kernel's launch duration (HIP events on the launch stream, inside the library) and
+    li = b.last_launch()            # (the launch shape of the timed step kernel: host-side bookkeeping, no GPU work)
+    # --full: dominant kernel's launch duration (HIP events on the launch stream, inside the library) and
     # the per-pass setupModel() kernel (torch events on the same, current, stream)
-    kms, sms = [], []
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(max(3, min(args.steps, 5))):
-        e0.record()
+    if args.full:
+        kms, sms = [], []
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(max(3, min(args.steps, 5))):
+            e0.record()
+            b.setup()
+            e1.record()
+            b.time_next_launch()            # (short launches -- the filter's 48-step forecast -- are timed on request only)
+            b.run(0, T, planes=planes)
+            torch.cuda.synchronize()
+            kms.append(b.last_kernel_ms())
+            sms.append(e0.elapsed_time(e1))
+        k_ms = float(np.mean(kms))
+        setup_ms = float(np.mean(sms))
+        li = b.last_launch()
+        plan_first = li["plan_build_ms"] + li["plan_upload_ms"]   # incl. the process's first-use costs of the runtime
+        # the steady-state cost of a new forcing: hand the same climate over again and re-plan
+        for s in range(S):
+            b.set_climate(s, clims[s])
         b.setup()
-        e1.record()
-        b.time_next_launch()            # (short launches -- the filter's 48-step forecast -- are timed on request only)
         b.run(0, T, planes=planes)
         torch.cuda.synchronize()
-        kms.append(b.last_kernel_ms())
-        sms.append(e0.elapsed_time(e1))
-    k_ms = float(np.mean(kms))
-    setup_ms = float(np.mean(sms))
-    li = b.last_launch()
-    plan_first = li["plan_build_ms"] + li["plan_upload_ms"]   # incl. the process's first-use costs of the runtime
-    # the steady-state cost of a new forcing: hand the same climate over again and re-plan
-    for s in range(S):
-        b.set_climate(s, clims[s])
-    b.setup()
-    b.run(0, T, planes=planes)
-    torch.cuda.synchronize()
-    li = b.last_launch()
-    plan_ms = li["plan_build_ms"] + li["plan_upload_ms"]   # site plans + the record type this kernel reads
-    if pf:   # the analysis step alone, torch events on the current stream (all its work is there)
+        li = b.last_launch()
+        plan_ms = li["plan_build_ms"] + li["plan_upload_ms"]   # site plans + the record type this kernel reads
+    if args.full and pf:   # the analysis step alone, torch events on the current stream (all its work is there)
         ams = []
         for _ in range(3):
             b.setup()
@@ -677,8 +739,6 @@ def main():
             torch.cuda.synchronize()
             ams.append(e0.elapsed_time(e1))
         pf_info["analysis_ms"] = float(np.mean(ams))
-        pf_info["exchange"] = pf_exchange
-        pf_info["collective"] = pf_collective
 
     # N > 1: the north star's exchange as written -- the member-resolved NEE/GPP/ET block of every
     # rank all-gathered -- measured in an extra untimed pass: the launch is cut into 10 segments
@@ -724,7 +784,7 @@ def main():
         except Exception as e:   # noqa: BLE001
             return {"error": repr(e)[:300]}
 
-    if distd and not pf:
+    if args.full and distd and not pf:
         gather_full = tolerant(leg_gather_full)
 
     # ... and the member-resolved form that fits under the kernel: every member's sums over --sum-steps steps (daily sums of a
@@ -763,7 +823,7 @@ def main():
                        "note": "one pass with every member's sums over sum_steps steps, summed inside the step kernel's launch, "
                                "all-gathered from every rank (segment k travels under the kernel of segment k+1)"}
 
-    if distd and not pf and b.sums_in_kernel():
+    if args.full and distd and not pf and b.sums_in_kernel():
         gather_sums = tolerant(leg_gather_sums)
 
     if args.dump_stats and not pf:
@@ -782,11 +842,10 @@ def main():
     units_per_pass = S * M * T * world
     value = units_per_pass * args.steps / dt
     per_launch_units = S * M * T
-    achieved = ALGO_BYTES[wl["prec"]] * per_launch_units / (k_ms * 1e-3) / 1e9
 
     # parity spot-check of this very run against the CPU oracle (checker only)
     parity = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             from tests import helpers
             ora = helpers.load_oracle()
@@ -812,7 +871,7 @@ def main():
 
     traffic, traffic_tag, valu_cycles = None, None, None
     tpath = os.path.join(REPO, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath):
+    if args.full and os.path.exists(tpath):
         try:
             ent = json.load(open(tpath)).get(args.workload, {})
             # only valid for the kernel it was collected on
@@ -831,7 +890,7 @@ def main():
     # memory, build + upload the site plan, setupModel(), the step kernel with the ensemble statistics,
     # and bring the statistics block back to the host -- what a caller pays per forcing + ensemble
     end_to_end = None
-    if rank == 0 and not pf and not args.no_end_to_end:
+    if args.full and rank == 0 and not pf and not args.no_end_to_end:
         try:
             host_stats = torch.empty(stats.shape, dtype=torch.float64, pin_memory=True)
 
@@ -909,18 +968,13 @@ def main():
             end_to_end = {"error": repr(e)}
 
     probe = None
-    if rank == 0 and world == 1 and not args.no_fill_probe and not pf and args.fast_math:
+    if args.full and rank == 0 and world == 1 and not args.no_fill_probe and not pf and args.fast_math:
         try:
             probe = fill_probe(sa, synth, flags, base, wl["prec"], local_rank)
         except Exception as e:
             probe = {"error": repr(e)}
 
     if rank == 0:
-        waves_per_block = li["block_threads"] // 64
-        if "Pair" in li["kernel"]:
-            waves_per_block = 6      # two of the eight wavefronts only keep the SIMD rotation and leave at once
-        cus_used = min(li["grid"], li["num_cus"]) if "Coop" in li["kernel"] else min((li["grid"] + 3) // 4, li["num_cus"])
-        simds_used = min(li["grid"] * min(waves_per_block, 4), 4 * li["num_cus"])
         line = {
             "metric": "ensemble-site-timesteps/sec", "value": value,
             "unit": "ensemble-site-timesteps/s", "n_gpus": world, "steps": args.steps,
@@ -938,33 +992,42 @@ def main():
                        "ranks_seen": ranks_seen, "devices_seen": devices_seen, "device_ids": device_ids,
                        **({"gather_full": gather_full} if gather_full else {}),
                        **({"gather_sums": gather_sums} if gather_sums else {}),
-                       **({"particle_filter": pf_info} if pf else {})},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                         "traffic_tag": traffic_tag,
-                         "hbm_measured_frac": (traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if traffic else None,
-                         "kernel": li["kernel"], "kernel_ms": k_ms,
-                         "grid": li["grid"], "block_threads": li["block_threads"],
-                         "waves_per_simd": li["grid"] * waves_per_block / (4.0 * li["num_cus"]),
-                         "waves_per_simd_register_budget": li["waves_per_simd"],
-                         "cus_used": cus_used, "cus_total": li["num_cus"],
-                         "simds_used": simds_used, "simds_total": 4 * li["num_cus"],
-                         "lds_bytes_per_workgroup": li["lds_bytes"],
-                         # the PHYSICAL ceiling beside the contract number (SURVEY 8(d) "ALU cross-check"): the share of
-                         # SIMD-cycles in which a vector ALU was executing -- SQ_ACTIVE_INST_VALU x 4 of the committed
-                         # profile (profiles/pmc_traffic.json, like `traffic`) over SIMDs x this run's kernel time at
-                         # the 2.4 GHz peak clock (a lower clock under load makes the true fraction higher)
-                         "valu_busy_frac": (valu_cycles / (4.0 * li["num_cus"] * k_ms * 1e-3 * SCLK_PEAK_HZ)) if valu_cycles else None,
-                         "valu_busy_frac_of_used_simds": (valu_cycles / (simds_used * k_ms * 1e-3 * SCLK_PEAK_HZ)) if valu_cycles else None,
-                         "valu_clock_ghz_assumed": SCLK_PEAK_HZ / 1e9,
-                         "issue_frac": (per_launch_units / (k_ms * 1e-3) / probe["rate"]) if probe and "rate" in probe else None,
-                         "fill_probe": probe,
-                         "plan_ms": plan_ms, "plan_ms_first_in_process": plan_first, "plan_build_ms": li["plan_build_ms"], "plan_upload_ms": li["plan_upload_ms"], "plan_threads": li["plan_threads"], "setup_ms": setup_ms,
-                         "end_to_end": end_to_end,
-                         "algorithmic_bytes_per_unit": ALGO_BYTES[wl["prec"]],
-                         "units_per_launch": per_launch_units},
-            "cpu_baseline": cpu, "parity": parity,
+                       **({"particle_filter": pf_info} if pf else {}),
+                       "kernel": li["kernel"]},
+            "full": args.full,
         }
+        if args.full:
+            achieved = ALGO_BYTES[wl["prec"]] * per_launch_units / (k_ms * 1e-3) / 1e9
+            waves_per_block = li["block_threads"] // 64
+            if "Pair" in li["kernel"]:
+                waves_per_block = 6      # two of the eight wavefronts only keep the SIMD rotation and leave at once
+            cus_used = min(li["grid"], li["num_cus"]) if "Coop" in li["kernel"] else min((li["grid"] + 3) // 4, li["num_cus"])
+            simds_used = min(li["grid"] * min(waves_per_block, 4), 4 * li["num_cus"])
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                                "traffic_tag": traffic_tag,
+                                "hbm_measured_frac": (traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if traffic else None,
+                                "kernel": li["kernel"], "kernel_ms": k_ms,
+                                "grid": li["grid"], "block_threads": li["block_threads"],
+                                "waves_per_simd": li["grid"] * waves_per_block / (4.0 * li["num_cus"]),
+                                "waves_per_simd_register_budget": li["waves_per_simd"],
+                                "cus_used": cus_used, "cus_total": li["num_cus"],
+                                "simds_used": simds_used, "simds_total": 4 * li["num_cus"],
+                                "lds_bytes_per_workgroup": li["lds_bytes"],
+                                # the PHYSICAL ceiling beside the contract number (SURVEY 8(d) "ALU cross-check"): the share of
+                                # SIMD-cycles in which a vector ALU was executing -- SQ_ACTIVE_INST_VALU x 4 of the committed
+                                # profile (profiles/pmc_traffic.json, like `traffic`) over SIMDs x this run's kernel time at
+                                # the 2.4 GHz peak clock (a lower clock under load makes the true fraction higher)
+                                "valu_busy_frac": (valu_cycles / (4.0 * li["num_cus"] * k_ms * 1e-3 * SCLK_PEAK_HZ)) if valu_cycles else None,
+                                "valu_busy_frac_of_used_simds": (valu_cycles / (simds_used * k_ms * 1e-3 * SCLK_PEAK_HZ)) if valu_cycles else None,
+                                "valu_clock_ghz_assumed": SCLK_PEAK_HZ / 1e9,
+                                "issue_frac": (per_launch_units / (k_ms * 1e-3) / probe["rate"]) if probe and "rate" in probe else None,
+                                "fill_probe": probe,
+                                "plan_ms": plan_ms, "plan_ms_first_in_process": plan_first, "plan_build_ms": li["plan_build_ms"], "plan_upload_ms": li["plan_upload_ms"], "plan_threads": li["plan_threads"], "setup_ms": setup_ms,
+                                "end_to_end": end_to_end,
+                                "algorithmic_bytes_per_unit": ALGO_BYTES[wl["prec"]],
+                                "units_per_launch": per_launch_units}
+            line["cpu_baseline"], line["parity"] = cpu, parity
         print(json.dumps(line))
     if distd:
         dist.destroy_process_group()

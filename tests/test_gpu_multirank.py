@@ -44,7 +44,7 @@ def test_two_ranks_rehearsed_on_one_gpu_equal_a_single_process(workload, members
     r2 = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), BENCH, "--gpus", "2",
-         "--rehearse", "--members", str(members), "--dump-stats", two] + common,
+         "--rehearse", "--members", str(members), "--dump-stats", two, "--full"] + common,
         capture_output=True, text=True, timeout=600, env=env, cwd=helpers.REPO)
     assert r2.returncode == 0, r2.stdout[-2000:] + r2.stderr[-3000:]
     j2 = _last_json(r2.stdout)
@@ -73,7 +73,7 @@ def test_bench_launches_its_own_ranks():
     child before anything touches the GPU and relays rank 0's one JSON line and the child's return code"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--rehearse", "--workload", "c2", "--nsteps", "480",
-                        "--steps", "2", "--warmup", "1", "--no-fill-probe", "--no-end-to-end"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-fill-probe", "--no-end-to-end"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=helpers.REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -90,7 +90,7 @@ def test_two_ranks_gather_every_members_daily_sums(workload, members, kernel):
     segments) is compared with the planes of a plain pass by bench.py itself"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--rehearse", "--workload", workload, "--nsteps", str(48 * 20 + 7),
-                        "--gather", "sums", "--steps", "2", "--warmup", "1", "--no-fill-probe", "--no-end-to-end", "--no-cpu-baseline"],
+                        "--gather", "sums", "--steps", "2", "--warmup", "1", "--full", "--no-fill-probe", "--no-end-to-end", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=helpers.REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = _last_json(r.stdout)
@@ -116,7 +116,7 @@ def test_particle_filter_cycle_two_ranks_rehearsed(tmp_path, exchange):
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), BENCH, "--gpus", "2",
          "--rehearse", "--workload", "c5", "--members", "4096", "--steps", "3", "--warmup", "1",
-         "--no-cpu-baseline", "--no-fill-probe", "--pf-exchange", exchange],
+         "--full", "--no-cpu-baseline", "--no-fill-probe", "--pf-exchange", exchange],
         capture_output=True, text=True, timeout=600, env=env, cwd=helpers.REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = _last_json(r.stdout)
@@ -138,7 +138,7 @@ def _rccl_one_rank(args, tmp_path, timeout=900):
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
          "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), BENCH, "--gpus", "1",
-         "--force-dist", "--no-cpu-baseline", "--no-fill-probe"] + args,
+         "--force-dist", "--full", "--no-cpu-baseline", "--no-fill-probe"] + args,
         capture_output=True, text=True, timeout=timeout, env=env, cwd=helpers.REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     return _last_json(r.stdout)

@@ -7,7 +7,7 @@ name=$1; shift
 for wl in "$@"; do
   for rep in 1 2 3; do
     for tree in . build/$name; do
-      (cd $tree && timeout 300 python bench.py --workload $wl --steps 5 --warmup 2 --no-cpu-baseline --no-fill-probe --no-end-to-end 2>/dev/null | python -c "
+      (cd $tree && timeout 300 python bench.py --workload $wl --steps 5 --warmup 2 --full --no-cpu-baseline --no-fill-probe --no-end-to-end 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

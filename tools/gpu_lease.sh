@@ -4,7 +4,7 @@
 # Results land under gpurun_out/<tag>/ (copy what is to be judged into profiles/).  Recipes:
 #   suite          the whole GPU test suite (pytest -m gpu)
 #   tests:<expr>   pytest -m gpu -k <expr>
-#   bench          the driver's default bench line
+#   bench          the driver's default bench line, with everything --full adds
 #   bench_all      one bench line per workload (no CPU baseline) -> bench_all.jsonl
 #   force_dist     bench.py --force-dist for every workload + c5 at --pretend-world 8 -> force_dist.jsonl
 #   pf             the cross-rank analysis at the slot counts of 1 / 2 / 4 / 8 ranks (tools/pf_peers_time.py), plain and
@@ -34,13 +34,13 @@ for R in "$@"; do
     smoke)
       timeout 600 python3 -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.txt 2>&1; tail -3 $O/smoke.txt ;;
     bench)
-      timeout 1200 python3 bench.py > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log | tail -1 > $O/bench_default.json
+      timeout 1200 python3 bench.py --full > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log | tail -1 > $O/bench_default.json
       python3 -c "import json; d=json.load(open('$O/bench_default.json')); print('value %.4g %s, ms/step %.3f, roofline %s' % (d['value'], d['unit'], d['ms_per_step'], {k: d['roofline'][k] for k in ('achieved', 'frac', 'traffic')}))" ;;
     bench_all)
       : > $O/bench_all.jsonl
       for wl in c10k c2 c2x16 c3 c4 c5 c10kn c10kr3 c4n; do
         steps=10; warm=2; [ "$wl" = c5 ] && steps=400 && warm=40
-        timeout 900 python3 bench.py --workload $wl --steps $steps --warmup $warm --no-cpu-baseline > $O/bench_$wl.log 2>&1
+        timeout 900 python3 bench.py --workload $wl --steps $steps --warmup $warm --full --no-cpu-baseline > $O/bench_$wl.log 2>&1
         grep '^{' $O/bench_$wl.log | tail -1 >> $O/bench_all.jsonl
         grep '^{' $O/bench_$wl.log | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$wl', 'value %.4g' % d['value'], 'ms/step %.4f' % d['ms_per_step'], 'frac %.3f' % d['roofline']['frac'], d['roofline'].get('kernel', '')[:60])"
       done ;;
@@ -58,7 +58,7 @@ for R in "$@"; do
         [ "$wl" = c5torch ] && steps=400 && warm=40 && extra="--pf-collective torch" && w=c5
         [ "$wl" = c5p8torch ] && steps=400 && warm=40 && extra="--pretend-world 8 --pf-collective torch" && w=c5
         timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-            bench.py --gpus 1 --force-dist --workload $w $extra --steps $steps --warmup $warm --no-cpu-baseline --no-fill-probe > $O/force_dist_$wl.log 2>&1
+            bench.py --gpus 1 --force-dist --full --workload $w $extra --steps $steps --warmup $warm --no-cpu-baseline --no-fill-probe > $O/force_dist_$wl.log 2>&1
         echo "rc=$? $wl"
         grep '^{' $O/force_dist_$wl.log | tail -1 >> $O/force_dist.jsonl
       done
@@ -81,10 +81,10 @@ PY
       cp $(find /tmp/prof_pf -name "*kernel_stats.csv" | head -1) $O/pf_peers_w8_kernel_stats.csv 2>/dev/null
       head -12 $O/pf_peers_w8_kernel_stats.csv | cut -c1-160 ;;
     profile:*)
-      wl=${R#profile:}; rm -rf /tmp/prof_$wl
+      wl=${R#profile:}; rm -rf "$TMPDIR/prof_$wl"
       steps=10; warm=2; [ "$wl" = c5 ] && steps=400 && warm=40
-      timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$wl -- python3 bench.py --workload $wl --steps $steps --warmup $warm --no-cpu-baseline --no-fill-probe --no-end-to-end > $O/profile_$wl.log 2>&1
-      cp $(find /tmp/prof_$wl -name "*kernel_stats.csv" | head -1) $O/${wl}_kernel_stats.csv 2>/dev/null
+      timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR/prof_$wl" -- python3 bench.py --workload $wl --steps $steps --warmup $warm --full --no-cpu-baseline --no-fill-probe --no-end-to-end > $O/profile_$wl.log 2>&1
+      cp $(find "$TMPDIR/prof_$wl" -name "*kernel_stats.csv" | head -1) $O/${wl}_kernel_stats.csv 2>/dev/null
       head -6 $O/${wl}_kernel_stats.csv | cut -c1-200 ;;
     node_gather)
       for d in 0 0,0; do timeout 600 python3 tools/node_gather_time.py 10240 1 $d 2>&1 | grep -v amdgpu.ids > $O/node_gather_time_$d.txt; cat $O/node_gather_time_$d.txt; done ;;
@@ -107,7 +107,7 @@ PY
       "$0" $TAG bench_all force_dist pf node_gather pf_consumer sums_time
       for wl in c3 c5 c4; do bash tools/gpu_pmc_branch.sh $wl > /dev/null 2>&1; cp gpurun_out/pmc_branch_$wl.txt $O/; done
       for wl in c4 c2x16 c10k; do for who in dev host; do timeout 600 python3 tools/e2e_breakdown.py $wl $who 2>&1 | grep -v amdgpu > $O/e2e_${wl}_$who.txt; done; done
-      timeout 900 python3 bench.py > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log | tail -1 > $O/bench_default.json ;;
+      timeout 900 python3 bench.py --full > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log | tail -1 > $O/bench_default.json ;;
     sums_time)
       { timeout 300 python3 tools/sums_time.py 10240 1 5 f64; timeout 300 python3 tools/sums_time.py 1024 32 5 f64; timeout 300 python3 tools/sums_time.py 40960 1 5 f64
         timeout 300 python3 tools/sums_time.py 65536 1 5 f32; timeout 300 python3 tools/sums_time.py 32768 1 5 f32; timeout 300 python3 tools/sums_time.py 16384 1 5 f32; } 2>&1 | grep -v amdgpu.ids > $O/sums_time.txt

@@ -456,6 +456,26 @@ def debug_log_cases():
         print("debug log", case, n, "rows, kept", len(idx))
 
 
+def restart_reader_codes():
+    """The reference binary's exit code when it resumes from each edited checkpoint of
+    tests/test_restart_io.py (EDITS): the test holds the engine's reader to these codes on any
+    machine, and re-runs the binary where oracle/_ref is built."""
+    import json
+    import pathlib
+    from tests import test_restart_io as t
+    codes = {}
+    tmp = pathlib.Path(tempfile.mkdtemp(prefix="restart_codes_"))
+    for name, fn in sorted(t.EDITS.items()):
+        d = tmp / name
+        d.mkdir()
+        codes[name] = t.reference_exit_code(REF_BIN, d, t.edited(d, fn), t._segment2(d))
+    shutil.rmtree(tmp)
+    with open(os.path.join(GOLD, "restart", "reader_exit_codes.json"), "w") as f:
+        json.dump(codes, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("restart reader exit codes", codes)
+
+
 if __name__ == "__main__":
     subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "oracle"), "ref", "oracle"])
     copy_smoke()
@@ -463,6 +483,7 @@ if __name__ == "__main__":
     synthetic()
     warning_counts()
     restart_cases()
+    restart_reader_codes()
     balance_case()
     events_infra_case()
     sipnet_infra_case()

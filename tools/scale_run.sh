@@ -32,7 +32,7 @@ fi
 # 2. the bench contract's lines (bench.py launches its own ranks)
 line() {   # line <tag> <bench args...>: one bench run, its JSON line tagged and appended
   local tag=$1; shift
-  timeout 1500 python3 bench.py "$@" > $O/bench_$tag.log 2>&1
+  timeout 1500 python3 bench.py --full "$@" > $O/bench_$tag.log 2>&1
   local rc=$?
   local j=$(grep '^{' $O/bench_$tag.log | tail -1)
   if [ -n "$j" ]; then echo "$j" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); d['leg']='$tag'; d['rc']=$rc; print(json.dumps(d))" >> $O/scale_lines.jsonl
