@@ -468,7 +468,8 @@ int sipnet_batch_export_restart(sipnet_batch *b, int32_t site, int32_t member,
  * the GLOBAL particle set (computed redundantly and bit-identically on every rank) ->
  * pack_members for the columns other ranks need -> [all-to-all] -> resample.  What moves per
  * particle is its checkpoint: the carried state vector and ring (+ converted parameters
- * when particles carry their own parameters).  One site per batch.
+ * when particles carry their own parameters).  One site per batch (many sites, a filter each:
+ * sipnet_batch_pf_analysis_sites).
  *
  * logw[col] = -0.5 * ((sum_t plane[t][col] - obs) / sigma)^2 (Gaussian likelihood of an
  * observed flux sum, e.g. daily NEE); -inf for members whose status is non-zero. */
@@ -536,6 +537,25 @@ int sipnet_batch_resample(sipnet_batch *b, const int32_t *d_src, const double *d
 int sipnet_batch_pf_analysis(sipnet_batch *b, const void *d_plane, int32_t elem_is_f32, int32_t n_steps,
                              int64_t ld, double obs, double sigma, double u0, int32_t with_params,
                              double *d_logw, int32_t *d_ancestors, int64_t *d_total, void *hip_stream);
+/* The same for a batch of many sites, each site a filter of its own.  Site s owns columns [s M, (s + 1) M),
+ * M = n_members.  All pointers are DEVICE pointers: d_obs, d_sigma, d_u0 [n_sites]; d_logw, d_ancestors and
+ * d_fixed_weights (may be NULL) [ncol]; d_site_total [n_sites] (may be NULL).  Per site: logw as
+ * sipnet_batch_pf_log_weights with obs[s], sigma[s]; w = llrint(exp(logw - m_s) * 2^30) with m_s the site's
+ * maximum; S_s = sum of the site's w; ancestor[s M + j] = s M + (first i with cdf_s[i] > min(((j + u0[s]) S_s) / M,
+ * S_s - 1)): a global column inside the site's own range.  site_total[s] = S_s, or
+ *   -1  obs[s] is NaN (no observation): identity ancestors, logw and w 0;
+ *   -2  a non-finite obs, sigma not finite and > 0, or u0 outside [0, 1): identity ancestors, logw and w 0;
+ *    0  no particle of the site has status 0: identity ancestors (sipnet_batch_pf_analysis puts them all on slot 0).
+ * Then sipnet_batch_resample with the ancestors (with_params: as there).  Everything is enqueued on hip_stream.
+ * d_site_total given: nothing is synchronised.  NULL: the totals are read back (hip_stream is synchronised) before
+ * the gather; a site at -2 gives SIPNET_ERR_BAD_ARGUMENT, else an analysed site at 0 SIPNET_ERR_BAD_PARAMETER, naming
+ * the first such site, and nothing is resampled.  SIPNET_ERR_BAD_ARGUMENT before any launch: a NULL required pointer,
+ * n_steps <= 0, ld < ncol, ncol > 4 194 304, a batch connected by sipnet_batch_pf_connect.  With n_sites = 1 and
+ * S > 0 the results are sipnet_batch_pf_analysis's, bit for bit. */
+int sipnet_batch_pf_analysis_sites(sipnet_batch *b, const void *d_plane, int32_t elem_is_f32, int32_t n_steps,
+                                   int64_t ld, const double *d_obs, const double *d_sigma, const double *d_u0,
+                                   int32_t with_params, double *d_logw, int32_t *d_ancestors,
+                                   int64_t *d_fixed_weights, int64_t *d_site_total, void *hip_stream);
 
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its

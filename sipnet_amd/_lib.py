@@ -158,6 +158,8 @@ SIGNATURES = {
     "sipnet_batch_member_words": (C.c_int32, [C.c_void_p, C.c_int32]),
     "sipnet_batch_pf_analysis": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_double,
                                            C.c_int32, _P, _P, _P, _P]),
+    "sipnet_batch_pf_analysis_sites": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, _P,
+                                                 _P, _P, _P]),
     "sipnet_batch_pf_publish": (C.c_int, [_P, C.c_int32, _P]),
     "sipnet_batch_pf_connect": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "sipnet_batch_pf_block_len": (C.c_int64, [_P]),

@@ -338,6 +338,32 @@ class Batch:
             self._stream()), "pf_analysis")
         return anc, logw
 
+    def pf_analysis_sites(self, plane, obs, sigma, u0, with_params=False, total_out=None, return_fixed=False):
+        """every site a filter of its own, one library call (sipnet_batch_pf_analysis_sites): obs, sigma, u0 hold one
+        value per site (array-likes, uploaded as float64, or float64 device tensors; obs NaN: no observation).
+        total_out: int64 device tensor [n_sites] for the sites' total weights (no host synchronisation).  Returns
+        (ancestors int32 [ncol] -- global columns --, logw f64 [ncol][, fixed-point weights int64 [ncol]]) on the device."""
+        t = self._torch
+
+        def per_site(x):
+            x = t.as_tensor(x, dtype=t.float64).reshape(-1).to(self.device).contiguous()
+            assert x.numel() == self.n_sites
+            return x
+
+        obs, sigma, u0 = per_site(obs), per_site(sigma), per_site(u0)
+        logw = t.empty(self.ncol, dtype=t.float64, device=self.device)
+        anc = t.empty(self.ncol, dtype=t.int32, device=self.device)
+        fixed = t.empty(self.ncol, dtype=t.int64, device=self.device) if return_fixed else None
+        if total_out is not None:
+            assert total_out.dtype == t.int64 and total_out.is_contiguous() and total_out.numel() == self.n_sites
+        check(self.L.sipnet_batch_pf_analysis_sites(
+            self.h, C.c_void_p(plane.data_ptr()), int(plane.dtype == t.float32), plane.shape[0], plane.shape[1],
+            C.c_void_p(obs.data_ptr()), C.c_void_p(sigma.data_ptr()), C.c_void_p(u0.data_ptr()), int(with_params),
+            C.c_void_p(logw.data_ptr()), C.c_void_p(anc.data_ptr()),
+            C.c_void_p(fixed.data_ptr()) if fixed is not None else None,
+            C.c_void_p(total_out.data_ptr()) if total_out is not None else None, self._stream()), "pf_analysis_sites")
+        return (anc, logw, fixed) if return_fixed else (anc, logw)
+
     # -- the filter across ranks by peer reads (sipnet_batch_pf_publish / _connect / _resample_peers) ----------
     def pf_publish(self, with_params=True):
         """-> bytes of this batch's sipnet_pf_peer descriptor (exchange them, then pf_connect)"""

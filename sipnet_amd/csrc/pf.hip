@@ -863,6 +863,243 @@ __global__ __launch_bounds__(256) void copyRowsKernel(double* __restrict__ dst, 
   for (int r = blockIdx.y; r < rows; r += gridDim.y) dst[(int64_t)r * dstPitch + c] = src[(int64_t)r * srcPitch + c];
 }
 
+// ---- the analysis of a batch of many sites (sipnet_batch_pf_analysis_sites) -------------------------------------------
+// Site s owns columns [s M, (s + 1) M) and is a filter of its own: its own maximum, integer prefix sum and systematic draw, its
+// ancestors inside its own range.  Sites never wait for each other: one workgroup per site (pfSitesKernel) when the sites
+// are small and at least as many as the CUs, else three launches (sitesChunkKernel | sitesWeightKernel | sitesAncestorKernel)
+// -- no grid barrier, no spin, no atomic in either.  The values are pfFixedWeight's and ancestorKernel's rule, so one site gives
+// sipnet_batch_pf_analysis's bits.
+constexpr int kSitesLds = 4096;      // sites of at most this many particles: one workgroup, the site's weights in LDS (32 KB)
+constexpr int kSitesMaxChunks = 1024;   // the split path: chunks per site at most (a chunk: 256 x 1, 2, .. 16 columns)
+constexpr long long kSiteMissing = -1, kSiteInvalid = -2;   // site totals of a site without an observation / with bad arguments
+// 0: analysed; kSiteMissing: obs is NaN; kSiteInvalid: a non-finite obs, sigma not finite and > 0, u0 outside [0, 1)
+__device__ __forceinline__ long long siteKind(double obs, double sigma, double u0) {
+  if (obs != obs) return kSiteMissing;
+  if (!(fabs(obs) < INFINITY) || !(sigma > 0.0) || !(sigma < INFINITY) || !(u0 >= 0.0) || !(u0 < 1.0)) return kSiteInvalid;
+  return 0;
+}
+struct SitesArgs {
+  const void* plane;
+  int32_t nSteps;
+  int64_t ld;
+  int64_t M;                  // particles per site
+  int32_t nChunks;            // split path: chunks per site
+  int32_t chunk;              // ... of `chunk` columns: 256 x the smallest power of two that needs at most kSitesMaxChunks
+  const double* status;
+  const double* obs;          // [n_sites]
+  const double* sigma;
+  const double* u0;
+  double* logw;               // [ncol]
+  int64_t* w;                 // [ncol] fixed-point weights: the caller's, or scratch (split path; pfSitesKernel: may be null)
+  int32_t* anc;               // [ncol] global columns
+  int64_t* total;             // [n_sites] scratch, always written
+  int64_t* totalOut;          // [n_sites] the caller's, may be null
+  double* chunkMax;           // split path: [n_sites][nChunks]
+  int64_t* chunkSum;          // [n_sites][nChunks]
+  int64_t* threadIncl;        // [n_sites][nChunks][256] every thread's inclusive sum inside its chunk
+};
+// p(j) of ancestorKernel, for a site of M particles and total weight S
+__device__ __forceinline__ double sitePoint(int64_t j, double u0, double S, double M) {
+  return fmin((((double)j + u0) * S) / M, S - 1.0);
+}
+__device__ __forceinline__ void siteIdentity(const SitesArgs& a, int s, int64_t base, long long kind) {
+  for (int64_t i = threadIdx.x; i < a.M; i += 256) a.anc[base + i] = (int32_t)(base + i);
+  if (threadIdx.x == 0) {
+    a.total[s] = kind;
+    if (a.totalOut) a.totalOut[s] = kind;
+  }
+}
+// a site that is not analysed (kind < 0): log-weights and weights 0, the particles stay
+__device__ __forceinline__ void siteSkip(const SitesArgs& a, int64_t base) {
+  for (int64_t i = threadIdx.x; i < a.M; i += 256) {
+    a.logw[base + i] = 0.0;
+    if (a.w) a.w[base + i] = 0;
+  }
+}
+// One workgroup = one site (blockIdx.x), M <= kSitesLds: log-weights (lanes on neighbouring columns) and their maximum | the
+// fixed-point weights of CONSECUTIVE slots per thread, one block scan | every particle's slot: bisection over the 256 inclusive
+// sums, then a walk of that thread's weights.  The weights stay in LDS from phase 1 (as log-weights) to phase 3.
+template <typename T>
+__global__ __launch_bounds__(256) void pfSitesKernel(SitesArgs a) {
+  __shared__ double smD[256];
+  __shared__ long long smWave[4];
+  __shared__ long long incl[256];
+  __shared__ union { double lw[kSitesLds]; long long w[kSitesLds]; } site;
+  const int tid = (int)threadIdx.x, s = (int)blockIdx.x;
+  const int64_t M = a.M, base = (int64_t)s * M;
+  const double obs = a.obs[s], sigma = a.sigma[s], u0 = a.u0[s];
+  const long long kind = siteKind(obs, sigma, u0);
+  if (kind < 0) {
+    siteSkip(a, base);
+    siteIdentity(a, s, base, kind);
+    return;
+  }
+  const double invSigma = 1.0 / sigma;
+  double mine = -INFINITY;
+  for (int i = tid; i < M; i += 256) {
+    const double lw = logWeightOf((const T*)a.plane, a.nSteps, a.ld, base + i, a.status, obs, invSigma, a.logw);
+    site.lw[i] = lw;
+    mine = fmax(mine, lw);
+  }
+  const double m = blockMax256(mine, smD);   // (its __syncthreads: every log-weight is in LDS)
+  const int per = (int)((M + 255) >> 8);
+  const int t0 = tid * per < M ? tid * per : (int)M, t1 = t0 + per < M ? t0 + per : (int)M;
+  long long mySum = 0;
+  for (int i = t0; i < t1; i++) {   // (this thread's slots only: the log-weight becomes the weight in place)
+    const long long w = pfFixedWeight(site.lw[i], m);
+    site.w[i] = w;
+    mySum += w;
+  }
+  long long Sll;
+  incl[tid] = blockScan256(mySum, smWave, &Sll);   // (its __syncthreads: every weight is in LDS)
+  __syncthreads();
+  if (a.w)
+    for (int i = tid; i < M; i += 256) a.w[base + i] = site.w[i];
+  if (Sll == 0) {   // nobody of this site ran: it keeps its particles (the other sites go on)
+    siteIdentity(a, s, base, 0);
+    return;
+  }
+  const double S = (double)Sll, Md = (double)M;
+  for (int j = tid; j < M; j += 256) {
+    const double p = sitePoint(j, u0, S, Md);
+    int tl = 0, th = 255;   // first thread with (double)incl > p (incl[255] = S > p: exists)
+    while (tl < th) {
+      const int mid = (tl + th) >> 1;
+      if ((double)incl[mid] > p) th = mid; else tl = mid + 1;
+    }
+    long long run = tl > 0 ? incl[tl - 1] : 0;
+    const int i0 = tl * per, iEnd = i0 + per < M ? i0 + per : (int)M;
+    int found = iEnd - 1;
+    for (int i = i0; i < iEnd; i++) {
+      run += site.w[i];
+      if ((double)run > p) { found = i; break; }
+    }
+    a.anc[base + j] = (int32_t)(base + found);
+  }
+  if (tid == 0) {
+    a.total[s] = Sll;
+    if (a.totalOut) a.totalOut[s] = Sll;
+  }
+}
+// split path, launch 1: chunk blockIdx.y of site blockIdx.x (x: up to 2^22 sites; y: at most 1024 chunks) -- log-weights and
+// their maximum
+template <typename T>
+__global__ __launch_bounds__(256) void sitesChunkKernel(SitesArgs a) {
+  __shared__ double smD[256];
+  const int s = (int)blockIdx.x, k = (int)blockIdx.y;
+  const int64_t base = (int64_t)s * a.M, lo = (int64_t)k * a.chunk, hi = lo + a.chunk < a.M ? lo + a.chunk : a.M;
+  const double obs = a.obs[s], sigma = a.sigma[s];
+  if (siteKind(obs, sigma, a.u0[s]) < 0) {   // (launch 2 writes the zeros)
+    if (threadIdx.x == 0) a.chunkMax[(int64_t)s * a.nChunks + k] = -INFINITY;
+    return;
+  }
+  const double invSigma = 1.0 / sigma;
+  double mine = -INFINITY;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += 256)
+    mine = fmax(mine, logWeightOf((const T*)a.plane, a.nSteps, a.ld, base + i, a.status, obs, invSigma, a.logw));
+  mine = blockMax256(mine, smD);
+  if (threadIdx.x == 0) a.chunkMax[(int64_t)s * a.nChunks + k] = mine;
+}
+// launch 2: the site's maximum, the chunk's fixed-point weights (chunk / 256 consecutive slots per thread), one block scan
+__global__ __launch_bounds__(256) void sitesWeightKernel(SitesArgs a) {
+  __shared__ double smD[256];
+  __shared__ long long smWave[4];
+  const int tid = (int)threadIdx.x, s = (int)blockIdx.x, k = (int)blockIdx.y;
+  const int64_t base = (int64_t)s * a.M, lo = (int64_t)k * a.chunk, hi = lo + a.chunk < a.M ? lo + a.chunk : a.M;
+  const int64_t ck = (int64_t)s * a.nChunks + k;
+  if (siteKind(a.obs[s], a.sigma[s], a.u0[s]) < 0) {
+    for (int64_t i = lo + tid; i < hi; i += 256) {
+      a.logw[base + i] = 0.0;
+      a.w[base + i] = 0;
+    }
+    return;
+  }
+  double pm = -INFINITY;
+  for (int q = tid; q < a.nChunks; q += 256) pm = fmax(pm, a.chunkMax[(int64_t)s * a.nChunks + q]);
+  const double m = blockMax256(pm, smD);
+  const int per = a.chunk >> 8;
+  const int64_t t0 = lo + (int64_t)tid * per < hi ? lo + (int64_t)tid * per : hi, t1 = t0 + per < hi ? t0 + per : hi;
+  long long mySum = 0;
+  for (int64_t i = t0; i < t1; i++) {
+    const long long w = pfFixedWeight(a.logw[base + i], m);
+    a.w[base + i] = w;
+    mySum += w;
+  }
+  long long chunkTotal;
+  a.threadIncl[ck * 256 + tid] = blockScan256(mySum, smWave, &chunkTotal);
+  if (tid == 0) a.chunkSum[ck] = chunkTotal;
+}
+// launch 3: particles [256 blockIdx.y, 256 blockIdx.y + 256) of site blockIdx.x -- the chunks' offsets, then each particle's
+// chunk (bisection of the offsets in LDS), thread (bisection of that chunk's 256 inclusive sums) and slot (a walk of that thread's chunk / 256 <= 16 weights)
+__global__ __launch_bounds__(256) void sitesAncestorKernel(SitesArgs a) {
+  __shared__ long long smWave[4];
+  __shared__ long long prefix[kSitesMaxChunks + 1];
+  const int tid = (int)threadIdx.x, s = (int)blockIdx.x, nCh = a.nChunks;
+  const int64_t base = (int64_t)s * a.M, jLo = (int64_t)blockIdx.y * 256;
+  const double u0 = a.u0[s];
+  const long long kind = siteKind(a.obs[s], a.sigma[s], u0);
+  auto identity = [&](long long tot) {
+    const int64_t j = jLo + tid;
+    if (j < a.M) a.anc[base + j] = (int32_t)(base + j);
+    if (blockIdx.y == 0 && tid == 0) {
+      a.total[s] = tot;
+      if (a.totalOut) a.totalOut[s] = tot;
+    }
+  };
+  if (kind < 0) { identity(kind); return; }
+  {   // four consecutive chunk sums per thread (nCh <= 1024), one block scan
+    constexpr int kPer = (kSitesMaxChunks + 255) / 256;
+    long long v[kPer], sum = 0;
+#pragma unroll
+    for (int q = 0; q < kPer; q++) {
+      const int c = tid * kPer + q;
+      v[q] = c < nCh ? a.chunkSum[(int64_t)s * nCh + c] : 0;
+      sum += v[q];
+    }
+    long long all;
+    long long run = blockScan256(sum, smWave, &all) - sum;
+    if (tid == 0) prefix[0] = 0;
+#pragma unroll
+    for (int q = 0; q < kPer; q++) {
+      const int c = tid * kPer + q;
+      run += v[q];
+      if (c < nCh) prefix[c + 1] = run;
+    }
+    __syncthreads();
+  }
+  const long long Sll = prefix[nCh];
+  if (Sll == 0) { identity(0); return; }
+  const int64_t j = jLo + tid;
+  if (j < a.M) {
+    const double S = (double)Sll, p = sitePoint(j, u0, S, (double)a.M);
+    int cl = 0, chh = nCh - 1;   // the chunk: first c with (double)prefix[c + 1] > p
+    while (cl < chh) {
+      const int mid = (cl + chh) >> 1;
+      if ((double)prefix[mid + 1] > p) chh = mid; else cl = mid + 1;
+    }
+    const long long cbase = prefix[cl];
+    const int64_t* inc = a.threadIncl + ((int64_t)s * nCh + cl) * 256;
+    int tl = 0, th = 255;        // the thread: first t with (double)(cbase + inc[t]) > p
+    while (tl < th) {
+      const int mid = (tl + th) >> 1;
+      if ((double)(cbase + inc[mid]) > p) th = mid; else tl = mid + 1;
+    }
+    long long run = cbase + (tl > 0 ? inc[tl - 1] : 0);
+    const int per = a.chunk >> 8;
+    const int64_t i0 = (int64_t)cl * a.chunk + (int64_t)tl * per, iEnd = i0 + per < a.M ? i0 + per : a.M;
+    int64_t found = iEnd - 1;
+    for (int64_t i = i0; i < iEnd; i++) {
+      run += a.w[base + i];
+      if ((double)run > p) { found = i; break; }
+    }
+    a.anc[base + j] = (int32_t)(base + found);
+  }
+  if (blockIdx.y == 0 && tid == 0) {
+    a.total[s] = Sll;
+    if (a.totalOut) a.totalOut[s] = Sll;
+  }
+}
+
 }  // namespace
 }  // namespace sipnet
 
@@ -987,7 +1224,12 @@ struct PfScratch {
   unsigned long long* d_barrier = nullptr;   // [kBarSets][kBarSetWords] + 1: the stuck word
   unsigned long long launches = 0;      // fused launches that were accepted by the runtime
   int occ[3] = {-1, -1, -1};            // resident workgroups per CU of pfFusedKernel<float,false> / <double,false> / <double,true>
+  void* d_sites = nullptr;              // sipnet_batch_pf_analysis_sites (sitesScratchFor)
+  size_t sitesBytes = 0;
   void release() {
+    if (d_sites) (void)hipFree(d_sites);
+    d_sites = nullptr;
+    sitesBytes = 0;
     if (d_max) (void)hipFree(d_max);
     if (d_w) (void)hipFree(d_w);
     if (d_cdf) (void)hipFree(d_cdf);
@@ -1251,17 +1493,10 @@ int sipnet_batch_pack_members(sipnet_batch* b, const int32_t* d_cols, int64_t n,
   return SIPNET_OK;
 }
 
-int sipnet_batch_resample(sipnet_batch* b, const int32_t* d_src, const double* d_recv,
-                          int32_t n_blocks, const int64_t* block_cols, int32_t with_params,
-                          void* hip_stream) {
-  if (!b || !d_src || n_blocks < 0 || n_blocks > kMaxBlocks || (n_blocks > 0 && !block_cols)) {
-    setError("sipnet_batch_resample: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  if (b->n_sites != 1) {
-    setError("sipnet_batch_resample: particles of different sites must not mix (n_sites must be 1)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+// sipnet_batch_resample's gather without its one-site check (sipnet_batch_pf_analysis_sites: ancestors that never leave
+// their site's columns)
+static int resampleColumns(sipnet_batch* b, const int32_t* d_src, const double* d_recv, int32_t n_blocks,
+                           const int64_t* block_cols, int32_t with_params, void* hip_stream) {
   int rc = useDevice(b);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -1342,6 +1577,20 @@ int sipnet_batch_resample(sipnet_batch* b, const int32_t* d_src, const double* d
     if (flag != 0) b->genericExponents = true;  // only ever widened: plain-exponent kernels must never see a general exponent
   }
   return SIPNET_OK;
+}
+
+int sipnet_batch_resample(sipnet_batch* b, const int32_t* d_src, const double* d_recv,
+                          int32_t n_blocks, const int64_t* block_cols, int32_t with_params,
+                          void* hip_stream) {
+  if (!b || !d_src || n_blocks < 0 || n_blocks > kMaxBlocks || (n_blocks > 0 && !block_cols)) {
+    setError("sipnet_batch_resample: bad argument");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  if (b->n_sites != 1) {
+    setError("sipnet_batch_resample: particles of different sites must not mix (n_sites must be 1)");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  return resampleColumns(b, d_src, d_recv, n_blocks, block_cols, with_params, hip_stream);
 }
 
 int sipnet_batch_pf_analysis(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps,
@@ -1435,6 +1684,104 @@ int sipnet_batch_pf_analysis(sipnet_batch* b, const void* d_plane, int32_t elem_
     }
   }
   return sipnet_batch_resample(b, d_ancestors, nullptr, 0, nullptr, with_params, hip_stream);
+}
+
+// scratch of the many-site analysis: the sites' totals, and for the split path the chunks' maxima, sums and threads' sums
+static int sitesScratchFor(PfScratch& sc, int64_t nSites, int64_t nChunks) {
+  const size_t bytes = (size_t)(nSites + nChunks * (2 + 256)) * sizeof(int64_t);
+  if (sc.sitesBytes < bytes) {
+    if (sc.d_sites) HIP_TRY(hipFree(sc.d_sites));
+    sc.d_sites = nullptr;
+    sc.sitesBytes = 0;
+    HIP_TRY(hipMalloc(&sc.d_sites, bytes));
+    sc.sitesBytes = bytes;
+  }
+  return SIPNET_OK;
+}
+
+int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                   const double* d_obs, const double* d_sigma, const double* d_u0, int32_t with_params,
+                                   double* d_logw, int32_t* d_ancestors, int64_t* d_fixed_weights, int64_t* d_site_total,
+                                   void* hip_stream) {
+  if (!b || !d_plane || !d_obs || !d_sigma || !d_u0 || !d_logw || !d_ancestors || n_steps <= 0 || ld < b->ncol ||
+      b->ncol > (int64_t)1 << 22) {
+    setError("sipnet_batch_pf_analysis_sites: bad argument (device pointers, n_steps > 0, ld >= ncol, at most 4194304 particles)");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  if (b->pfPeers) {
+    setError("sipnet_batch_pf_analysis_sites: this batch is connected to a filter across ranks (sipnet_batch_pf_connect): "
+             "resample through sipnet_batch_pf_resample_peers");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  int rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  b->pfPre.valid = false;
+  PfScratch& sc = scratchOf(b);
+  rc = pfScratchFor(sc, b->ncol, stream);
+  if (rc) return rc;
+  const int64_t M = b->n_members, nSites = b->n_sites;
+  // one workgroup per site only when the sites fill the device: fewer sites than CUs leave CUs idle while a few of them
+  // read all the planes (64 x 4096 particles: 0.22 ms against 0.14 split, profiles/r07_pf_sites_time.txt)
+  const bool split = M > kSitesLds || nSites < b->numCUs || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
+  int chunk = 256;   // (at least two workgroups per CU for the log-weights of a few big sites)
+  while ((M + chunk - 1) / chunk > kSitesMaxChunks) chunk *= 2;
+  const int nChunks = (int)((M + chunk - 1) / chunk);
+  rc = sitesScratchFor(sc, nSites, split ? nSites * nChunks : 0);
+  if (rc) return rc;
+  SitesArgs sa{};
+  sa.plane = d_plane;
+  sa.nSteps = n_steps;
+  sa.ld = ld;
+  sa.M = M;
+  sa.nChunks = nChunks;
+  sa.chunk = chunk;
+  sa.status = b->d_state + (size_t)ST_status * b->ncol;
+  sa.obs = d_obs;
+  sa.sigma = d_sigma;
+  sa.u0 = d_u0;
+  sa.logw = d_logw;
+  sa.w = d_fixed_weights;
+  sa.anc = d_ancestors;
+  sa.total = (int64_t*)sc.d_sites;
+  sa.totalOut = d_site_total;
+  if (!split) {   // one workgroup per site, one launch
+    if (elem_is_f32) hipLaunchKernelGGL(pfSitesKernel<float>, dim3((unsigned)nSites), dim3(256), 0, stream, sa);
+    else hipLaunchKernelGGL(pfSitesKernel<double>, dim3((unsigned)nSites), dim3(256), 0, stream, sa);
+  } else {        // sites too big for one workgroup: chunks of `chunk` columns, three launches
+    sa.chunkMax = (double*)(sa.total + nSites);
+    sa.chunkSum = sa.total + nSites + nSites * nChunks;
+    sa.threadIncl = sa.chunkSum + nSites * nChunks;
+    if (!sa.w) sa.w = sc.d_w;
+    const dim3 chunks((unsigned)nSites, (unsigned)nChunks);
+    if (elem_is_f32) hipLaunchKernelGGL(sitesChunkKernel<float>, chunks, dim3(256), 0, stream, sa);
+    else hipLaunchKernelGGL(sitesChunkKernel<double>, chunks, dim3(256), 0, stream, sa);
+    hipLaunchKernelGGL(sitesWeightKernel, chunks, dim3(256), 0, stream, sa);
+    hipLaunchKernelGGL(sitesAncestorKernel, dim3((unsigned)nSites, (unsigned)((M + 255) / 256)), dim3(256), 0, stream, sa);
+  }
+  HIP_TRY(hipGetLastError());
+  b->pfInfo.fused = split ? 0 : 1;
+  b->pfInfo.grid = split ? 0 : (int32_t)nSites;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = b->ncol;
+  if (!d_site_total) {   // the synchronous checks, before anything is resampled
+    std::vector<int64_t> tot((size_t)nSites);
+    HIP_TRY(hipMemcpyAsync(tot.data(), sc.d_sites, (size_t)nSites * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int64_t s = 0; s < nSites; s++)
+      if (tot[(size_t)s] == kSiteInvalid) {
+        setError("sipnet_batch_pf_analysis_sites: site " + std::to_string(s) +
+                 ": bad argument (a finite obs needs a finite sigma > 0; 0 <= u0 < 1); nothing was resampled");
+        return SIPNET_ERR_BAD_ARGUMENT;
+      }
+    for (int64_t s = 0; s < nSites; s++)
+      if (tot[(size_t)s] == 0) {
+        setError("sipnet_batch_pf_analysis_sites: site " + std::to_string(s) +
+                 ": every particle has zero weight; nothing was resampled");
+        return SIPNET_ERR_BAD_PARAMETER;
+      }
+  }
+  return resampleColumns(b, d_ancestors, nullptr, 0, nullptr, with_params, hip_stream);
 }
 
 }  // extern "C"
