@@ -310,7 +310,8 @@ enum sipnet_kernel_option {
   SIPNET_KOPT_PF_MULTI_LAUNCH = 512, /* particle filter: the analysis as separate launches (log-weights | fixed-point weights |
                                         prefix sum | ancestors), never the one-launch kernel whose workgroups spin at barriers
                                         in device memory.  Chosen without being asked when fewer than 8 such workgroups could
-                                        be resident (sipnet_batch_set_device_share, a sliver of a partitioned device) */
+                                        be resident (sipnet_batch_set_device_share, a sliver of a partitioned device).
+                                        Also forces the per-chunk launches of sipnet_batch_enkf_analysis_sites */
   SIPNET_KOPT_PF_MOVE_PARAMS = 1024, /* particle filter across ranks, particles carrying their parameters: move the 640 bytes
                                         of converted parameter rows with every resampled particle (round 5) instead of
                                         replicating all ranks' parameters once at sipnet_batch_pf_connect and moving a 4-byte
@@ -556,6 +557,48 @@ int sipnet_batch_pf_analysis_sites(sipnet_batch *b, const void *d_plane, int32_t
                                    int64_t ld, const double *d_obs, const double *d_sigma, const double *d_u0,
                                    int32_t with_params, double *d_logw, int32_t *d_ancestors,
                                    int64_t *d_fixed_weights, int64_t *d_site_total, void *hip_stream);
+
+/* ---- ensemble Kalman filter analysis of the member pools, a filter per site ------------------------------------
+ * Observation operators (h of one member, from its forecast state, planes and converted parameters):
+ *   POOLS: h = scale * (sum of the pools in pool_mask) / (param >= 0 ? prm[param] : 1)
+ *   PLANE: h = scale * (sum over t < n_steps of planes[plane][t][col]) / (param >= 0 ? prm[param] : 1)
+ * pool_mask bits 0..12 are the state slots 0..12 (Envi order: plantWoodC, plantLeafC, soilC, soilWater, litterC, snow,
+ * coarseRootC, fineRootC, minN, soilOrgN, litterN, plantStorageN, plantCAccountingDelta); plane 0 NEE, 1 GPP, 2 ET;
+ * param a sipnet_param_index (leafCSpWt for LAI, soilWHC for soil wetness), read for the member's own column. */
+enum sipnet_enkf_kind { SIPNET_ENKF_POOLS = 0, SIPNET_ENKF_PLANE = 1 };
+typedef struct sipnet_enkf_obs {
+  int32_t kind;       /* enum sipnet_enkf_kind */
+  int32_t pool_mask;  /* POOLS only */
+  int32_t plane;      /* PLANE only */
+  int32_t param;      /* -1, or a converted-parameter index to divide by */
+  double scale;
+} sipnet_enkf_obs;
+/* Site s (columns [s M, (s + 1) M)) is a filter of its own over its LIVE members (state[29] == 0, site plan status OK;
+ * n of them): the h of every operator from the forecast; with lambda = inflation[s] every analysed pool and every h
+ * becomes mean + lambda (x - mean) (lambda == 1: unchanged); then the ensemble adjustment Kalman filter (serial EnSRF):
+ * observations in index order, NaN ones skipped, each from the statistics of the current ensemble (means, then centred
+ * sums with divisor n - 1): R = sd^2, K_v = cov(x_v, h_i) / (var(h_i) + R), alpha = 1 / (1 + sqrt(R / (var(h_i) + R))),
+ * x_v += K_v (y - mean(h_i)) - alpha K_v (h_i - mean(h_i)) for the analysed pools and the later h.  Last, analysed pools
+ * other than plantCAccountingDelta are clipped at 0 from below, and a member whose result fails hasSufficientBiomass
+ * (plantWoodC, plantWoodC + plantCAccountingDelta, fineRootC + coarseRootC all > 1e-6) keeps its forecast pools.
+ * Only the d_state slots in analysed_mask of live members are written; everything else stays bit-identical.
+ * Pointers: ops, d_planes (may be NULL, or hold NULLs for planes no operator reads) are HOST arrays; d_planes[k] [n_steps][ld]
+ * (doubles, or floats with elem_is_f32), d_obs / d_sd [n_sites][n_obs] (obs NaN: not observed), d_inflation [n_sites]
+ * (NULL: 1) and d_site_info [n_sites][4] are DEVICE arrays.  site_info[s] = {code, observations used, live members,
+ * members that kept their forecast}; code 1 analysed, -1 no observation, -2 bad input (a non-NaN non-finite obs, an sd
+ * not finite and > 0, a lambda not finite or < 1; the site is untouched), 0 fewer than 2 live members (untouched).
+ * d_site_info given: nothing is synchronised.  NULL: obs, sd and inflation are read back and checked first; a -2 site
+ * gives SIPNET_ERR_BAD_ARGUMENT naming it, and nothing is written.  SIPNET_ERR_BAD_ARGUMENT before any launch: a NULL
+ * batch, ops, obs or sd; n_obs outside 1..16; a zero or out-of-range mask; a bad param or plane index, or a PLANE
+ * operator whose plane pointer is NULL; n_steps <= 0 or ld < ncol when planes are used; ncol > 4 194 304; a batch
+ * connected by sipnet_batch_pf_connect.  Pending set_params rows are flushed first; a forecast's armed or left
+ * log-weights are dropped (as sipnet_batch_set_state); the batch's records-done count is kept.  Results do not depend on
+ * the path taken (one workgroup per site, or per-chunk launches: SIPNET_KOPT_PF_MULTI_LAUNCH) nor on the call;
+ * sipnet_batch_pf_info's fused then says which path ran (1: one workgroup per site). */
+int sipnet_batch_enkf_analysis_sites(sipnet_batch *b, int32_t n_obs, const sipnet_enkf_obs *ops, int32_t analysed_mask,
+                                     const void *const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                     const double *d_obs, const double *d_sd, const double *d_inflation,
+                                     int32_t *d_site_info, void *hip_stream);
 
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its
@@ -840,7 +883,9 @@ int sipnet_debug_plan_compare(sipnet_batch *b, int32_t site, int32_t ignore_log2
                               int64_t *n_ops_differing, int32_t *first_step, int32_t *first_offset,
                               int32_t *device_info);
 /* Test hooks.  sipnet_debug_set_num_cus: pretend the device has this many compute units (the kernel choice of
- * SIPNET_KERNEL_AUTO and the particle filter's resident-grid budget follow it: 32 = one partition of a CPX-mode MI355X).
+ * SIPNET_KERNEL_AUTO and the particle filter's resident-grid budget follow it: 32 = one partition of a CPX-mode MI355X;
+ * sipnet_batch_enkf_analysis_sites takes one workgroup per site from 4 sites per CU, so num_cus 1 forces that path for
+ * batches of at least 4 sites of at most 4096 members).
  * sipnet_debug_pf_barrier: polls a barrier of the one-launch analysis waits before it gives up (0: the default, ~0.3 s), and
  * a workgroup of the NEXT such launch that leaves without arriving (-1: none) -- the test of the "grid not co-resident"
  * path without having to produce one. */

@@ -42,6 +42,15 @@ SHARD_MEMBERS, SHARD_SITES = 0, 1
 ALL_SITES = -1
 
 
+ENKF_POOLS, ENKF_PLANE = 0, 1   # enum sipnet_enkf_kind
+
+
+class EnkfObs(C.Structure):
+    """struct sipnet_enkf_obs: one observation operator of sipnet_batch_enkf_analysis_sites"""
+    _fields_ = [("kind", C.c_int32), ("pool_mask", C.c_int32), ("plane", C.c_int32), ("param", C.c_int32),
+                ("scale", C.c_double)]
+
+
 class Event(C.Structure):
     """struct sipnet_event"""
     _fields_ = [("type", C.c_int32), ("year", C.c_int32), ("day", C.c_int32),
@@ -160,6 +169,8 @@ SIGNATURES = {
                                            C.c_int32, _P, _P, _P, _P]),
     "sipnet_batch_pf_analysis_sites": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, _P,
                                                  _P, _P, _P]),
+    "sipnet_batch_enkf_analysis_sites": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
+                                                   _P, _P, _P, _P]),
     "sipnet_batch_pf_publish": (C.c_int, [_P, C.c_int32, _P]),
     "sipnet_batch_pf_connect": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "sipnet_batch_pf_block_len": (C.c_int64, [_P]),

@@ -364,6 +364,54 @@ class Batch:
             C.c_void_p(total_out.data_ptr()) if total_out is not None else None, self._stream()), "pf_analysis_sites")
         return (anc, logw, fixed) if return_fixed else (anc, logw)
 
+    def enkf_analysis_sites(self, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
+        """an ensemble Kalman filter analysis of the member pools, every site a filter of its own, one library call
+        (sipnet_batch_enkf_analysis_sites).  obs, sd: [n_sites][n_obs] (array-likes, uploaded as float64, or float64 device
+        tensors; obs NaN: not observed); operators: sa.enkf_pools / sa.enkf_plane, one per observation column; analysed:
+        the pool names the update writes; planes: run()'s [3][n_steps][ld] tensor, or a list of three (None for planes no
+        operator reads); inflation: one value per site (None: 1).  info_out: int32 device tensor [n_sites][4] for
+        {code, observations used, live members, members kept on their forecast} (no host synchronisation); without it the
+        call checks the inputs first and raises before anything is written."""
+        from ._lib import EnkfObs
+        from .config import pool_mask
+        t = self._torch
+        ops = list(operators)
+        n_obs = len(ops)
+
+        def dev(x, n, what):
+            x = t.as_tensor(x, dtype=t.float64).reshape(-1).to(self.device).contiguous()
+            if x.numel() != n:
+                raise ValueError(f"enkf_analysis_sites: {what} needs {n} values, got {x.numel()}")
+            return x
+
+        obs, sd = dev(obs, self.n_sites * n_obs, "obs"), dev(sd, self.n_sites * n_obs, "sd")
+        infl = dev(inflation, self.n_sites, "inflation") if inflation is not None else None
+        arr = (EnkfObs * max(n_obs, 1))(*ops)
+        ptrs = (C.c_void_p * 3)()
+        f32, n_steps, ld = 0, 0, 0
+        if planes is not None:
+            layouts = set()
+            for k in range(3):
+                p = planes[k]
+                if p is None:
+                    continue
+                if not p.is_cuda or p.dim() != 2 or p.dtype not in (t.float32, t.float64) or p.stride(1) != 1:
+                    raise ValueError("enkf_analysis_sites: a plane must be a [n_steps][ld] float32 / float64 device tensor "
+                                     "with unit column stride")
+                ptrs[k] = p.data_ptr()
+                layouts.add((int(p.dtype == t.float32), p.shape[0], p.stride(0)))
+            if len(layouts) > 1:
+                raise ValueError("enkf_analysis_sites: the planes differ in dtype, step count or row pitch: " + str(layouts))
+            if layouts:
+                f32, n_steps, ld = layouts.pop()
+        if info_out is not None and (info_out.dtype != t.int32 or not info_out.is_contiguous() or not info_out.is_cuda
+                                     or info_out.numel() != 4 * self.n_sites):
+            raise ValueError("enkf_analysis_sites: info_out must be a contiguous int32 device tensor of n_sites x 4")
+        check(self.L.sipnet_batch_enkf_analysis_sites(
+            self.h, n_obs, arr, pool_mask(analysed), ptrs if planes is not None else None, f32, n_steps, ld,
+            C.c_void_p(obs.data_ptr()), C.c_void_p(sd.data_ptr()), C.c_void_p(infl.data_ptr()) if infl is not None else None,
+            C.c_void_p(info_out.data_ptr()) if info_out is not None else None, self._stream()), "enkf_analysis_sites")
+
     # -- the filter across ranks by peer reads (sipnet_batch_pf_publish / _connect / _resample_peers) ----------
     def pf_publish(self, with_params=True):
         """-> bytes of this batch's sipnet_pf_peer descriptor (exchange them, then pf_connect)"""

@@ -65,6 +65,43 @@ def read_config(path):
     return cfg
 
 
+# the pools of the carried state, state slots 0..12 (Envi order, include/sipnet_amd.h): what an EnKF analysis updates
+POOLS = ["plantWoodC", "plantLeafC", "soilC", "soilWater", "litterC", "snow", "coarseRootC", "fineRootC", "minN",
+         "soilOrgN", "litterN", "plantStorageN", "plantCAccountingDelta"]
+PLANES = ["nee", "gpp", "et"]
+
+
+def pool_mask(names):
+    """bit mask of pool names (state slots 0..12)"""
+    names = [names] if isinstance(names, str) else list(names)
+    m = 0
+    for n in names:
+        m |= 1 << POOLS.index(n)
+    return m
+
+
+def enkf_pools(pools, divide_by=None, scale=1.0):
+    """EnKF observation operator h = scale * (sum of these pools) / (the member's converted parameter `divide_by`, if given),
+    e.g. LAI = enkf_pools(["plantLeafC"], divide_by="leafCSpWt")"""
+    from ._lib import ENKF_POOLS, EnkfObs
+    return EnkfObs(ENKF_POOLS, pool_mask(pools), 0, _param_or_none(divide_by), float(scale))
+
+
+def enkf_plane(plane, divide_by=None, scale=1.0):
+    """EnKF observation operator h = scale * (sum of a plane -- "nee", "gpp" or "et" -- over the forecast window)"""
+    from ._lib import ENKF_PLANE, EnkfObs
+    return EnkfObs(ENKF_PLANE, 0, PLANES.index(plane), _param_or_none(divide_by), float(scale))
+
+
+def _param_or_none(name):
+    if name is None:
+        return -1
+    i = param_index(name)
+    if i < 0:
+        raise KeyError(name)
+    return i
+
+
 PARAM_NAMES = None
 
 

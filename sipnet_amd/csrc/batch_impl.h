@@ -188,10 +188,14 @@ struct sipnet_batch {
   // uploads that need a kernel (the parameter conversion) run on a stream of the batch's own: on the null stream
   // they would queue behind whatever another batch is running on a blocking stream
   hipStream_t upStream = nullptr;
+  // sipnet_batch_enkf_analysis_sites (enkf.hip): working copies, partial sums and site statistics, grow-only
+  void* d_enkf = nullptr;
+  size_t enkfBytes = 0;
 };
 int flushParams(sipnet_batch* b, hipStream_t stream);   // engine.hip: upload + convert what set_params left pending
 int materializeParams(sipnet_batch* b, hipStream_t stream);   // pf.hip: d_prm back into column order (no-op unless prmIndexed)
 void pfDropBank(sipnet_batch* b);   // pf.hip: a connected filter's bank of all ranks' parameters is void (new parameters, moved rows)
+void enkfRelease(sipnet_batch* b);   // enkf.hip: frees the analysis scratch (called by sipnet_batch_destroy)
 
 // "This batch has work in flight on `stream`."  The event itself is recorded only when somebody needs it (a wait from
 // another stream, a host-side wait or query): work queued later on the SAME stream is ordered behind it anyway, and an

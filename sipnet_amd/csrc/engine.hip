@@ -780,6 +780,7 @@ void sipnet_batch_destroy(sipnet_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   pfRelease(b);
+  enkfRelease(b);
   if (b->d_rawStage) (void)hipFree(b->d_rawStage);
   if (b->hostRaw) (void)hipHostFree(b->hostRaw);
   if (b->hostFast) (void)hipHostFree(b->hostFast);

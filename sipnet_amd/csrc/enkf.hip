@@ -1,0 +1,584 @@
+// enkf.hip -- sipnet_batch_enkf_analysis_sites: an ensemble Kalman filter analysis of the member pools, a filter per site.
+//
+// Site s owns columns [s M, (s + 1) M).  Its live members' analysed pools and predicted observations are the analysis's
+// variables: working copies W[v][member], v < nA the analysed pools (in state-slot order), nA + i the h of operator i.
+// The serial square-root update (EAKF, Whitaker & Hamill 2002) recomputes every observation's statistics from the current
+// ensemble: sums of the variables, then centred sums against h_i.  A sum is always taken in ONE order: chunks of 256
+// members, a chunk by a fixed tree (every wave by an xor-shuffle butterfly, then the four waves in order); the chunk totals
+// in segments of segLen(nCh) >= 16 consecutive chunks, each in order from 0.0; one segment is the site's total, several (at
+// most 64) are combined by one wave's xor-shuffle butterfly.  A site of the one-workgroup-per-site kernel has at most 16 chunks,
+// one segment: so that kernel and the per-chunk launches give the same bits.  No grid barrier, no spin, no atomic.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "batch_impl.h"
+
+namespace {
+
+constexpr int kMaxObs = 16;
+constexpr int kPools = 13;                 // state slots 0..12: the Envi pools
+constexpr int kMaxVars = kPools + kMaxObs;
+constexpr int kMaxGroupChunks = 16;        // one workgroup per site: sites of at most 16 x 256 members
+constexpr int kLdsWork = 40 * 1024;        // ... whose working copies fit here stay in LDS, else in the scratch block
+constexpr double kTiny = 0.000001;         // TINY, common/util.h
+constexpr int kStat = 3 * kMaxVars;         // split path, per site: means | K | alpha K of every variable
+constexpr int kAnalysed = 1, kNoObs = -1, kBadInput = -2, kTooFew = 0;
+
+struct EnkfOp {
+  int32_t kind, mask, plane, param;
+  double scale;
+};
+struct EnkfArgs {
+  EnkfOp op[kMaxObs];
+  int32_t nObs, nA, nv, nCh;
+  int32_t pool[kPools];                    // the analysed state slots, ascending
+  const void* planes[3];
+  int32_t nSteps;
+  int64_t ld;
+  const double* obs;                       // [n_sites][nObs]
+  const double* sd;
+  const double* infl;                      // [n_sites] or null
+  int32_t* info;                           // [n_sites][4]
+  double* state;                           // [NSTATE][ncol]
+  int64_t ncol, M;
+  const int32_t* siteStatus;
+  const double* prm;                       // converted parameters: prm[p * prmPitch + (prmId ? prmId[col] : col)]
+  int64_t prmPitch;
+  const int32_t* prmId;
+  double* work;                            // [nv][ncol]
+  double* part;                            // split path: [n_sites][nCh][kMaxVars] a chunk's sums
+  double* stat;                            // split path: [n_sites][kStat]
+  int32_t* cnt;                            // split path: [n_sites][nCh] live members / members kept on their forecast
+  int32_t* kept;
+  int32_t* site;                           // split path: [n_sites][2] the site's code and live count (enkfCodeKernel)
+  int32_t useLds;                          // one workgroup per site: W in LDS ([nv][M])
+};
+
+__device__ __forceinline__ bool liveAt(const EnkfArgs& a, int s, int64_t j) {
+  return j < a.M && a.siteStatus[s] == 0 && a.state[(int64_t)ST_status * a.ncol + (int64_t)s * a.M + j] == 0.0;
+}
+
+// the site's inputs: kBadInput, kNoObs, or kAnalysed (before the live count); *used = observations that are not NaN
+__host__ __device__ inline int siteInputs(const double* obs, const double* sd, const double* infl, int nObs, int s, int* used) {
+  bool bad = false;
+  int u = 0;
+  for (int i = 0; i < nObs; i++) {
+    const double y = obs[(int64_t)s * nObs + i], e = sd[(int64_t)s * nObs + i];
+    if (y != y) continue;
+    if (!(fabs(y) < INFINITY) || !(e > 0.0) || !(e < INFINITY)) bad = true;
+    u++;
+  }
+  if (infl) {
+    const double l = infl[s];
+    if (!(l >= 1.0) || !(l < INFINITY)) bad = true;
+  }
+  *used = u;
+  return bad ? kBadInput : (u == 0 ? kNoObs : kAnalysed);
+}
+
+// h of operator i for column col, from the forecast
+template <typename T>
+__device__ double predicted(const EnkfArgs& a, int i, int64_t col) {
+  const EnkfOp& o = a.op[i];
+  double sum = 0.0;
+  if (o.kind == SIPNET_ENKF_POOLS) {
+    for (int p = 0; p < kPools; p++)
+      if (o.mask & (1 << p)) sum += a.state[(int64_t)p * a.ncol + col];
+  } else {
+    const T* pl = (const T*)a.planes[o.plane];
+    for (int t = 0; t < a.nSteps; t++) sum += (double)pl[(int64_t)t * a.ld + col];
+  }
+  double h = o.scale * sum;
+  if (o.param >= 0) h = h / a.prm[(int64_t)o.param * a.prmPitch + (a.prmId ? (int64_t)a.prmId[col] : col)];
+  return h;
+}
+
+__device__ __forceinline__ double waveSum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ double combine4(const double* smW, int q) {   // smW [4][kMaxVars]: the waves in order
+  return ((smW[q] + smW[kMaxVars + q]) + smW[2 * kMaxVars + q]) + smW[3 * kMaxVars + q];
+}
+// chunks per segment of a site of nCh chunks: at most 64 segments
+constexpr int kMaxSegs = 64;
+__device__ __forceinline__ int segLen(int nCh) { return nCh <= 16 * kMaxSegs ? 16 : (nCh + kMaxSegs - 1) / kMaxSegs; }
+// variable q of an observation stage i: the analysed pools, then h_i (q = nA), then the later h
+__device__ __forceinline__ int varOf(const EnkfArgs& a, int q, int i) { return q < a.nA ? q : q + i; }
+
+// the gains of observation i (sd e) from the centred sums: K_q and alpha K_q of variable q (q = nA: h_i itself, unused)
+__device__ __forceinline__ void gains(const EnkfArgs& a, int q, int V, double n, const double* csum, double e, double* K,
+                                      double* aK) {
+  if (q >= V) return;
+  const double R = e * e, varh = csum[a.nA] / (n - 1.0), denom = varh + R;
+  const double alpha = 1.0 / (1.0 + sqrt(R / denom));
+  const double k = (csum[q] / (n - 1.0)) / denom;
+  K[q] = k;
+  aK[q] = alpha * k;
+}
+__device__ __forceinline__ double moved(double x, double K, double aK, double innov, double dh) { return (x + K * innov) - aK * dh; }
+__device__ __forceinline__ double inflated(double x, double mean, double lam) { return mean + lam * (x - mean); }
+
+// the physical limits of one live member: its analysed pools clipped, then hasSufficientBiomass (sipnet.c:1530-1536) of
+// the result; false = the member keeps its forecast.  fin[v] gets the clipped values.
+__device__ bool limited(const EnkfArgs& a, int64_t col, const double* W, int64_t ldw, int64_t j, double* fin) {
+  double f[kPools];
+  for (int p = 0; p < kPools; p++) f[p] = a.state[(int64_t)p * a.ncol + col];
+  bool finite = true;
+  for (int q = 0; q < a.nA; q++) {
+    double v = W[(int64_t)q * ldw + j];
+    if (a.pool[q] != ST_plantCAccountingDelta && v < 0.0) v = 0.0;
+    finite = finite && fabs(v) < INFINITY;
+    fin[q] = v;
+    f[a.pool[q]] = v;
+  }
+  const double totalWood = f[ST_plantWoodC] + f[ST_plantCAccountingDelta], totalRoot = f[ST_fineRootC] + f[ST_coarseRootC];
+  return finite && f[ST_plantWoodC] > kTiny && totalWood > kTiny && totalRoot > kTiny;
+}
+
+// ---- one workgroup per site -------------------------------------------------------------------------------------------
+struct GroupLds {
+  double smW[kMaxGroupChunks][4 * kMaxVars];
+  double chunkTot[kMaxGroupChunks][kMaxVars];
+  double tot[kMaxVars];
+  double mean[kMaxVars];
+  double K[kMaxVars], aK[kMaxVars];
+  int smI[4];
+};
+// the site's sums of val(j, q), q < V, in the fixed order -> g.tot
+template <class F>
+__device__ void siteSums(GroupLds& g, int V, int nCh, F val) {
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int q = 0; q < V; q++)
+    for (int c = 0; c < nCh; c++) {
+      const double v = waveSum(val((int64_t)c * 256 + tid, q));
+      if (lane == 0) g.smW[c][wave * kMaxVars + q] = v;
+    }
+  __syncthreads();
+  for (int k = tid; k < V * nCh; k += 256) g.chunkTot[k / V][k % V] = combine4(g.smW[k / V], k % V);
+  __syncthreads();
+  if (tid < V) {
+    double t = 0.0;
+    for (int c = 0; c < nCh; c++) t += g.chunkTot[c][tid];
+    g.tot[tid] = t;
+  }
+  __syncthreads();
+}
+__device__ int blockCount(GroupLds& g, int v) {
+  const int tid = (int)threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((tid & 63) == 0) g.smI[tid >> 6] = v;
+  __syncthreads();
+  const int n = g.smI[0] + g.smI[1] + g.smI[2] + g.smI[3];
+  __syncthreads();
+  return n;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void enkfSiteKernel(EnkfArgs a) {
+  extern __shared__ double ldsWork[];
+  __shared__ GroupLds g;
+  const int tid = (int)threadIdx.x, s = (int)blockIdx.x, nCh = a.nCh, nA = a.nA, nv = a.nv;
+  const int64_t base = (int64_t)s * a.M;
+  double* W = a.useLds ? ldsWork : a.work + base;
+  const int64_t ldw = a.useLds ? a.M : a.ncol;
+  int used;
+  int code = siteInputs(a.obs, a.sd, a.infl, a.nObs, s, &used);
+  int mine = 0;
+  for (int64_t j = tid; j < a.M; j += 256) mine += liveAt(a, s, j) ? 1 : 0;
+  const int n = blockCount(g, mine);
+  if (code == kAnalysed && n < 2) code = kTooFew;
+  if (code != kAnalysed) {
+    if (tid == 0) {
+      int32_t* inf = a.info + 4 * (int64_t)s;
+      inf[0] = code; inf[1] = 0; inf[2] = n; inf[3] = 0;
+    }
+    return;
+  }
+  // the working copies: analysed pools and predicted observations of the live members (each member: its own thread throughout)
+  for (int64_t j = tid; j < a.M; j += 256)
+    if (liveAt(a, s, j)) {
+      for (int q = 0; q < nA; q++) W[(int64_t)q * ldw + j] = a.state[(int64_t)a.pool[q] * a.ncol + base + j];
+      for (int i = 0; i < a.nObs; i++) W[(int64_t)(nA + i) * ldw + j] = predicted<T>(a, i, base + j);
+    }
+  const double nd = (double)n;
+  const double lam = a.infl ? a.infl[s] : 1.0;
+  if (lam != 1.0) {
+    siteSums(g, nv, nCh, [&](int64_t j, int q) { return liveAt(a, s, j) ? W[(int64_t)q * ldw + j] : 0.0; });
+    if (tid < nv) g.mean[tid] = g.tot[tid] / nd;
+    __syncthreads();
+    for (int64_t j = tid; j < a.M; j += 256)
+      if (liveAt(a, s, j))
+        for (int q = 0; q < nv; q++) W[(int64_t)q * ldw + j] = inflated(W[(int64_t)q * ldw + j], g.mean[q], lam);
+  }
+  for (int i = 0; i < a.nObs; i++) {
+    const double y = a.obs[(int64_t)s * a.nObs + i];
+    if (y != y) continue;
+    const double e = a.sd[(int64_t)s * a.nObs + i];
+    const int V = nv - i;
+    const double* Wh = W + (int64_t)(nA + i) * ldw;
+    siteSums(g, V, nCh, [&](int64_t j, int q) { return liveAt(a, s, j) ? W[(int64_t)varOf(a, q, i) * ldw + j] : 0.0; });
+    if (tid < V) g.mean[tid] = g.tot[tid] / nd;
+    __syncthreads();
+    const double hbar = g.mean[nA];
+    siteSums(g, V, nCh, [&](int64_t j, int q) {
+      return liveAt(a, s, j) ? (W[(int64_t)varOf(a, q, i) * ldw + j] - g.mean[q]) * (Wh[j] - hbar) : 0.0;
+    });
+    gains(a, tid, V, nd, g.tot, e, g.K, g.aK);
+    __syncthreads();
+    const double innov = y - hbar;
+    for (int64_t j = tid; j < a.M; j += 256)
+      if (liveAt(a, s, j)) {
+        const double dh = Wh[j] - hbar;
+        for (int q = 0; q < V; q++)
+          if (q != nA) {
+            double* x = W + (int64_t)varOf(a, q, i) * ldw + j;
+            *x = moved(*x, g.K[q], g.aK[q], innov, dh);
+          }
+      }
+  }
+  int kept = 0;
+  for (int64_t j = tid; j < a.M; j += 256)
+    if (liveAt(a, s, j)) {
+      double fin[kPools];
+      if (limited(a, base + j, W, ldw, j, fin)) {
+        for (int q = 0; q < nA; q++) a.state[(int64_t)a.pool[q] * a.ncol + base + j] = fin[q];
+      } else {
+        kept++;
+      }
+    }
+  kept = blockCount(g, kept);
+  if (tid == 0) {
+    int32_t* inf = a.info + 4 * (int64_t)s;
+    inf[0] = kAnalysed; inf[1] = used; inf[2] = n; inf[3] = kept;
+  }
+}
+
+// ---- the split path: grid (sites, chunks of 256 members), one launch per stage --------------------------------------------
+// the site's code, as enkfCodeKernel left it
+__device__ __forceinline__ int splitCode(const EnkfArgs& a, int s) { return a.site[2 * (int64_t)s]; }
+// one workgroup per site: the sum of a site's per-chunk counts (ints: any order)
+__device__ int siteCount(const int32_t* v, int64_t nCh) {
+  __shared__ int smI[4];
+  const int tid = (int)threadIdx.x;
+  int c = 0;
+  for (int64_t k = tid; k < nCh; k += 256) c += v[k];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  if ((tid & 63) == 0) smI[tid >> 6] = c;
+  __syncthreads();
+  return smI[0] + smI[1] + smI[2] + smI[3];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void enkfLoadKernel(EnkfArgs a) {
+  __shared__ int smI[4];
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int64_t j = (int64_t)blockIdx.y * 256 + tid, col = (int64_t)s * a.M + j;
+  const bool live = liveAt(a, s, j);
+  if (live) {
+    for (int q = 0; q < a.nA; q++) a.work[(int64_t)q * a.ncol + col] = a.state[(int64_t)a.pool[q] * a.ncol + col];
+    for (int i = 0; i < a.nObs; i++) a.work[(int64_t)(a.nA + i) * a.ncol + col] = predicted<T>(a, i, col);
+  }
+  int v = live ? 1 : 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((tid & 63) == 0) smI[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) a.cnt[(int64_t)s * a.nCh + blockIdx.y] = smI[0] + smI[1] + smI[2] + smI[3];
+}
+
+// one workgroup per site, after the load: the live count and the site's code, once
+__global__ __launch_bounds__(256) void enkfCodeKernel(EnkfArgs a) {
+  const int s = (int)blockIdx.x;
+  const int n = siteCount(a.cnt + (int64_t)s * a.nCh, a.nCh);
+  if (threadIdx.x == 0) {
+    int used;
+    int code = siteInputs(a.obs, a.sd, a.infl, a.nObs, s, &used);
+    if (code == kAnalysed && n < 2) code = kTooFew;
+    a.site[2 * (int64_t)s] = code;
+    a.site[2 * (int64_t)s + 1] = n;
+  }
+}
+
+// a chunk's sums for stage i (i < 0: the inflation's means over all variables): centred = 0 the variables,
+// 1 the centred products with h_i (means from stat)
+__global__ __launch_bounds__(256) void enkfPartialKernel(EnkfArgs a, int i, int centred) {
+  __shared__ double smW[4 * kMaxVars];
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x, c = (int)blockIdx.y;
+  if (splitCode(a, s) != kAnalysed) return;
+  if (i < 0 && !(a.infl && a.infl[s] != 1.0)) return;
+  if (i >= 0 && a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i]) return;
+  const int ii = i < 0 ? 0 : i, V = a.nv - ii;
+  const int64_t j = (int64_t)c * 256 + tid, col = (int64_t)s * a.M + j;
+  const bool live = liveAt(a, s, j);
+  const double* mean = a.stat + (int64_t)s * kStat;
+  const double dh = live && centred ? a.work[(int64_t)(a.nA + ii) * a.ncol + col] - mean[a.nA] : 0.0;
+  for (int q = 0; q < V; q++) {
+    double v = 0.0;
+    if (live) {
+      const double x = a.work[(int64_t)varOf(a, q, ii) * a.ncol + col];
+      v = centred ? (x - mean[q]) * dh : x;
+    }
+    v = waveSum(v);
+    if ((tid & 63) == 0) smW[(tid >> 6) * kMaxVars + q] = v;
+  }
+  __syncthreads();
+  if (tid < V) a.part[((int64_t)s * a.nCh + c) * kMaxVars + tid] = combine4(smW, tid);
+}
+
+// one workgroup per site: the chunks' sums (every segment of every variable in order; the segments by one wave's butterfly)
+// -> the means (centred = 0) or the gains (centred = 1)
+__global__ __launch_bounds__(256) void enkfFinalKernel(EnkfArgs a, int i, int centred) {
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
+  if (splitCode(a, s) != kAnalysed) return;
+  if (i < 0 && !(a.infl && a.infl[s] != 1.0)) return;
+  if (i >= 0 && a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i]) return;
+  __shared__ double tot[kMaxVars], seg[kMaxSegs][kMaxVars];
+  const int ii = i < 0 ? 0 : i, V = a.nv - ii, n = a.site[2 * (int64_t)s + 1];
+  const int L = segLen(a.nCh), nSeg = (a.nCh + L - 1) / L;
+  const double* part = a.part + (int64_t)s * a.nCh * kMaxVars;
+  for (int k = tid; k < nSeg * V; k += 256) {   // (segment g of variable q)
+    const int g = k / V, q = k % V, c1 = (g + 1) * L < a.nCh ? (g + 1) * L : a.nCh;
+    double t = 0.0;
+    for (int c = g * L; c < c1; c++) t += part[(int64_t)c * kMaxVars + q];
+    seg[g][q] = t;
+  }
+  __syncthreads();
+  if (nSeg == 1) {
+    if (tid < V) tot[tid] = seg[0][tid];
+  } else {
+    const int lane = tid & 63;
+    for (int q = tid >> 6; q < V; q += 4) {   // (every wave its own variables)
+      const double t = waveSum(lane < nSeg ? seg[lane][q] : 0.0);
+      if (lane == 0) tot[q] = t;
+    }
+  }
+  __syncthreads();
+  double* st = a.stat + (int64_t)s * kStat;
+  if (!centred) {
+    if (tid < V) st[tid] = tot[tid] / (double)n;
+  } else {
+    gains(a, tid, V, (double)n, tot, a.sd[(int64_t)s * a.nObs + i], st + kMaxVars, st + 2 * kMaxVars);
+  }
+}
+
+// a chunk's members moved by observation i (i < 0: inflated)
+__global__ __launch_bounds__(256) void enkfUpdateKernel(EnkfArgs a, int i) {
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
+  if (splitCode(a, s) != kAnalysed) return;
+  if (i < 0 && !(a.infl && a.infl[s] != 1.0)) return;
+  if (i >= 0 && a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i]) return;
+  const int64_t j = (int64_t)blockIdx.y * 256 + tid, col = (int64_t)s * a.M + j;
+  if (!liveAt(a, s, j)) return;
+  const double* st = a.stat + (int64_t)s * kStat;
+  if (i < 0) {
+    const double lam = a.infl[s];
+    for (int q = 0; q < a.nv; q++) {
+      double* x = a.work + (int64_t)q * a.ncol + col;
+      *x = inflated(*x, st[q], lam);
+    }
+    return;
+  }
+  const int V = a.nv - i;
+  const double hbar = st[a.nA], innov = a.obs[(int64_t)s * a.nObs + i] - hbar;
+  const double dh = a.work[(int64_t)(a.nA + i) * a.ncol + col] - hbar;
+  for (int q = 0; q < V; q++)
+    if (q != a.nA) {
+      double* x = a.work + (int64_t)varOf(a, q, i) * a.ncol + col;
+      *x = moved(*x, st[kMaxVars + q], st[2 * kMaxVars + q], innov, dh);
+    }
+}
+
+__global__ __launch_bounds__(256) void enkfLimitKernel(EnkfArgs a) {
+  __shared__ int smI[4];
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
+  if (splitCode(a, s) != kAnalysed) return;
+  const int64_t j = (int64_t)blockIdx.y * 256 + tid, col = (int64_t)s * a.M + j;
+  int kept = 0;
+  if (liveAt(a, s, j)) {
+    double fin[kPools];
+    if (limited(a, col, a.work + (int64_t)s * a.M, a.ncol, j, fin)) {
+      for (int q = 0; q < a.nA; q++) a.state[(int64_t)a.pool[q] * a.ncol + col] = fin[q];
+    } else {
+      kept = 1;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
+  if ((tid & 63) == 0) smI[tid >> 6] = kept;
+  __syncthreads();
+  if (tid == 0) a.kept[(int64_t)s * a.nCh + blockIdx.y] = smI[0] + smI[1] + smI[2] + smI[3];
+}
+
+// one workgroup per site
+__global__ __launch_bounds__(256) void enkfInfoKernel(EnkfArgs a) {
+  const int s = (int)blockIdx.x;
+  const int code = splitCode(a, s);
+  const int kept = code == kAnalysed ? siteCount(a.kept + (int64_t)s * a.nCh, a.nCh) : 0;
+  if (threadIdx.x == 0) {
+    int used;
+    (void)siteInputs(a.obs, a.sd, a.infl, a.nObs, s, &used);
+    int32_t* inf = a.info + 4 * (int64_t)s;
+    inf[0] = code; inf[1] = code == kAnalysed ? used : 0; inf[2] = a.site[2 * (int64_t)s + 1]; inf[3] = kept;
+  }
+}
+
+}  // namespace
+
+void enkfRelease(sipnet_batch* b) {
+  if (b->d_enkf) (void)hipFree(b->d_enkf);
+  b->d_enkf = nullptr;
+  b->enkfBytes = 0;
+}
+
+extern "C" {
+
+int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                     const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                     const double* d_obs, const double* d_sd, const double* d_inflation,
+                                     int32_t* d_site_info, void* hip_stream) {
+  const int32_t allPools = (1 << kPools) - 1;
+  auto bad = [](const std::string& why) {
+    setError("sipnet_batch_enkf_analysis_sites: " + why);
+    return SIPNET_ERR_BAD_ARGUMENT;
+  };
+  if (!b || !ops || !d_obs || !d_sd) return bad("a NULL batch, operators, observations or sds");
+  if (n_obs < 1 || n_obs > kMaxObs) return bad("n_obs must be 1..16");
+  if (analysed_mask == 0 || (analysed_mask & ~allPools)) return bad("analysed_mask must name pools 0..12");
+  bool planesUsed = false;
+  for (int i = 0; i < n_obs; i++) {
+    const sipnet_enkf_obs& o = ops[i];
+    const std::string at = "operator " + std::to_string(i) + ": ";
+    if (o.param < -1 || o.param >= SIPNET_NPARAMS) return bad(at + "param is not a parameter index");
+    if (o.kind == SIPNET_ENKF_POOLS) {
+      if (o.pool_mask == 0 || (o.pool_mask & ~allPools)) return bad(at + "pool_mask must name pools 0..12");
+    } else if (o.kind == SIPNET_ENKF_PLANE) {
+      if (o.plane < 0 || o.plane > 2) return bad(at + "plane must be 0 (NEE), 1 (GPP) or 2 (ET)");
+      if (!d_planes || !d_planes[o.plane]) return bad(at + "its plane pointer is NULL");
+      planesUsed = true;
+    } else {
+      return bad(at + "unknown kind");
+    }
+  }
+  if (planesUsed && (n_steps <= 0 || ld < b->ncol)) return bad("planes need n_steps > 0 and ld >= ncol");
+  if (b->ncol > (int64_t)1 << 22) return bad("at most 4194304 members");
+  if (b->pfPeers) return bad("this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
+  int rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int64_t nSites = b->n_sites, M = b->n_members, ncol = b->ncol;
+  if (!d_site_info) {   // the synchronous form: the inputs are checked before anything is launched
+    std::vector<double> obs((size_t)(nSites * n_obs)), sd(obs.size()), infl(d_inflation ? (size_t)nSites : 0);
+    HIP_TRY(hipMemcpyAsync(obs.data(), d_obs, obs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(sd.data(), d_sd, sd.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (d_inflation) HIP_TRY(hipMemcpyAsync(infl.data(), d_inflation, infl.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int64_t s = 0; s < nSites; s++) {
+      int used;
+      if (siteInputs(obs.data(), sd.data(), d_inflation ? infl.data() : nullptr, n_obs, (int)s, &used) == kBadInput)
+        return bad("site " + std::to_string(s) + ": bad input (a finite obs needs a finite sd > 0; the inflation must be finite "
+                   "and >= 1); nothing was written");
+    }
+  }
+  b->pfPre.valid = false;
+  b->pfArm.set = false;
+  rc = orderBehindBusy(b, stream);
+  if (rc) return rc;
+  rc = flushParams(b, stream);
+  if (rc) return rc;
+
+  EnkfArgs a{};
+  a.nObs = n_obs;
+  for (int i = 0; i < n_obs; i++) a.op[i] = EnkfOp{ops[i].kind, ops[i].pool_mask, ops[i].plane, ops[i].param, ops[i].scale};
+  for (int p = 0; p < kPools; p++)
+    if (analysed_mask & (1 << p)) a.pool[a.nA++] = p;
+  a.nv = a.nA + n_obs;
+  a.nCh = (int32_t)((M + 255) / 256);
+  for (int k = 0; k < 3; k++) a.planes[k] = d_planes ? d_planes[k] : nullptr;
+  a.nSteps = n_steps;
+  a.ld = ld;
+  a.obs = d_obs;
+  a.sd = d_sd;
+  a.infl = d_inflation;
+  a.state = b->d_state;
+  a.ncol = ncol;
+  a.M = M;
+  a.siteStatus = b->d_siteStatus;
+  if (b->prmIndexed) {   // (after a resampling with_params: column c's parameters are bank column d_prmId[c])
+    a.prm = b->d_prmBank ? b->d_prmBank : b->d_prm;
+    a.prmPitch = b->d_prmBank ? b->prmBankPitch : ncol;
+    a.prmId = b->d_prmId;
+  } else {
+    a.prm = b->d_prm;
+    a.prmPitch = ncol;
+    a.prmId = nullptr;
+  }
+  // the per-chunk launches unless the sites outnumber the CUs four times over (profiles/r08_enkf_sites_time.txt: one
+  // workgroup per site loses or ties at every shape up to 256 sites x 1 024 members -- 0.29 ms against 0.19); big sites or
+  // SIPNET_KOPT_PF_MULTI_LAUNCH: always the launches
+  const bool group = M <= 256 * kMaxGroupChunks && nSites >= 4 * (int64_t)b->numCUs &&
+                     !(b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
+  const size_t ldsBytes = (size_t)a.nv * (size_t)M * sizeof(double);
+  a.useLds = group && ldsBytes <= (size_t)kLdsWork;
+  // scratch: working copies [nv][ncol] | part [sites][chunks][kMaxVars] | stat [sites][kStat] | info [sites][4],
+  // cnt, kept [sites][chunks], site [sites][2]
+  const size_t nWork = a.useLds ? 0 : (size_t)a.nv * (size_t)ncol;
+  const size_t nPart = group ? 0 : (size_t)nSites * a.nCh * kMaxVars, nStat = group ? 0 : (size_t)nSites * kStat;
+  const size_t nInt = (size_t)nSites * 4 + (group ? 0 : 2 * (size_t)nSites * a.nCh + 2 * (size_t)nSites);
+  const size_t bytes = (nWork + nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t);
+  if (b->enkfBytes < bytes) {
+    rc = waitIdle(b);   // (the old block may still be read by a launch in flight)
+    if (rc) return rc;
+    enkfRelease(b);
+    HIP_TRY(hipMalloc(&b->d_enkf, bytes));
+    b->enkfBytes = bytes;
+  }
+  a.work = (double*)b->d_enkf;
+  a.part = a.work + nWork;
+  a.stat = a.part + nPart;
+  int32_t* ints = (int32_t*)(a.stat + nStat);
+  a.info = d_site_info ? d_site_info : ints;
+  a.cnt = ints + (size_t)nSites * 4;
+  a.kept = a.cnt + (size_t)nSites * a.nCh;
+  a.site = a.kept + (size_t)nSites * a.nCh;
+
+  if (group) {
+    const size_t dyn = a.useLds ? ldsBytes : 0;
+    if (elem_is_f32) hipLaunchKernelGGL(enkfSiteKernel<float>, dim3((unsigned)nSites), dim3(256), dyn, stream, a);
+    else hipLaunchKernelGGL(enkfSiteKernel<double>, dim3((unsigned)nSites), dim3(256), dyn, stream, a);
+  } else {
+    const dim3 chunks((unsigned)nSites, (unsigned)a.nCh), sites((unsigned)nSites);
+    if (elem_is_f32) hipLaunchKernelGGL(enkfLoadKernel<float>, chunks, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(enkfLoadKernel<double>, chunks, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(enkfCodeKernel, sites, dim3(256), 0, stream, a);
+    if (d_inflation) {
+      hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, -1, 0);
+      hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, -1, 0);
+      hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, -1);
+    }
+    for (int i = 0; i < n_obs; i++) {
+      hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, i, 0);
+      hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, i, 0);
+      hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, i, 1);
+      hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, i, 1);
+      hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, i);
+    }
+    hipLaunchKernelGGL(enkfLimitKernel, chunks, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(enkfInfoKernel, sites, dim3(256), 0, stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  b->pfInfo.fused = group ? 1 : 0;
+  b->pfInfo.grid = group ? (int32_t)nSites : 0;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = ncol;
+  return markBusy(b, stream);
+}
+
+}  // extern "C"
