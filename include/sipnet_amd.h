@@ -600,6 +600,55 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch *b, int32_t n_obs, const sipne
                                      const double *d_obs, const double *d_sd, const double *d_inflation,
                                      int32_t *d_site_info, void *hip_stream);
 
+/* ---- localized ensemble Kalman filter across the sites of one batch ---------------------------------------------
+ * Member j of every site is one member of a JOINT ensemble, and an observation moves the sites near it (PEcAn's
+ * multi-site SDA, Dokoohaki et al. 2022).  A localization lists, for each site s, neighbour sites t != s with a taper
+ * rho_st in (0, 1] (HOST CSR arrays: the neighbours of s are nbr[nbr_ptr[s] .. nbr_ptr[s + 1]), rows strictly ascending,
+ * rho alongside); s itself always has rho 1.  Its footprint F(s) is {s} and its neighbours; symmetry is not required.
+ * Inputs are those of sipnet_batch_enkf_analysis_sites.  A site's variables are its analysed pools and the h_{t,i} of its
+ * operators (working copies); L_t its live members (state[29] == 0, site plan status OK).
+ * Codes, before any update (equal to sipnet_batch_enkf_analysis_sites' codes when no site has neighbours): -2 bad input
+ * (the same check); a SOURCE has good inputs, >= 2 live members and a non-NaN observation (that call's code 1); a site is
+ * REACHED when some source s has it in F(s).  Otherwise, a site reached or with a non-NaN observation of its own gets 1
+ * with >= 2 live members, 0 with fewer; every other site -1.  Sites -2, 0 and -1 are left bit-identical, are never a
+ * target, and their observations are not used.  Every code-1 site is inflated with its own lambda first.
+ * Then the observation slots (s, i) in site-major order (s = 0 .. n_sites - 1, then i), a slot skipped when its obs is
+ * NaN or s is not code 1.  Slot (s, i), y, R = sd^2: over L_s (n members) hbar, V = sum (h - hbar)^2 / (n - 1) of
+ * h = h_{s,i}, D = V + R, alpha = 1 / (1 + sqrt(R / D)), innov = y - hbar.  For each code-1 target t in F(s): J = L_s
+ * and L_t (skipped if |J| < 2); the variables of t are its analysed pools and its h of every slot after (s, i); per
+ * variable x, the means of x and h over J, c = sum_J (x - xbar_J)(h - hbar_J), K = rho_st ((c / (|J| - 1)) / D), and
+ * x_j = (x_j + K innov) - (alpha K)(h_j - hbar) for j in J.  h_{s,i} itself is never written.  Last, each code-1 site
+ * gets the limits of sipnet_batch_enkf_analysis_sites (clipping, hasSufficientBiomass) and its live members' analysed
+ * pools are written back.  site_info[s] = {code, own observations used, live members, members kept on their forecast}.
+ * With every list empty the state and site_info equal sipnet_batch_enkf_analysis_sites' bit for bit.
+ * The schedule: slots whose footprints meet are in conflict; the host assigns each slot, in serial order, the level
+ * 1 + (the last level that touched a site of F(s)), none = -1 (empty lists: level(s, i) = i).  Conflicting slots keep
+ * their serial order, and the slots of one level touch disjoint sites, so one launch per level (a workgroup per
+ * (slot, target) pair) gives the serial result; it covers NaN slots too and depends on the lists and n_obs only.
+ * Results do not depend on the schedule (sipnet_debug_enkf_local_serial: one slot per launch) nor on the call.
+ *
+ * sipnet_enkf_local_schedule: host only, no device: checks the lists, fills level_of_slot [n_sites][n_obs] (may be
+ *   NULL) and *n_levels.  SIPNET_ERR_BAD_ARGUMENT (sipnet_last_error says why): nbr_ptr[0] != 0 or decreasing, an index
+ *   out of range or the row's own site, a row not strictly ascending, a rho not finite or outside (0, 1], n_obs outside
+ *   1..16, n_sites < 1.
+ * sipnet_batch_enkf_local_create: the same checks for b's n_sites; the schedule and the lists on b's device.  A
+ *   localization belongs to b and must be destroyed (sipnet_enkf_local_destroy) before b.
+ * sipnet_batch_enkf_analysis_local: everything of sipnet_batch_enkf_analysis_sites (pointers, the synchronous form when
+ *   d_site_info is NULL, the refusals); also SIPNET_ERR_BAD_ARGUMENT for a NULL localization, one made for another batch
+ *   or another n_obs, and more than 4096 members per site. */
+typedef struct sipnet_enkf_local sipnet_enkf_local;
+int sipnet_enkf_local_schedule(int32_t n_sites, int32_t n_obs, const int64_t *nbr_ptr, const int32_t *nbr,
+                               const double *rho, int32_t *level_of_slot, int32_t *n_levels);
+int sipnet_batch_enkf_local_create(sipnet_batch *b, int32_t n_obs, const int64_t *nbr_ptr, const int32_t *nbr,
+                                   const double *rho, sipnet_enkf_local **out);
+int32_t sipnet_enkf_local_levels(const sipnet_enkf_local *L);
+void sipnet_enkf_local_destroy(sipnet_enkf_local *L);
+int sipnet_batch_enkf_analysis_local(sipnet_batch *b, const sipnet_enkf_local *L, int32_t n_obs,
+                                     const sipnet_enkf_obs *ops, int32_t analysed_mask, const void *const d_planes[3],
+                                     int32_t elem_is_f32, int32_t n_steps, int64_t ld, const double *d_obs,
+                                     const double *d_sd, const double *d_inflation, int32_t *d_site_info,
+                                     void *hip_stream);
+
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its
  * range) and known on the device only; RCCL's send / receive sizes are host arguments, so an all-to-all
@@ -891,6 +940,9 @@ int sipnet_debug_plan_compare(sipnet_batch *b, int32_t site, int32_t ignore_log2
  * path without having to produce one. */
 int sipnet_debug_set_num_cus(sipnet_batch *b, int32_t num_cus);
 int sipnet_debug_pf_barrier(sipnet_batch *b, int32_t spin_budget, int32_t absent_workgroup);
+/* sipnet_debug_enkf_local_serial: on != 0 makes sipnet_batch_enkf_analysis_local launch one slot at a time in serial
+ * order instead of one launch per level (the test of the schedule: the results must not change). */
+int sipnet_debug_enkf_local_serial(sipnet_enkf_local *L, int32_t on);
 
 /* Device buffer helpers for callers without their own allocator (the CLI). */
 void *sipnet_dev_alloc(size_t bytes);

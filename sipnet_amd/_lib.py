@@ -171,6 +171,13 @@ SIGNATURES = {
                                                  _P, _P, _P]),
     "sipnet_batch_enkf_analysis_sites": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
                                                    _P, _P, _P, _P]),
+    "sipnet_enkf_local_schedule": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "sipnet_batch_enkf_local_create": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
+    "sipnet_enkf_local_levels": (C.c_int32, [_P]),
+    "sipnet_enkf_local_destroy": (None, [_P]),
+    "sipnet_batch_enkf_analysis_local": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64,
+                                                   _P, _P, _P, _P, _P]),
+    "sipnet_debug_enkf_local_serial": (C.c_int, [_P, C.c_int32]),
     "sipnet_batch_pf_publish": (C.c_int, [_P, C.c_int32, _P]),
     "sipnet_batch_pf_connect": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "sipnet_batch_pf_block_len": (C.c_int64, [_P]),

@@ -73,6 +73,8 @@ class Batch:
 
     # -- lifetime ---------------------------------------------------------------
     def close(self):
+        for loc in list(getattr(self, "_localizations", ())):   # (a localization must go before its batch)
+            loc.close()
         if getattr(self, "h", None):
             self.L.sipnet_batch_destroy(self.h)
             self.h = None
@@ -372,16 +374,46 @@ class Batch:
         operator reads); inflation: one value per site (None: 1).  info_out: int32 device tensor [n_sites][4] for
         {code, observations used, live members, members kept on their forecast} (no host synchronisation); without it the
         call checks the inputs first and raises before anything is written."""
+        args, keep = self._enkf_args("enkf_analysis_sites", obs, sd, operators, analysed, planes, inflation, info_out)
+        check(self.L.sipnet_batch_enkf_analysis_sites(self.h, *args, self._stream()), "enkf_analysis_sites")
+        del keep
+
+    def enkf_localization(self, nbr_ptr, nbr, rho, n_obs):
+        """a localization of this batch's sites for enkf_analysis_local (sipnet_batch_enkf_local_create): site s's neighbours
+        nbr[nbr_ptr[s]:nbr_ptr[s + 1]] (strictly ascending, not s) with tapers rho in (0, 1] -- e.g. sa.gaspari_cohn's CSR
+        arrays -- for n_obs observation columns.  -> an EnkfLocalization (.n_levels, .close()); closing the batch closes it."""
+        from .enkf_local import EnkfLocalization
+        loc = EnkfLocalization(self, nbr_ptr, nbr, rho, n_obs)
+        if not hasattr(self, "_localizations"):
+            import weakref
+            self._localizations = weakref.WeakSet()
+        self._localizations.add(loc)
+        return loc
+
+    def enkf_analysis_local(self, local, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
+        """a localized ensemble Kalman filter analysis across the sites (sipnet_batch_enkf_analysis_local): member j of every
+        site is one member of a joint ensemble, and an observation moves the sites of its footprint, weighted by the
+        localization's tapers.  local: enkf_localization(...) of this batch with n_obs = len(operators); the other
+        arguments as enkf_analysis_sites."""
+        if getattr(local, "h", None) is None:
+            raise ValueError("enkf_analysis_local: the localization is closed")
+        args, keep = self._enkf_args("enkf_analysis_local", obs, sd, operators, analysed, planes, inflation, info_out)
+        check(self.L.sipnet_batch_enkf_analysis_local(self.h, local.h, *args, self._stream()), "enkf_analysis_local")
+        del keep
+
+    def _enkf_args(self, what, obs, sd, operators, analysed, planes, inflation, info_out):
+        """the EnKF analyses' arguments from n_obs to d_site_info, and the uploaded tensors they point into (keep them
+        alive until the call)"""
         from ._lib import EnkfObs
         from .config import pool_mask
         t = self._torch
         ops = list(operators)
         n_obs = len(ops)
 
-        def dev(x, n, what):
+        def dev(x, n, name):
             x = t.as_tensor(x, dtype=t.float64).reshape(-1).to(self.device).contiguous()
             if x.numel() != n:
-                raise ValueError(f"enkf_analysis_sites: {what} needs {n} values, got {x.numel()}")
+                raise ValueError(f"{what}: {name} needs {n} values, got {x.numel()}")
             return x
 
         obs, sd = dev(obs, self.n_sites * n_obs, "obs"), dev(sd, self.n_sites * n_obs, "sd")
@@ -396,21 +428,21 @@ class Batch:
                 if p is None:
                     continue
                 if not p.is_cuda or p.dim() != 2 or p.dtype not in (t.float32, t.float64) or p.stride(1) != 1:
-                    raise ValueError("enkf_analysis_sites: a plane must be a [n_steps][ld] float32 / float64 device tensor "
+                    raise ValueError(f"{what}: a plane must be a [n_steps][ld] float32 / float64 device tensor "
                                      "with unit column stride")
                 ptrs[k] = p.data_ptr()
                 layouts.add((int(p.dtype == t.float32), p.shape[0], p.stride(0)))
             if len(layouts) > 1:
-                raise ValueError("enkf_analysis_sites: the planes differ in dtype, step count or row pitch: " + str(layouts))
+                raise ValueError(f"{what}: the planes differ in dtype, step count or row pitch: " + str(layouts))
             if layouts:
                 f32, n_steps, ld = layouts.pop()
         if info_out is not None and (info_out.dtype != t.int32 or not info_out.is_contiguous() or not info_out.is_cuda
                                      or info_out.numel() != 4 * self.n_sites):
-            raise ValueError("enkf_analysis_sites: info_out must be a contiguous int32 device tensor of n_sites x 4")
-        check(self.L.sipnet_batch_enkf_analysis_sites(
-            self.h, n_obs, arr, pool_mask(analysed), ptrs if planes is not None else None, f32, n_steps, ld,
-            C.c_void_p(obs.data_ptr()), C.c_void_p(sd.data_ptr()), C.c_void_p(infl.data_ptr()) if infl is not None else None,
-            C.c_void_p(info_out.data_ptr()) if info_out is not None else None, self._stream()), "enkf_analysis_sites")
+            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x 4")
+        args = (n_obs, arr, pool_mask(analysed), ptrs if planes is not None else None, f32, n_steps, ld,
+                C.c_void_p(obs.data_ptr()), C.c_void_p(sd.data_ptr()), C.c_void_p(infl.data_ptr()) if infl is not None else None,
+                C.c_void_p(info_out.data_ptr()) if info_out is not None else None)
+        return args, (obs, sd, infl, arr, ptrs)
 
     # -- the filter across ranks by peer reads (sipnet_batch_pf_publish / _connect / _resample_peers) ----------
     def pf_publish(self, with_params=True):

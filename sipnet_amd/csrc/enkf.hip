@@ -8,6 +8,8 @@
 // in segments of segLen(nCh) >= 16 consecutive chunks, each in order from 0.0; one segment is the site's total, several (at
 // most 64) are combined by one wave's xor-shuffle butterfly.  A site of the one-workgroup-per-site kernel has at most 16 chunks,
 // one segment: so that kernel and the per-chunk launches give the same bits.  No grid barrier, no spin, no atomic.
+// sipnet_batch_enkf_analysis_local (the localized analysis across sites) reuses the per-chunk launches around a launch per
+// level of its host schedule: one workgroup per (observation slot, target site), in the one-workgroup sum order.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -55,6 +57,7 @@ struct EnkfArgs {
   int32_t* cnt;                            // split path: [n_sites][nCh] live members / members kept on their forecast
   int32_t* kept;
   int32_t* site;                           // split path: [n_sites][2] the site's code and live count (enkfCodeKernel)
+  int32_t* src;                            // localized analysis: [n_sites] enkfCodeKernel's codes, kept (else null)
   int32_t useLds;                          // one workgroup per site: W in LDS ([nv][M])
 };
 
@@ -111,12 +114,18 @@ __device__ __forceinline__ int segLen(int nCh) { return nCh <= 16 * kMaxSegs ? 1
 // variable q of an observation stage i: the analysed pools, then h_i (q = nA), then the later h
 __device__ __forceinline__ int varOf(const EnkfArgs& a, int q, int i) { return q < a.nA ? q : q + i; }
 
+// the observation's denominator var(h) + R (sd e) from h's centred sum hsum over n members; *alpha its square-root factor
+__device__ __forceinline__ double obsDenom(double hsum, double n, double e, double* alpha) {
+  const double R = e * e, varh = hsum / (n - 1.0), denom = varh + R;
+  *alpha = 1.0 / (1.0 + sqrt(R / denom));
+  return denom;
+}
 // the gains of observation i (sd e) from the centred sums: K_q and alpha K_q of variable q (q = nA: h_i itself, unused)
 __device__ __forceinline__ void gains(const EnkfArgs& a, int q, int V, double n, const double* csum, double e, double* K,
                                       double* aK) {
   if (q >= V) return;
-  const double R = e * e, varh = csum[a.nA] / (n - 1.0), denom = varh + R;
-  const double alpha = 1.0 / (1.0 + sqrt(R / denom));
+  double alpha;
+  const double denom = obsDenom(csum[a.nA], n, e, &alpha);
   const double k = (csum[q] / (n - 1.0)) / denom;
   K[q] = k;
   aK[q] = alpha * k;
@@ -304,6 +313,7 @@ __global__ __launch_bounds__(256) void enkfCodeKernel(EnkfArgs a) {
     if (code == kAnalysed && n < 2) code = kTooFew;
     a.site[2 * (int64_t)s] = code;
     a.site[2 * (int64_t)s + 1] = n;
+    if (a.src) a.src[s] = code;
   }
 }
 
@@ -430,6 +440,76 @@ __global__ __launch_bounds__(256) void enkfInfoKernel(EnkfArgs a) {
   }
 }
 
+// ---- the localized analysis (sipnet_batch_enkf_analysis_local) -------------------------------------------------------------
+// One (slot, target) pair: observation i of site s moves the variables of site t (t in F(s)) with the taper rho.
+struct LocalPair {
+  int32_t s, i, t;
+  double rho;
+};
+
+// one thread per site, after enkfCodeKernel: a site without observations (-1) that a source (a.src == 1) reaches gets 1, or 0
+// with fewer than 2 live members.  The sources are read from a.src, which nothing here writes.
+__global__ __launch_bounds__(256) void enkfReachKernel(EnkfArgs a, const int64_t* inPtr, const int32_t* in, int64_t nSites) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= nSites || a.src[t] != kNoObs) return;
+  for (int64_t k = inPtr[t]; k < inPtr[t + 1]; k++)
+    if (a.src[in[k]] == kAnalysed) {
+      a.site[2 * t] = a.site[2 * t + 1] >= 2 ? kAnalysed : kTooFew;
+      return;
+    }
+}
+
+// one workgroup per (slot, target) pair of a level (M <= 4096: one segment, the one-workgroup-per-site sum order).  The slot's
+// mean and spread of h = h_{s,i} over L_s first, as every pair of the slot computes them; then the means and centred sums of
+// t's variables against h over J = L_s and L_t, and J's members moved.  t's variables: its analysed pools, then its h of the
+// slots after (s, i) (all of them for t > s, those after i for t = s, none for t < s).  Pairs of one level write disjoint
+// sites and read no h_{s,i} that another pair writes.
+__global__ __launch_bounds__(256) void enkfLocalKernel(EnkfArgs a, const LocalPair* pairs, int64_t first) {
+  __shared__ GroupLds g;
+  const LocalPair p = pairs[first + blockIdx.x];
+  const int s = p.s, i = p.i, t = p.t, tid = (int)threadIdx.x, nA = a.nA, nCh = a.nCh;
+  const double y = a.obs[(int64_t)s * a.nObs + i];
+  if (y != y || splitCode(a, s) != kAnalysed || splitCode(a, t) != kAnalysed) return;
+  const double* h = a.work + (int64_t)(nA + i) * a.ncol + (int64_t)s * a.M;
+  double* Wt = a.work + (int64_t)t * a.M;
+  const int hFirst = t > s ? 0 : (t == s ? i + 1 : a.nObs);
+  const int V = a.nObs - hFirst + nA;
+  auto var = [&](int q) { return Wt + (int64_t)(q < nA ? q : q + hFirst) * a.ncol; };
+  auto inJ = [&](int64_t j) { return liveAt(a, s, j) && liveAt(a, t, j); };
+  int mine = 0;
+  for (int64_t j = tid; j < a.M; j += 256) mine += inJ(j) ? 1 : 0;
+  const int nJ = blockCount(g, mine);
+  if (nJ < 2) return;
+  const double n = (double)a.site[2 * (int64_t)s + 1];
+  siteSums(g, 1, nCh, [&](int64_t j, int) { return liveAt(a, s, j) ? h[j] : 0.0; });
+  const double hbar = g.tot[0] / n;
+  siteSums(g, 1, nCh, [&](int64_t j, int) { return liveAt(a, s, j) ? (h[j] - hbar) * (h[j] - hbar) : 0.0; });
+  double alpha;
+  const double D = obsDenom(g.tot[0], n, a.sd[(int64_t)s * a.nObs + i], &alpha);
+  const double nd = (double)nJ;
+  siteSums(g, 1, nCh, [&](int64_t j, int) { return inJ(j) ? h[j] : 0.0; });
+  const double hbarJ = g.tot[0] / nd;
+  siteSums(g, V, nCh, [&](int64_t j, int q) { return inJ(j) ? var(q)[j] : 0.0; });
+  if (tid < V) g.mean[tid] = g.tot[tid] / nd;
+  __syncthreads();
+  siteSums(g, V, nCh, [&](int64_t j, int q) { return inJ(j) ? (var(q)[j] - g.mean[q]) * (h[j] - hbarJ) : 0.0; });
+  if (tid < V) {
+    const double k = p.rho * ((g.tot[tid] / (nd - 1.0)) / D);
+    g.K[tid] = k;
+    g.aK[tid] = alpha * k;
+  }
+  __syncthreads();
+  const double innov = y - hbar;
+  for (int64_t j = tid; j < a.M; j += 256)
+    if (inJ(j)) {
+      const double dh = h[j] - hbar;
+      for (int q = 0; q < V; q++) {
+        double* x = var(q) + j;
+        *x = moved(*x, g.K[q], g.aK[q], innov, dh);
+      }
+    }
+}
+
 }  // namespace
 
 void enkfRelease(sipnet_batch* b) {
@@ -438,15 +518,16 @@ void enkfRelease(sipnet_batch* b) {
   b->enkfBytes = 0;
 }
 
-extern "C" {
+namespace {
 
-int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
-                                     const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
-                                     const double* d_obs, const double* d_sd, const double* d_inflation,
-                                     int32_t* d_site_info, void* hip_stream) {
+// The checks and the arguments both analyses share, up to the scratch block: 0, or the error (the message names `name`).
+// The synchronous form (no d_site_info) reads obs, sd and inflation back and refuses a bad site before anything is written.
+int enkfBegin(const char* name, sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+              const void* const d_planes[3], int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
+              const double* d_inflation, int32_t* d_site_info, hipStream_t stream, EnkfArgs& a) {
   const int32_t allPools = (1 << kPools) - 1;
-  auto bad = [](const std::string& why) {
-    setError("sipnet_batch_enkf_analysis_sites: " + why);
+  auto bad = [name](const std::string& why) {
+    setError(std::string(name) + ": " + why);
     return SIPNET_ERR_BAD_ARGUMENT;
   };
   if (!b || !ops || !d_obs || !d_sd) return bad("a NULL batch, operators, observations or sds");
@@ -472,7 +553,6 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
   if (b->pfPeers) return bad("this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
   int rc = useDevice(b);
   if (rc) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
   const int64_t nSites = b->n_sites, M = b->n_members, ncol = b->ncol;
   if (!d_site_info) {   // the synchronous form: the inputs are checked before anything is launched
     std::vector<double> obs((size_t)(nSites * n_obs)), sd(obs.size()), infl(d_inflation ? (size_t)nSites : 0);
@@ -494,7 +574,7 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
   rc = flushParams(b, stream);
   if (rc) return rc;
 
-  EnkfArgs a{};
+  a = EnkfArgs{};
   a.nObs = n_obs;
   for (int i = 0; i < n_obs; i++) a.op[i] = EnkfOp{ops[i].kind, ops[i].pool_mask, ops[i].plane, ops[i].param, ops[i].scale};
   for (int p = 0; p < kPools; p++)
@@ -520,6 +600,101 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
     a.prmPitch = ncol;
     a.prmId = nullptr;
   }
+  return 0;
+}
+
+// the batch's analysis scratch block, grown to at least `bytes`
+int enkfScratch(sipnet_batch* b, size_t bytes) {
+  if (b->enkfBytes < bytes) {
+    int rc = waitIdle(b);   // (the old block may still be read by a launch in flight)
+    if (rc) return rc;
+    enkfRelease(b);
+    HIP_TRY(hipMalloc(&b->d_enkf, bytes));
+    b->enkfBytes = bytes;
+  }
+  return 0;
+}
+
+// the load, the codes and the inflation of the per-chunk launches (grid: sites x chunks, or sites)
+template <typename T>
+void splitFront(const EnkfArgs& a, dim3 chunks, dim3 sites, hipStream_t stream) {
+  hipLaunchKernelGGL(enkfLoadKernel<T>, chunks, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(enkfCodeKernel, sites, dim3(256), 0, stream, a);
+}
+void splitInflation(const EnkfArgs& a, dim3 chunks, dim3 sites, hipStream_t stream) {
+  hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, -1, 0);
+  hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, -1, 0);
+  hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, -1);
+}
+
+// The localization's lists checked, and the greedy schedule of the slots (s, i) in serial order: level(s, i) = 1 + the last
+// level that touched a site of F(s) = {s} + nbr(s) (none: -1, so empty lists give level i).  Conflicting slots (footprints that
+// meet) are therefore in serial order, and the slots of one level have disjoint footprints.  level: [n_sites][n_obs].
+int localSchedule(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
+                  std::vector<int32_t>& level, int32_t* nLevels) {
+  auto bad = [name](const std::string& why) {
+    setError(std::string(name) + ": " + why);
+    return SIPNET_ERR_BAD_ARGUMENT;
+  };
+  if (nObs < 1 || nObs > kMaxObs) return bad("n_obs must be 1..16");
+  if (nSites < 1 || (int64_t)nSites * nObs > INT32_MAX) return bad("n_sites must be >= 1 (and n_sites x n_obs < 2^31)");
+  if (!ptr) return bad("a NULL nbr_ptr");
+  if (ptr[0] != 0) return bad("nbr_ptr[0] must be 0");
+  for (int32_t s = 0; s < nSites; s++)
+    if (ptr[s + 1] < ptr[s]) return bad("nbr_ptr must be non-decreasing (site " + std::to_string(s) + ")");
+  if (ptr[nSites] > 0 && (!nbr || !rho)) return bad("a NULL nbr or rho with neighbours listed");
+  for (int32_t s = 0; s < nSites; s++)
+    for (int64_t k = ptr[s]; k < ptr[s + 1]; k++) {
+      const std::string at = "site " + std::to_string(s) + ", entry " + std::to_string(k - ptr[s]) + ": ";
+      if (nbr[k] < 0 || nbr[k] >= nSites) return bad(at + "neighbour index out of range");
+      if (nbr[k] == s) return bad(at + "a site is not its own neighbour");
+      if (k > ptr[s] && nbr[k] <= nbr[k - 1]) return bad(at + "a row must be strictly ascending (no duplicates)");
+      if (!(rho[k] > 0.0 && rho[k] <= 1.0)) return bad(at + "rho must be finite and in (0, 1]");
+    }
+  std::vector<int32_t> last((size_t)nSites, -1);
+  level.assign((size_t)nSites * nObs, 0);
+  int32_t top = -1;
+  for (int32_t s = 0; s < nSites; s++)
+    for (int32_t i = 0; i < nObs; i++) {
+      int32_t l = last[s];
+      for (int64_t k = ptr[s]; k < ptr[s + 1]; k++) l = last[nbr[k]] > l ? last[nbr[k]] : l;
+      l += 1;
+      last[s] = l;
+      for (int64_t k = ptr[s]; k < ptr[s + 1]; k++) last[nbr[k]] = l;
+      level[(size_t)s * nObs + i] = l;
+      top = l > top ? l : top;
+    }
+  *nLevels = top + 1;
+  return 0;
+}
+
+}  // namespace
+
+// a localization: the level-ordered table of (slot, target) pairs and the in-neighbour lists, on the batch's device
+struct sipnet_enkf_local {
+  sipnet_batch* b = nullptr;
+  int32_t device = 0, nSites = 0, nObs = 0, nLevels = 0;
+  bool serial = false;                     // sipnet_debug_enkf_local_serial: one slot per launch, in serial order
+  std::vector<int64_t> levelOff;           // [nLevels + 1]: the pairs of level l are [levelOff[l], levelOff[l + 1])
+  std::vector<int64_t> slotOff;            // [n_sites][n_obs]: where slot (s, i)'s 1 + deg(s) pairs start
+  std::vector<int32_t> slotLen;
+  LocalPair* d_pair = nullptr;
+  int64_t* d_inPtr = nullptr;              // [n_sites + 1]: site t is a neighbour of the sites d_in[d_inPtr[t] ..)
+  int32_t* d_in = nullptr;
+};
+
+extern "C" {
+
+int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                     const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                     const double* d_obs, const double* d_sd, const double* d_inflation,
+                                     int32_t* d_site_info, void* hip_stream) {
+  hipStream_t stream = (hipStream_t)hip_stream;
+  EnkfArgs a;
+  int rc = enkfBegin("sipnet_batch_enkf_analysis_sites", b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd,
+                     d_inflation, d_site_info, stream, a);
+  if (rc) return rc;
+  const int64_t nSites = b->n_sites, M = b->n_members, ncol = b->ncol;
   // the per-chunk launches unless the sites outnumber the CUs four times over (profiles/r08_enkf_sites_time.txt: one
   // workgroup per site loses or ties at every shape up to 256 sites x 1 024 members -- 0.29 ms against 0.19); big sites or
   // SIPNET_KOPT_PF_MULTI_LAUNCH: always the launches
@@ -532,14 +707,8 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
   const size_t nWork = a.useLds ? 0 : (size_t)a.nv * (size_t)ncol;
   const size_t nPart = group ? 0 : (size_t)nSites * a.nCh * kMaxVars, nStat = group ? 0 : (size_t)nSites * kStat;
   const size_t nInt = (size_t)nSites * 4 + (group ? 0 : 2 * (size_t)nSites * a.nCh + 2 * (size_t)nSites);
-  const size_t bytes = (nWork + nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t);
-  if (b->enkfBytes < bytes) {
-    rc = waitIdle(b);   // (the old block may still be read by a launch in flight)
-    if (rc) return rc;
-    enkfRelease(b);
-    HIP_TRY(hipMalloc(&b->d_enkf, bytes));
-    b->enkfBytes = bytes;
-  }
+  rc = enkfScratch(b, (nWork + nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t));
+  if (rc) return rc;
   a.work = (double*)b->d_enkf;
   a.part = a.work + nWork;
   a.stat = a.part + nPart;
@@ -555,14 +724,9 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
     else hipLaunchKernelGGL(enkfSiteKernel<double>, dim3((unsigned)nSites), dim3(256), dyn, stream, a);
   } else {
     const dim3 chunks((unsigned)nSites, (unsigned)a.nCh), sites((unsigned)nSites);
-    if (elem_is_f32) hipLaunchKernelGGL(enkfLoadKernel<float>, chunks, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(enkfLoadKernel<double>, chunks, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(enkfCodeKernel, sites, dim3(256), 0, stream, a);
-    if (d_inflation) {
-      hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, -1, 0);
-      hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, -1, 0);
-      hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, -1);
-    }
+    if (elem_is_f32) splitFront<float>(a, chunks, sites, stream);
+    else splitFront<double>(a, chunks, sites, stream);
+    if (d_inflation) splitInflation(a, chunks, sites, stream);
     for (int i = 0; i < n_obs; i++) {
       hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, i, 0);
       hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, i, 0);
@@ -576,6 +740,160 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
   HIP_TRY(hipGetLastError());
   b->pfInfo.fused = group ? 1 : 0;
   b->pfInfo.grid = group ? (int32_t)nSites : 0;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = ncol;
+  return markBusy(b, stream);
+}
+
+int sipnet_enkf_local_schedule(int32_t n_sites, int32_t n_obs, const int64_t* nbr_ptr, const int32_t* nbr, const double* rho,
+                               int32_t* level_of_slot, int32_t* n_levels) {
+  if (!n_levels) {
+    setError("sipnet_enkf_local_schedule: a NULL n_levels");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  std::vector<int32_t> level;
+  int rc = localSchedule("sipnet_enkf_local_schedule", n_sites, n_obs, nbr_ptr, nbr, rho, level, n_levels);
+  if (rc) return rc;
+  if (level_of_slot) std::copy(level.begin(), level.end(), level_of_slot);
+  return SIPNET_OK;
+}
+
+void sipnet_enkf_local_destroy(sipnet_enkf_local* L) {
+  if (!L) return;
+  (void)hipSetDevice(L->device);
+  if (L->d_pair) (void)hipFree(L->d_pair);
+  if (L->d_inPtr) (void)hipFree(L->d_inPtr);
+  if (L->d_in) (void)hipFree(L->d_in);
+  delete L;
+}
+
+int sipnet_batch_enkf_local_create(sipnet_batch* b, int32_t n_obs, const int64_t* nbr_ptr, const int32_t* nbr,
+                                   const double* rho, sipnet_enkf_local** out) {
+  const char* name = "sipnet_batch_enkf_local_create";
+  if (!b || !out) {
+    setError(std::string(name) + ": a NULL batch or out");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  *out = nullptr;
+  std::vector<int32_t> level;
+  int32_t nLevels = 0;
+  const int32_t nSites = b->n_sites;
+  int rc = localSchedule(name, nSites, n_obs, nbr_ptr, nbr, rho, level, &nLevels);
+  if (rc) return rc;
+  rc = useDevice(b);
+  if (rc) return rc;
+  // the pairs sorted by level; within a level by slot in serial order, a slot's own site first
+  std::vector<int64_t> levelOff((size_t)nLevels + 1, 0);
+  for (int32_t s = 0; s < nSites; s++)
+    for (int32_t i = 0; i < n_obs; i++) levelOff[(size_t)level[(size_t)s * n_obs + i] + 1] += 1 + (nbr_ptr[s + 1] - nbr_ptr[s]);
+  for (int32_t l = 0; l < nLevels; l++) levelOff[l + 1] += levelOff[l];
+  std::vector<LocalPair> pairs((size_t)levelOff[nLevels]);
+  std::vector<int64_t> fill(levelOff.begin(), levelOff.end() - 1), slotOff((size_t)nSites * n_obs);
+  std::vector<int32_t> slotLen((size_t)nSites * n_obs);
+  for (int32_t s = 0; s < nSites; s++)
+    for (int32_t i = 0; i < n_obs; i++) {
+      int64_t& k = fill[level[(size_t)s * n_obs + i]];
+      slotOff[(size_t)s * n_obs + i] = k;
+      slotLen[(size_t)s * n_obs + i] = (int32_t)(1 + nbr_ptr[s + 1] - nbr_ptr[s]);
+      pairs[(size_t)k++] = LocalPair{s, i, s, 1.0};
+      for (int64_t e = nbr_ptr[s]; e < nbr_ptr[s + 1]; e++) pairs[(size_t)k++] = LocalPair{s, i, nbr[e], rho[e]};
+    }
+  // the in-neighbour lists: site t is reached from the sites that list it
+  std::vector<int64_t> inPtr((size_t)nSites + 1, 0);
+  for (int64_t e = 0; e < nbr_ptr[nSites]; e++) inPtr[(size_t)nbr[e] + 1]++;
+  for (int32_t t = 0; t < nSites; t++) inPtr[t + 1] += inPtr[t];
+  std::vector<int32_t> in((size_t)inPtr[nSites]);
+  std::vector<int64_t> at(inPtr.begin(), inPtr.end() - 1);
+  for (int32_t s = 0; s < nSites; s++)
+    for (int64_t e = nbr_ptr[s]; e < nbr_ptr[s + 1]; e++) in[(size_t)at[nbr[e]]++] = s;
+
+  sipnet_enkf_local* L = new sipnet_enkf_local;
+  L->b = b;
+  L->device = b->device;
+  L->nSites = nSites;
+  L->nObs = n_obs;
+  L->nLevels = nLevels;
+  L->levelOff = std::move(levelOff);
+  L->slotOff = std::move(slotOff);
+  L->slotLen = std::move(slotLen);
+  auto upload = [](void** d, const void* h, size_t bytes) -> int {
+    HIP_TRY(hipMalloc(d, bytes > 0 ? bytes : 8));
+    if (bytes) HIP_TRY(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+    return 0;
+  };
+  if ((rc = upload((void**)&L->d_pair, pairs.data(), pairs.size() * sizeof(LocalPair))) ||
+      (rc = upload((void**)&L->d_inPtr, inPtr.data(), inPtr.size() * sizeof(int64_t))) ||
+      (rc = upload((void**)&L->d_in, in.data(), in.size() * sizeof(int32_t)))) {
+    sipnet_enkf_local_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return SIPNET_OK;
+}
+
+int32_t sipnet_enkf_local_levels(const sipnet_enkf_local* L) { return L ? L->nLevels : 0; }
+
+int sipnet_debug_enkf_local_serial(sipnet_enkf_local* L, int32_t on) {
+  if (!L) {
+    setError("sipnet_debug_enkf_local_serial: a NULL localization");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  L->serial = on != 0;
+  return SIPNET_OK;
+}
+
+int sipnet_batch_enkf_analysis_local(sipnet_batch* b, const sipnet_enkf_local* L, int32_t n_obs, const sipnet_enkf_obs* ops,
+                                     int32_t analysed_mask, const void* const d_planes[3], int32_t elem_is_f32,
+                                     int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
+                                     const double* d_inflation, int32_t* d_site_info, void* hip_stream) {
+  const char* name = "sipnet_batch_enkf_analysis_local";
+  auto bad = [name](const std::string& why) {
+    setError(std::string(name) + ": " + why);
+    return SIPNET_ERR_BAD_ARGUMENT;
+  };
+  if (!b || !L) return bad("a NULL batch or localization");
+  if (L->b != b) return bad("the localization belongs to another batch");
+  if (L->nObs != n_obs) return bad("the localization was made for n_obs = " + std::to_string(L->nObs));
+  if (b->n_members > 256 * kMaxGroupChunks) return bad("at most 4096 members per site");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  EnkfArgs a;
+  int rc = enkfBegin(name, b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream, a);
+  if (rc) return rc;
+  const int64_t nSites = b->n_sites, ncol = b->ncol;
+  // scratch: the per-chunk launches' layout (working copies | part | stat | info, cnt, kept, site), then src [sites]
+  const size_t nWork = (size_t)a.nv * (size_t)ncol, nPart = (size_t)nSites * a.nCh * kMaxVars, nStat = (size_t)nSites * kStat;
+  const size_t nInt = (size_t)nSites * 4 + 2 * (size_t)nSites * a.nCh + 3 * (size_t)nSites;
+  rc = enkfScratch(b, (nWork + nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t));
+  if (rc) return rc;
+  a.work = (double*)b->d_enkf;
+  a.part = a.work + nWork;
+  a.stat = a.part + nPart;
+  int32_t* ints = (int32_t*)(a.stat + nStat);
+  a.info = d_site_info ? d_site_info : ints;
+  a.cnt = ints + (size_t)nSites * 4;
+  a.kept = a.cnt + (size_t)nSites * a.nCh;
+  a.site = a.kept + (size_t)nSites * a.nCh;
+  a.src = a.site + 2 * (size_t)nSites;
+
+  const dim3 chunks((unsigned)nSites, (unsigned)a.nCh), sites((unsigned)nSites);
+  if (elem_is_f32) splitFront<float>(a, chunks, sites, stream);
+  else splitFront<double>(a, chunks, sites, stream);
+  hipLaunchKernelGGL(enkfReachKernel, dim3((unsigned)((nSites + 255) / 256)), dim3(256), 0, stream, a, L->d_inPtr, L->d_in,
+                     nSites);
+  if (d_inflation) splitInflation(a, chunks, sites, stream);
+  if (L->serial) {
+    for (size_t k = 0; k < L->slotOff.size(); k++)
+      hipLaunchKernelGGL(enkfLocalKernel, dim3((unsigned)L->slotLen[k]), dim3(256), 0, stream, a, L->d_pair, L->slotOff[k]);
+  } else {
+    for (int32_t l = 0; l < L->nLevels; l++)
+      hipLaunchKernelGGL(enkfLocalKernel, dim3((unsigned)(L->levelOff[l + 1] - L->levelOff[l])), dim3(256), 0, stream, a,
+                         L->d_pair, L->levelOff[l]);
+  }
+  hipLaunchKernelGGL(enkfLimitKernel, chunks, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(enkfInfoKernel, sites, dim3(256), 0, stream, a);
+  HIP_TRY(hipGetLastError());
+  b->pfInfo.fused = 0;
+  b->pfInfo.grid = 0;
   b->pfInfo.budget = 0;
   b->pfInfo.nSlots = ncol;
   return markBusy(b, stream);
