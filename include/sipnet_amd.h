@@ -649,6 +649,49 @@ int sipnet_batch_enkf_analysis_local(sipnet_batch *b, const sipnet_enkf_local *L
                                      const double *d_sd, const double *d_inflation, int32_t *d_site_info,
                                      void *hip_stream);
 
+/* ---- block-local ensemble Kalman filter: every site analysed on its own, in one pass ------------------------------
+ * A LOCAL ANALYSIS (the LETKF family, Hunt et al. 2007): each target site is its own filter over the observations
+ * within its reach, on private copies of what they predict, and the observation error is localized instead of the
+ * covariance: an observation that reaches a target with taper rho has variance R / rho there.  Nothing a target reads
+ * is written by another target, so the number of launches is a constant, whatever the lists look like.  This is a
+ * DIFFERENT filter from sipnet_batch_enkf_analysis_local, not another route to its numbers: there every site sees the
+ * updates its neighbours' observations made to the joint ensemble, in serial order; here a target sees its neighbours'
+ * forecasts only.  The two agree when every site reaches every other with rho = 1 and all members are live, and both
+ * equal sipnet_batch_enkf_analysis_sites (to rounding here) when the lists are empty.
+ * The localization L, the inputs, the live members L_t, the operators h, the codes (-2, -1, 0, 1, sources, reached
+ * sites) and the inflation of every code-1 site are exactly those of sipnet_batch_enkf_analysis_local; sites with a
+ * code other than 1 stay bit-identical.
+ * The rows of a code-1 target t (n = |L_t|): every slot (u, i) with u code 1, obs[u][i] not NaN and t in F(u), in
+ * site-major order (u ascending, then i); the taper is rho_ut, 1 for u = t.  A row from u != t is DROPPED when some
+ * member of L_t is not live at u.  d_rows (DEVICE, [n_sites][2] int32, may be NULL) gets {rows used, rows dropped} of
+ * every site (0, 0 for a code other than 1).
+ * t takes a private copy of h_{u,i} over L_t for each of its rows (after u's inflation), then runs the serial
+ * square-root filter of sipnet_batch_enkf_analysis_sites over them, all statistics over L_t with divisor n - 1:
+ * R = sd[u][i]^2 / rho_ut, D = var(h) + R, alpha = 1 / (1 + sqrt(R / D)), K_v = cov(x_v, h) / D,
+ * x_v += K_v (y - mean(h)) - alpha K_v (h - mean(h)) for t's analysed pools and its later private rows.  No other
+ * site's working copy is read after the copy, or written at all.  Then the limits (clipping, hasSufficientBiomass),
+ * the write-back and site_info of sipnet_batch_enkf_analysis_sites ({code, own observations used, live members,
+ * members kept on their forecast}).
+ * The arithmetic is that update carried out on the (pools + rows) x rows sample covariance of the target, which the
+ * update is linear in: one pass over the members forms it, the chain of rows works on it alone, one pass applies the
+ * accumulated transform.  The result equals the member-space update to rounding (tests: 1e-10 of max(|x|, ensemble
+ * sd)), every sum is taken in one fixed order (a repeated call gives the same bits), and a target's result does not
+ * depend on which other sites the lists hold.  The small matrices live in LDS when the largest target's fit, else in
+ * global memory; sipnet_batch_pf_info's fused says which (1: LDS), the bits are the same.
+ * Refusals and the synchronous form (d_site_info NULL) as sipnet_batch_enkf_analysis_local; also, before any launch,
+ * SIPNET_ERR_BAD_ARGUMENT when some site's n_obs x (1 + in-neighbours) exceeds SIPNET_ENKF_BLOCK_MAX_ROWS.
+ * sipnet_enkf_local_rows: host only, no device: the list checks of sipnet_enkf_local_schedule (there are no tapers
+ *   to check), then rows_of_site [n_sites] (may be NULL) = n_obs x (1 + in-neighbours) and *max_rows (may be NULL),
+ *   so that a caller can ask first.  sipnet_batch_enkf_local_create accepts lists beyond the cap as before. */
+#define SIPNET_ENKF_BLOCK_MAX_ROWS 128
+int sipnet_enkf_local_rows(int32_t n_sites, int32_t n_obs, const int64_t *nbr_ptr, const int32_t *nbr,
+                           int32_t *rows_of_site, int32_t *max_rows);
+int sipnet_batch_enkf_analysis_block(sipnet_batch *b, const sipnet_enkf_local *L, int32_t n_obs,
+                                     const sipnet_enkf_obs *ops, int32_t analysed_mask, const void *const d_planes[3],
+                                     int32_t elem_is_f32, int32_t n_steps, int64_t ld, const double *d_obs,
+                                     const double *d_sd, const double *d_inflation, int32_t *d_site_info,
+                                     int32_t *d_rows, void *hip_stream);
+
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its
  * range) and known on the device only; RCCL's send / receive sizes are host arguments, so an all-to-all

@@ -10,8 +10,11 @@
 // one segment: so that kernel and the per-chunk launches give the same bits.  No grid barrier, no spin, no atomic.
 // sipnet_batch_enkf_analysis_local (the localized analysis across sites) reuses the per-chunk launches around a launch per
 // level of its host schedule: one workgroup per (observation slot, target site), in the one-workgroup sum order.
+// sipnet_batch_enkf_analysis_block (the block-local analysis) reuses them around ONE launch, a workgroup per target site, that
+// runs the target's serial update on its small sample covariance (below).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -510,6 +513,255 @@ __global__ __launch_bounds__(256) void enkfLocalKernel(EnkfArgs a, const LocalPa
     }
 }
 
+
+// ---- the block-local analysis (sipnet_batch_enkf_analysis_block) -----------------------------------------------------------
+// One workgroup per target site t, all targets in one launch.  t's variables are its nA analysed pools and p rows: the predicted
+// observations h_{u,i} of the code-1 sites u that reach it (and its own), read over L_t from the working copies, which nothing
+// writes after the inflation -- so the private copies of the contract need no memory.  The serial square-root update is linear
+// in the variables, so it runs on their sample covariance: one pass over the members forms C = cov(variable, row) ([nA + p][p]),
+// the chain of p updates works on C, the means and the transform T (variable = its forecast + sum_w T[.][w] (row w's forecast
+// anomaly)) alone, and a last pass applies T to the members.  Since alpha (2 - alpha var(h) / D) = 1, a step takes C to its
+// Schur complement: C[v][w] -= K_v C[h][w].
+// The matrices: Cx, Tx [nA][p] of the pools; S [p][p] holds C of the rows in its upper triangle (S[k][w], w >= k) and T of the
+// rows strictly below the diagonal (T[k][k] = 1 is implied).  They live in LDS, where the staging tile was, when every target's
+// fit (kLds), else in the target's block of global memory.  Every sum is taken in one order: the members in order.
+constexpr int kBlockRows = SIPNET_ENKF_BLOCK_MAX_ROWS;
+constexpr int kBlockVars = kPools + kBlockRows;
+constexpr int kTile = 32;                  // members staged per tile
+constexpr int kBlockMembers = 256 * kMaxGroupChunks;
+constexpr int kBatch = 8;                  // loads in flight per thread before their stores
+constexpr int kBlockMaxTiles = 32 * 33 / 2 + 4 * 32;   // blocks of 4 x 4 entries of C at 128 rows and 13 pools
+constexpr int kBlockSmall = 48;            // targets of up to this many rows and 512 members: 256 threads; else 1024 (the chain
+                                           // is a chain of LDS latencies that more waves hide; small targets only pay for their
+                                           // barriers).  The arithmetic does not depend on the number of threads.
+
+struct BlockLds {
+  int64_t rowOff[kBlockVars];              // variable v of member j: a.work[rowOff[v] + j] (v < nA: t's pools, then its rows)
+  double y[kBlockRows], R[kBlockRows];
+  double mean0[kBlockVars], mean[kBlockVars], K[kBlockVars];
+  int32_t srcOk[kBlockRows];               // in-neighbour k: every member of L_t is live there
+  double alpha;
+  int32_t p, selfPos;
+  unsigned char flag[kBlockRows];          // slot (source, operator) of t: 1 a row, 2 a dropped row
+  uint16_t tile[kBlockMaxTiles];           // C's blocks of 4 x 4 entries: (row block << 8) | column block
+  unsigned char live[kBlockMembers];
+};
+__host__ __device__ inline int round4(int x) { return (x + 3) & ~3; }
+// doubles of a target's matrices and of the staging tile
+__host__ __device__ inline size_t blockMatSize(int nA, int p) { return (size_t)(p + 2 * nA) * (size_t)p; }
+__host__ __device__ inline int blockStagePitch(int nA, int p) { return round4(round4(p) + nA); }
+
+template <bool kLds, int kBlockThreads>
+__global__ __launch_bounds__(kBlockThreads) void enkfBlockKernel(EnkfArgs a, const int64_t* inPtr, const int32_t* in, const double* inRho,
+                                                       double* matGlobal, int64_t matPitch, int32_t* rowsOut) {
+  constexpr int kBlockTiles = (kBlockMaxTiles + kBlockThreads - 1) / kBlockThreads;   // blocks of 4 x 4 entries of C a thread owns
+  extern __shared__ __attribute__((aligned(16))) double blockDyn[];
+  __shared__ BlockLds g;
+  const int t = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, nA = a.nA;
+  const int64_t M = a.M;
+  if (splitCode(a, t) != kAnalysed) {
+    if (rowsOut && tid < 2) rowsOut[2 * (int64_t)t + tid] = 0;
+    return;
+  }
+  for (int64_t j = tid; j < M; j += kBlockThreads) g.live[j] = liveAt(a, t, j) ? 1 : 0;
+  __syncthreads();
+  // which in-neighbours cover L_t
+  const int64_t in0 = inPtr[t], nIn = inPtr[t + 1] - in0;
+  for (int k = wave; k < nIn; k += kBlockThreads / 64) {
+    const int u = in[in0 + k];
+    int missing = 0;
+    if (splitCode(a, u) == kAnalysed)
+      for (int64_t j = lane; j < M; j += 64) missing += g.live[j] && !liveAt(a, u, j) ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) missing += __shfl_xor(missing, off, 64);
+    if (lane == 0) g.srcOk[k] = missing == 0;
+  }
+  if (tid < nIn && in[in0 + tid] < t && (tid + 1 == nIn || in[in0 + tid + 1] > t)) g.selfPos = tid + 1;   // (one writer)
+  if (tid == 0 && (nIn == 0 || in[in0] > t)) g.selfPos = 0;
+  __syncthreads();
+  // the rows in site-major order: t takes its place among its in-neighbours (ascending); a thread per slot (source, operator)
+  const int nSlots = ((int)nIn + 1) * a.nObs;   // (at most kBlockRows: the host refuses lists beyond the cap)
+  int flag = 0;                                 // 1 a row, 2 a dropped row
+  double y = 0.0, R = 0.0;
+  int64_t off = 0;
+  if (tid < nSlots) {
+    const int q = tid / a.nObs, i = tid - q * a.nObs, selfPos = g.selfPos;
+    const bool self = q == selfPos;
+    const int64_t k = in0 + (q < selfPos ? q : q - 1);
+    const int u = self ? t : in[k];
+    const double rho = self ? 1.0 : inRho[k], e = a.sd[(int64_t)u * a.nObs + i];
+    y = a.obs[(int64_t)u * a.nObs + i];
+    if (splitCode(a, u) == kAnalysed && y == y) flag = self || g.srcOk[k - in0] ? 1 : 2;
+    R = (e * e) / rho;
+    off = (int64_t)(nA + i) * a.ncol + (int64_t)u * M;
+    g.flag[tid] = (unsigned char)flag;
+  }
+  __syncthreads();
+  if (flag == 1) {
+    int row = 0;
+    for (int e = 0; e < tid; e++) row += g.flag[e] == 1 ? 1 : 0;
+    g.rowOff[nA + row] = off;
+    g.y[row] = y;
+    g.R[row] = R;
+  }
+  if (tid < nA) g.rowOff[tid] = (int64_t)tid * a.ncol + (int64_t)t * M;
+  if (tid == 0) {
+    int p = 0, dropped = 0;
+    for (int e = 0; e < nSlots; e++) {
+      p += g.flag[e] == 1 ? 1 : 0;
+      dropped += g.flag[e] == 2 ? 1 : 0;
+    }
+    g.p = p;
+    if (rowsOut) {
+      rowsOut[2 * (int64_t)t] = p;
+      rowsOut[2 * (int64_t)t + 1] = dropped;
+    }
+  }
+  __syncthreads();
+  const int p = g.p, V = nA + p;
+  if (p == 0) return;   // (its pools stay as inflated; the limits follow)
+  const double nd = (double)a.site[2 * (int64_t)t + 1];
+  const int P4 = round4(p), pitch = blockStagePitch(nA, p);
+  double* stage = blockDyn;                                       // [kTile][pitch]: the rows first, then the pools
+  double* S = kLds ? blockDyn : matGlobal + (int64_t)t * matPitch;
+  double* Cx = S + (size_t)p * p;
+  double* Tx = Cx + (size_t)nA * p;
+  // the forecast means
+  for (int vb = wave; vb < V; vb += kBlockThreads / 16) {   // (four variables of a wave at a time: their loads overlap)
+    double sum[4] = {};
+    for (int64_t j = lane; j < M; j += 64)
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+        if (vb + kBlockThreads / 64 * u < V) sum[u] += g.live[j] ? a.work[g.rowOff[vb + kBlockThreads / 64 * u] + j] : 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const double tot = waveSum(sum[u]);
+      if (lane == 0 && vb + kBlockThreads / 64 * u < V) g.mean0[vb + kBlockThreads / 64 * u] = g.mean[vb + kBlockThreads / 64 * u] = tot / nd;
+    }
+  }
+  // the blocks of 4 x 4 entries of C in staging order (the rows, then the pools): of the rows' blocks only those on or above
+  // the diagonal.  Block number k belongs to thread k % kBlockThreads.
+  const int nWt = P4 / 4, nXt = (pitch - P4) / 4, nTri = nWt * (nWt + 1) / 2, nB = nTri + nXt * nWt;
+  for (int rt = tid; rt < nWt + nXt; rt += kBlockThreads) {
+    const int first = rt < nWt ? rt : 0, at = rt < nWt ? rt * nWt - rt * (rt - 1) / 2 : nTri + (rt - nWt) * nWt;
+    for (int wt = first; wt < nWt; wt++) g.tile[at + wt - first] = (uint16_t)((rt << 8) | wt);
+  }
+  __syncthreads();
+  // C: the centred products, a tile of members at a time.  A thread keeps its blocks in registers over all the tiles, so an
+  // entry is the sum over the members in order, and the staging tile shares its LDS with the matrices, written afterwards.
+  int r0[kBlockTiles], w0[kBlockTiles];
+  double acc[kBlockTiles][4][4] = {};
+#pragma unroll
+  for (int k = 0; k < kBlockTiles; k++) {
+    const int blk = tid + kBlockThreads * k;
+    r0[k] = blk < nB ? 4 * (g.tile[blk] >> 8) : -1;
+    w0[k] = blk < nB ? 4 * (g.tile[blk] & 255) : 0;
+  }
+  for (int64_t j0 = 0; j0 < M; j0 += kTile) {
+    for (int k0 = tid; k0 < pitch * kTile; k0 += kBlockThreads * kBatch) {   // (a batch of loads, then its stores)
+      double val[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; u++) {
+        const int k = k0 + kBlockThreads * u, sv = k / kTile, jj = k % kTile;
+        const int v = sv < P4 ? (sv < p ? nA + sv : -1) : (sv - P4 < nA ? sv - P4 : -1);
+        const int64_t j = j0 + jj;
+        val[u] = k < pitch * kTile && v >= 0 && j < M && g.live[j] ? a.work[g.rowOff[v] + j] - g.mean0[v] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; u++) {
+        const int k = k0 + kBlockThreads * u;
+        if (k < pitch * kTile) stage[(k % kTile) * pitch + k / kTile] = val[u];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kBlockTiles; k++)
+      if (r0[k] >= 0)
+        for (int jj = 0; jj < kTile; jj++) {
+          const double2* ra = (const double2*)(stage + jj * pitch + r0[k]);
+          const double2* wb = (const double2*)(stage + jj * pitch + w0[k]);
+          const double2 a0 = ra[0], a1 = ra[1], b0 = wb[0], b1 = wb[1];
+          const double av[4] = {a0.x, a0.y, a1.x, a1.y}, bv[4] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) acc[k][r][c] += av[r] * bv[c];
+        }
+    __syncthreads();
+  }
+  for (size_t k = tid; k < blockMatSize(nA, p); k += kBlockThreads) S[k] = 0.0;   // (T starts at 0: its unit diagonal is implied)
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kBlockTiles; k++)
+    if (r0[k] >= 0)
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          const int sv = r0[k] + r, w = w0[k] + c;
+          if (w >= p) continue;
+          if (sv < P4) {
+            if (sv < p && w >= sv) S[(size_t)sv * p + w] = acc[k][r][c] / (nd - 1.0);
+          } else if (sv - P4 < nA) {
+            Cx[(size_t)(sv - P4) * p + w] = acc[k][r][c] / (nd - 1.0);
+          }
+        }
+  __syncthreads();
+  // the chain
+  for (int l = 0; l < p; l++) {
+    const double* Sl = S + (size_t)l * p;
+    const double innov = g.y[l] - g.mean[nA + l];
+    if (tid < V) {   // (the divisions and the square root in the few waves that hold a variable, not in all of them)
+      const double R = g.R[l], D = Sl[l] + R;
+      g.K[tid] = tid < nA ? Cx[(size_t)tid * p + l] / D : (tid - nA > l ? Sl[tid - nA] / D : 0.0);
+      if (tid == 0) g.alpha = 1.0 / (1.0 + sqrt(R / D));
+    }
+    __syncthreads();
+    const double alpha = g.alpha;
+    if (tid < V) g.mean[tid] += g.K[tid] * innov;
+    // the pools, then the rows after l: column w of kBatch of them at a time (their loads, then their stores).  Left of the
+    // diagonal entry l the column is T's, right of it C's; of a row k's C only w >= k is kept.
+    const int nR = nA + (p - 1 - l), w = tid & 127;
+    if (w < p) {
+      const double slw = Sl[w];
+      for (int rb = tid >> 7; rb < nR; rb += kBlockThreads / 128 * kBatch) {
+        double val[kBatch], K[kBatch];
+        int at[kBatch];   // (the entry's place counted from S: S | Cx | Tx)
+#pragma unroll
+        for (int u = 0; u < kBatch; u++) {
+          const int r = rb + kBlockThreads / 128 * u, k = r < nA ? -1 : l + 1 + (r - nA);
+          at[u] = -1;
+          if (r < nR && (w <= l || k < 0 || w >= k)) at[u] = (k >= 0 ? k : p + (w <= l ? nA : 0) + r) * p + w;
+          K[u] = r < nR ? g.K[k < 0 ? r : nA + k] : 0.0;
+          val[u] = at[u] >= 0 && w != l ? S[at[u]] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; u++)
+          if (at[u] >= 0) S[at[u]] = w < l ? val[u] - (alpha * K[u]) * slw : (w == l ? -(alpha * K[u]) : val[u] - K[u] * slw);
+      }
+    }
+    __syncthreads();
+  }
+  // the members: forecast + the mean's shift + T x (the rows' forecast anomalies)
+  for (int64_t j = tid; j < M; j += kBlockThreads)
+    if (g.live[j]) {
+      double acc[kPools] = {};
+#pragma unroll 8
+      for (int w = 0; w < p; w++) {
+        const double d = a.work[g.rowOff[nA + w] + j] - g.mean0[nA + w];
+#pragma unroll
+        for (int q = 0; q < kPools; q++)
+          if (q < nA) acc[q] += Tx[(size_t)q * p + w] * d;
+      }
+#pragma unroll
+      for (int q = 0; q < kPools; q++)
+        if (q < nA) {
+          double* x = a.work + g.rowOff[q] + j;
+          *x = (*x + (g.mean[q] - g.mean0[q])) + acc[q];
+        }
+    }
+}
+
 }  // namespace
 
 void enkfRelease(sipnet_batch* b) {
@@ -630,27 +882,12 @@ void splitInflation(const EnkfArgs& a, dim3 chunks, dim3 sites, hipStream_t stre
 // The localization's lists checked, and the greedy schedule of the slots (s, i) in serial order: level(s, i) = 1 + the last
 // level that touched a site of F(s) = {s} + nbr(s) (none: -1, so empty lists give level i).  Conflicting slots (footprints that
 // meet) are therefore in serial order, and the slots of one level have disjoint footprints.  level: [n_sites][n_obs].
+int localLists(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
+               bool withRho);
 int localSchedule(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
                   std::vector<int32_t>& level, int32_t* nLevels) {
-  auto bad = [name](const std::string& why) {
-    setError(std::string(name) + ": " + why);
-    return SIPNET_ERR_BAD_ARGUMENT;
-  };
-  if (nObs < 1 || nObs > kMaxObs) return bad("n_obs must be 1..16");
-  if (nSites < 1 || (int64_t)nSites * nObs > INT32_MAX) return bad("n_sites must be >= 1 (and n_sites x n_obs < 2^31)");
-  if (!ptr) return bad("a NULL nbr_ptr");
-  if (ptr[0] != 0) return bad("nbr_ptr[0] must be 0");
-  for (int32_t s = 0; s < nSites; s++)
-    if (ptr[s + 1] < ptr[s]) return bad("nbr_ptr must be non-decreasing (site " + std::to_string(s) + ")");
-  if (ptr[nSites] > 0 && (!nbr || !rho)) return bad("a NULL nbr or rho with neighbours listed");
-  for (int32_t s = 0; s < nSites; s++)
-    for (int64_t k = ptr[s]; k < ptr[s + 1]; k++) {
-      const std::string at = "site " + std::to_string(s) + ", entry " + std::to_string(k - ptr[s]) + ": ";
-      if (nbr[k] < 0 || nbr[k] >= nSites) return bad(at + "neighbour index out of range");
-      if (nbr[k] == s) return bad(at + "a site is not its own neighbour");
-      if (k > ptr[s] && nbr[k] <= nbr[k - 1]) return bad(at + "a row must be strictly ascending (no duplicates)");
-      if (!(rho[k] > 0.0 && rho[k] <= 1.0)) return bad(at + "rho must be finite and in (0, 1]");
-    }
+  int rc = localLists(name, nSites, nObs, ptr, nbr, rho, true);
+  if (rc) return rc;
   std::vector<int32_t> last((size_t)nSites, -1);
   level.assign((size_t)nSites * nObs, 0);
   int32_t top = -1;
@@ -667,6 +904,39 @@ int localSchedule(const char* name, int32_t nSites, int32_t nObs, const int64_t*
   *nLevels = top + 1;
   return 0;
 }
+// the checks of a localization's lists (withRho: and of its tapers)
+int localLists(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
+               bool withRho) {
+  auto bad = [name](const std::string& why) {
+    setError(std::string(name) + ": " + why);
+    return SIPNET_ERR_BAD_ARGUMENT;
+  };
+  if (nObs < 1 || nObs > kMaxObs) return bad("n_obs must be 1..16");
+  if (nSites < 1 || (int64_t)nSites * nObs > INT32_MAX) return bad("n_sites must be >= 1 (and n_sites x n_obs < 2^31)");
+  if (!ptr) return bad("a NULL nbr_ptr");
+  if (ptr[0] != 0) return bad("nbr_ptr[0] must be 0");
+  for (int32_t s = 0; s < nSites; s++)
+    if (ptr[s + 1] < ptr[s]) return bad("nbr_ptr must be non-decreasing (site " + std::to_string(s) + ")");
+  if (ptr[nSites] > 0 && (!nbr || (withRho && !rho))) return bad("a NULL nbr or rho with neighbours listed");
+  for (int32_t s = 0; s < nSites; s++)
+    for (int64_t k = ptr[s]; k < ptr[s + 1]; k++) {
+      const std::string at = "site " + std::to_string(s) + ", entry " + std::to_string(k - ptr[s]) + ": ";
+      if (nbr[k] < 0 || nbr[k] >= nSites) return bad(at + "neighbour index out of range");
+      if (nbr[k] == s) return bad(at + "a site is not its own neighbour");
+      if (k > ptr[s] && nbr[k] <= nbr[k - 1]) return bad(at + "a row must be strictly ascending (no duplicates)");
+      if (withRho && !(rho[k] > 0.0 && rho[k] <= 1.0)) return bad(at + "rho must be finite and in (0, 1]");
+    }
+  return 0;
+}
+// n_obs x (1 + in-neighbours) of every site: the most rows a target of the block-local analysis can have
+std::vector<int32_t> localRows(int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr) {
+  std::vector<int32_t> rows((size_t)nSites, nObs);
+  for (int64_t e = 0; e < ptr[nSites]; e++) {
+    int32_t& r = rows[(size_t)nbr[e]];
+    r = r > INT32_MAX - nObs ? INT32_MAX : r + nObs;
+  }
+  return rows;
+}
 
 }  // namespace
 
@@ -681,6 +951,8 @@ struct sipnet_enkf_local {
   LocalPair* d_pair = nullptr;
   int64_t* d_inPtr = nullptr;              // [n_sites + 1]: site t is a neighbour of the sites d_in[d_inPtr[t] ..)
   int32_t* d_in = nullptr;
+  double* d_inRho = nullptr;               // the tapers rho_ut in d_in's order
+  int32_t maxRows = 0;                     // the block-local analysis: the largest n_obs x (1 + in-neighbours) of a site
 };
 
 extern "C" {
@@ -764,6 +1036,7 @@ void sipnet_enkf_local_destroy(sipnet_enkf_local* L) {
   if (L->d_pair) (void)hipFree(L->d_pair);
   if (L->d_inPtr) (void)hipFree(L->d_inPtr);
   if (L->d_in) (void)hipFree(L->d_in);
+  if (L->d_inRho) (void)hipFree(L->d_inRho);
   delete L;
 }
 
@@ -803,9 +1076,14 @@ int sipnet_batch_enkf_local_create(sipnet_batch* b, int32_t n_obs, const int64_t
   for (int64_t e = 0; e < nbr_ptr[nSites]; e++) inPtr[(size_t)nbr[e] + 1]++;
   for (int32_t t = 0; t < nSites; t++) inPtr[t + 1] += inPtr[t];
   std::vector<int32_t> in((size_t)inPtr[nSites]);
+  std::vector<double> inRho(in.size());
   std::vector<int64_t> at(inPtr.begin(), inPtr.end() - 1);
   for (int32_t s = 0; s < nSites; s++)
-    for (int64_t e = nbr_ptr[s]; e < nbr_ptr[s + 1]; e++) in[(size_t)at[nbr[e]]++] = s;
+    for (int64_t e = nbr_ptr[s]; e < nbr_ptr[s + 1]; e++) {
+      inRho[(size_t)at[nbr[e]]] = rho[e];
+      in[(size_t)at[nbr[e]]++] = s;
+    }
+  const std::vector<int32_t> rows = localRows(nSites, n_obs, nbr_ptr, nbr);
 
   sipnet_enkf_local* L = new sipnet_enkf_local;
   L->b = b;
@@ -813,6 +1091,7 @@ int sipnet_batch_enkf_local_create(sipnet_batch* b, int32_t n_obs, const int64_t
   L->nSites = nSites;
   L->nObs = n_obs;
   L->nLevels = nLevels;
+  L->maxRows = *std::max_element(rows.begin(), rows.end());
   L->levelOff = std::move(levelOff);
   L->slotOff = std::move(slotOff);
   L->slotLen = std::move(slotLen);
@@ -823,7 +1102,8 @@ int sipnet_batch_enkf_local_create(sipnet_batch* b, int32_t n_obs, const int64_t
   };
   if ((rc = upload((void**)&L->d_pair, pairs.data(), pairs.size() * sizeof(LocalPair))) ||
       (rc = upload((void**)&L->d_inPtr, inPtr.data(), inPtr.size() * sizeof(int64_t))) ||
-      (rc = upload((void**)&L->d_in, in.data(), in.size() * sizeof(int32_t)))) {
+      (rc = upload((void**)&L->d_in, in.data(), in.size() * sizeof(int32_t))) ||
+      (rc = upload((void**)&L->d_inRho, inRho.data(), inRho.size() * sizeof(double)))) {
     sipnet_enkf_local_destroy(L);
     return rc;
   }
@@ -894,6 +1174,94 @@ int sipnet_batch_enkf_analysis_local(sipnet_batch* b, const sipnet_enkf_local* L
   HIP_TRY(hipGetLastError());
   b->pfInfo.fused = 0;
   b->pfInfo.grid = 0;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = ncol;
+  return markBusy(b, stream);
+}
+
+int sipnet_enkf_local_rows(int32_t n_sites, int32_t n_obs, const int64_t* nbr_ptr, const int32_t* nbr, int32_t* rows_of_site,
+                           int32_t* max_rows) {
+  int rc = localLists("sipnet_enkf_local_rows", n_sites, n_obs, nbr_ptr, nbr, nullptr, false);
+  if (rc) return rc;
+  const std::vector<int32_t> rows = localRows(n_sites, n_obs, nbr_ptr, nbr);
+  if (rows_of_site) std::copy(rows.begin(), rows.end(), rows_of_site);
+  if (max_rows) *max_rows = *std::max_element(rows.begin(), rows.end());
+  return SIPNET_OK;
+}
+
+int sipnet_batch_enkf_analysis_block(sipnet_batch* b, const sipnet_enkf_local* L, int32_t n_obs, const sipnet_enkf_obs* ops,
+                                     int32_t analysed_mask, const void* const d_planes[3], int32_t elem_is_f32,
+                                     int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
+                                     const double* d_inflation, int32_t* d_site_info, int32_t* d_rows, void* hip_stream) {
+  const char* name = "sipnet_batch_enkf_analysis_block";
+  auto bad = [name](const std::string& why) {
+    setError(std::string(name) + ": " + why);
+    return SIPNET_ERR_BAD_ARGUMENT;
+  };
+  if (!b || !L) return bad("a NULL batch or localization");
+  if (L->b != b) return bad("the localization belongs to another batch");
+  if (L->nObs != n_obs) return bad("the localization was made for n_obs = " + std::to_string(L->nObs));
+  if (b->n_members > kBlockMembers) return bad("at most 4096 members per site");
+  if (L->maxRows > kBlockRows)
+    return bad("a site has " + std::to_string(L->maxRows) + " rows (n_obs x (1 + in-neighbours)); at most " +
+               std::to_string(kBlockRows) + " (SIPNET_ENKF_BLOCK_MAX_ROWS, sipnet_enkf_local_rows)");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  EnkfArgs a;
+  int rc = enkfBegin(name, b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream, a);
+  if (rc) return rc;
+  const int64_t nSites = b->n_sites, ncol = b->ncol;
+  // the matrices of every target in LDS, where the staging tile was, when the largest fits beside the kernel's own LDS
+  const size_t matDoubles = blockMatSize(a.nA, L->maxRows), stageDoubles = (size_t)kTile * blockStagePitch(a.nA, L->maxRows);
+  int ldsMax = 0;
+  hipFuncAttributes attr;
+  HIP_TRY(hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, b->device));
+  const bool small = L->maxRows <= kBlockSmall && b->n_members <= 512;
+  const void* ldsKernel = small ? (const void*)enkfBlockKernel<true, 256> : (const void*)enkfBlockKernel<true, 1024>;
+  HIP_TRY(hipFuncGetAttributes(&attr, ldsKernel));
+  const size_t ldsWant = std::max(stageDoubles, matDoubles) * sizeof(double);
+  bool useLds = ldsWant + attr.sharedSizeBytes <= (size_t)ldsMax;
+  if (useLds && ldsWant > 48 * 1024 &&
+      hipFuncSetAttribute(ldsKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsWant) != hipSuccess) {
+    (void)hipGetLastError();
+    useLds = false;
+  }
+  // scratch: the per-chunk launches' layout (working copies | part | stat | the matrices | info, cnt, kept, site, src)
+  const size_t nWork = (size_t)a.nv * (size_t)ncol, nPart = (size_t)nSites * a.nCh * kMaxVars, nStat = (size_t)nSites * kStat;
+  const size_t nMat = useLds ? 0 : (size_t)nSites * matDoubles;
+  const size_t nInt = (size_t)nSites * 4 + 2 * (size_t)nSites * a.nCh + 3 * (size_t)nSites;
+  rc = enkfScratch(b, (nWork + nPart + nStat + nMat) * sizeof(double) + nInt * sizeof(int32_t));
+  if (rc) return rc;
+  a.work = (double*)b->d_enkf;
+  a.part = a.work + nWork;
+  a.stat = a.part + nPart;
+  double* mat = a.stat + nStat;
+  int32_t* ints = (int32_t*)(mat + nMat);
+  a.info = d_site_info ? d_site_info : ints;
+  a.cnt = ints + (size_t)nSites * 4;
+  a.kept = a.cnt + (size_t)nSites * a.nCh;
+  a.site = a.kept + (size_t)nSites * a.nCh;
+  a.src = a.site + 2 * (size_t)nSites;
+
+  const dim3 chunks((unsigned)nSites, (unsigned)a.nCh), sites((unsigned)nSites);
+  if (elem_is_f32) splitFront<float>(a, chunks, sites, stream);
+  else splitFront<double>(a, chunks, sites, stream);
+  hipLaunchKernelGGL(enkfReachKernel, dim3((unsigned)((nSites + 255) / 256)), dim3(256), 0, stream, a, L->d_inPtr, L->d_in,
+                     nSites);
+  if (d_inflation) splitInflation(a, chunks, sites, stream);
+  const size_t dyn = useLds ? ldsWant : stageDoubles * sizeof(double);
+  double* matArg = useLds ? nullptr : mat;
+  const int64_t matPitch = useLds ? 0 : (int64_t)matDoubles;
+  auto launch = [&](auto kernel, int threads) {
+    hipLaunchKernelGGL(kernel, sites, dim3(threads), dyn, stream, a, L->d_inPtr, L->d_in, L->d_inRho, matArg, matPitch,
+                       d_rows);
+  };
+  if (small) launch(useLds ? enkfBlockKernel<true, 256> : enkfBlockKernel<false, 256>, 256);
+  else launch(useLds ? enkfBlockKernel<true, 1024> : enkfBlockKernel<false, 1024>, 1024);
+  hipLaunchKernelGGL(enkfLimitKernel, chunks, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(enkfInfoKernel, sites, dim3(256), 0, stream, a);
+  HIP_TRY(hipGetLastError());
+  b->pfInfo.fused = useLds ? 1 : 0;
+  b->pfInfo.grid = (int32_t)nSites;
   b->pfInfo.budget = 0;
   b->pfInfo.nSlots = ncol;
   return markBusy(b, stream);

@@ -1,6 +1,7 @@
-"""Localization for the ensemble Kalman filter across the sites of one batch (sipnet_batch_enkf_analysis_local): the
-Gaspari-Cohn taper of the distances between sites, the host schedule of the observation slots, and the localization object
-Batch.enkf_localization returns."""
+"""Localization for the ensemble Kalman filters across the sites of one batch (sipnet_batch_enkf_analysis_local, the serial
+filter over the joint ensemble, and sipnet_batch_enkf_analysis_block, the block-local one): the Gaspari-Cohn taper of the
+distances between sites, the host schedule of the observation slots, the row counts of the block-local analysis, and the
+localization object Batch.enkf_localization returns."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +9,7 @@ import numpy as np
 from ._lib import check, lib
 
 EARTH_RADIUS_KM = 6371.0
+ENKF_BLOCK_MAX_ROWS = 128   # SIPNET_ENKF_BLOCK_MAX_ROWS
 
 
 def _csr(nbr_ptr, nbr, rho):
@@ -38,6 +40,19 @@ def enkf_local_schedule(nbr_ptr, nbr, rho, n_obs):
                                            C.c_void_p(level.ctypes.data) if level.size else None, C.byref(n_levels)),
           "enkf_local_schedule")
     return level, int(n_levels.value)
+
+
+def enkf_local_rows(nbr_ptr, nbr, n_obs):
+    """the row counts of sipnet_batch_enkf_analysis_block (sipnet_enkf_local_rows, host only) for n_sites = len(nbr_ptr) - 1
+    sites: n_obs x (1 + in-neighbours) of every site -> (rows [n_sites] int32, the largest).  The call refuses a batch whose
+    largest exceeds sa.ENKF_BLOCK_MAX_ROWS.  Raises SipnetError on a list the library refuses."""
+    ptr, idx, _ = _csr(nbr_ptr, nbr, np.zeros(np.asarray(nbr).size))
+    n_sites = ptr.size - 1
+    rows = np.zeros(max(n_sites, 0), dtype=np.int32)
+    most = C.c_int32(0)
+    check(lib().sipnet_enkf_local_rows(n_sites, int(n_obs), C.c_void_p(ptr.ctypes.data), _ptr(idx),
+                                       C.c_void_p(rows.ctypes.data) if rows.size else None, C.byref(most)), "enkf_local_rows")
+    return rows, int(most.value)
 
 
 def gaspari_cohn(lat_deg, lon_deg, half_width_km):
@@ -85,7 +100,8 @@ def taper(r):
 
 class EnkfLocalization:
     """a localization of one batch's sites (sipnet_enkf_local): made by Batch.enkf_localization, closed before its batch
-    (Batch.close does that).  n_levels: launches per analysis."""
+    (Batch.close does that).  n_levels: level launches per enkf_analysis_local; max_rows: the largest row count of a site
+    in enkf_analysis_block (sa.enkf_local_rows)."""
 
     def __init__(self, batch, nbr_ptr, nbr, rho, n_obs):
         self.h = None
@@ -98,6 +114,7 @@ class EnkfLocalization:
         check(self.L.sipnet_batch_enkf_local_create(batch.h, self.n_obs, C.c_void_p(ptr.ctypes.data), _ptr(idx), _ptr(w),
                                                     C.byref(h)), "enkf_localization")
         self.h = h
+        self.max_rows = enkf_local_rows(ptr, idx, self.n_obs)[1]
 
     @property
     def n_levels(self):
