@@ -395,10 +395,9 @@ class Batch:
         site is one member of a joint ensemble, and an observation moves the sites of its footprint, weighted by the
         localization's tapers.  local: enkf_localization(...) of this batch with n_obs = len(operators); the other
         arguments as enkf_analysis_sites."""
-        if getattr(local, "h", None) is None:
-            raise ValueError("enkf_analysis_local: the localization is closed")
+        loc = self._open_localization("enkf_analysis_local", local)
         args, keep = self._enkf_args("enkf_analysis_local", obs, sd, operators, analysed, planes, inflation, info_out)
-        check(self.L.sipnet_batch_enkf_analysis_local(self.h, local.h, *args, self._stream()), "enkf_analysis_local")
+        check(self.L.sipnet_batch_enkf_analysis_local(self.h, loc, *args, self._stream()), "enkf_analysis_local")
         del keep
 
     def enkf_analysis_block(self, local, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None,
@@ -409,17 +408,23 @@ class Batch:
         order across sites); pick this one for regional batches.  local: enkf_localization(...) of this batch with
         n_obs = len(operators) and max_rows <= sa.ENKF_BLOCK_MAX_ROWS; rows_out: int32 device tensor [n_sites][2] for
         {rows used, rows dropped}; the other arguments as enkf_analysis_sites."""
-        if getattr(local, "h", None) is None:
-            raise ValueError("enkf_analysis_block: the localization is closed")
+        loc = self._open_localization("enkf_analysis_block", local)
         t = self._torch
         if rows_out is not None and (rows_out.dtype != t.int32 or not rows_out.is_contiguous() or not rows_out.is_cuda
                                      or rows_out.numel() != 2 * self.n_sites):
             raise ValueError("enkf_analysis_block: rows_out must be a contiguous int32 device tensor of n_sites x 2")
         args, keep = self._enkf_args("enkf_analysis_block", obs, sd, operators, analysed, planes, inflation, info_out)
-        check(self.L.sipnet_batch_enkf_analysis_block(self.h, local.h, *args,
+        check(self.L.sipnet_batch_enkf_analysis_block(self.h, loc, *args,
                                                       C.c_void_p(rows_out.data_ptr()) if rows_out is not None else None,
                                                       self._stream()), "enkf_analysis_block")
         del keep
+
+    @staticmethod
+    def _open_localization(what, local):
+        """the handle of an EnkfLocalization that has not been closed"""
+        if getattr(local, "h", None) is None:
+            raise ValueError(f"{what}: the localization is closed")
+        return local.h
 
     def _enkf_args(self, what, obs, sd, operators, analysed, planes, inflation, info_out):
         """the EnKF analyses' arguments from n_obs to d_site_info, and the uploaded tensors they point into (keep them

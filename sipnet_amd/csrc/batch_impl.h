@@ -16,7 +16,7 @@
 namespace sipnet {
 void setError(const std::string& s);
 }
-using namespace sipnet;  // internal header: only engine.hip and pf.hip include it
+using namespace sipnet;  // internal header: only engine.hip, pf.hip and enkf.hip include it
 
 #define HIP_TRY(expr)                                                         \
   do {                                                                        \
@@ -188,7 +188,8 @@ struct sipnet_batch {
   // uploads that need a kernel (the parameter conversion) run on a stream of the batch's own: on the null stream
   // they would queue behind whatever another batch is running on a blocking stream
   hipStream_t upStream = nullptr;
-  // sipnet_batch_enkf_analysis_sites (enkf.hip): working copies, partial sums and site statistics, grow-only
+  // the three sipnet_batch_enkf_analysis_* calls (enkf.hip): their scratch block (working copies, partial sums, site
+  // statistics, the block-local matrices, counts and codes), grow-only
   void* d_enkf = nullptr;
   size_t enkfBytes = 0;
 };

@@ -1,4 +1,6 @@
-// enkf.hip -- sipnet_batch_enkf_analysis_sites: an ensemble Kalman filter analysis of the member pools, a filter per site.
+// enkf.hip -- the three ensemble Kalman filter analyses of the member pools: sipnet_batch_enkf_analysis_sites (a filter per
+// site), sipnet_batch_enkf_analysis_local (the localized serial filter across sites) and sipnet_batch_enkf_analysis_block (the
+// block-local filter: every site on its own, in one pass).
 //
 // Site s owns columns [s M, (s + 1) M).  Its live members' analysed pools and predicted observations are the analysis's
 // variables: working copies W[v][member], v < nA the analysed pools (in state-slot order), nA + i the h of operator i.
@@ -8,10 +10,14 @@
 // in segments of segLen(nCh) >= 16 consecutive chunks, each in order from 0.0; one segment is the site's total, several (at
 // most 64) are combined by one wave's xor-shuffle butterfly.  A site of the one-workgroup-per-site kernel has at most 16 chunks,
 // one segment: so that kernel and the per-chunk launches give the same bits.  No grid barrier, no spin, no atomic.
-// sipnet_batch_enkf_analysis_local (the localized analysis across sites) reuses the per-chunk launches around a launch per
-// level of its host schedule: one workgroup per (observation slot, target site), in the one-workgroup sum order.
-// sipnet_batch_enkf_analysis_block (the block-local analysis) reuses them around ONE launch, a workgroup per target site, that
-// runs the target's serial update on its small sample covariance (below).
+// The localized analysis reuses the per-chunk launches around a launch per level of its host schedule: one workgroup per
+// (observation slot, target site), in the one-workgroup sum order.  The block-local analysis reuses them around ONE launch, a
+// workgroup per target site, that runs the target's serial update on its small sample covariance (below).
+//
+// The host side: every entry point is its checks (localChecks for the two with a localization, then enkfBegin), the scratch
+// block (enkfScratch), the front of the per-chunk launches (enkfFront: load, codes, reach, inflation), a middle of its own, and
+// the tail (enkfEnd: limits, info, bookkeeping).  The per-site call may instead run its one-workgroup-per-site kernel between
+// scratch and tail.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -108,6 +114,16 @@ __device__ __forceinline__ double waveSum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+// the sum of an int over the workgroup's 256 threads (ints: any order), to every thread: every wave by an xor-shuffle
+// butterfly, the four wave totals through smI[4] (a second sum through the same smI needs a barrier first)
+__device__ __forceinline__ int blockSum(int* smI, int v) {
+  const int tid = (int)threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((tid & 63) == 0) smI[tid >> 6] = v;
+  __syncthreads();
+  return smI[0] + smI[1] + smI[2] + smI[3];
+}
 __device__ __forceinline__ double combine4(const double* smW, int q) {   // smW [4][kMaxVars]: the waves in order
   return ((smW[q] + smW[kMaxVars + q]) + smW[2 * kMaxVars + q]) + smW[3 * kMaxVars + q];
 }
@@ -182,12 +198,7 @@ __device__ void siteSums(GroupLds& g, int V, int nCh, F val) {
   __syncthreads();
 }
 __device__ int blockCount(GroupLds& g, int v) {
-  const int tid = (int)threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((tid & 63) == 0) g.smI[tid >> 6] = v;
-  __syncthreads();
-  const int n = g.smI[0] + g.smI[1] + g.smI[2] + g.smI[3];
+  const int n = blockSum(g.smI, v);
   __syncthreads();
   return n;
 }
@@ -278,14 +289,15 @@ __device__ __forceinline__ int splitCode(const EnkfArgs& a, int s) { return a.si
 // one workgroup per site: the sum of a site's per-chunk counts (ints: any order)
 __device__ int siteCount(const int32_t* v, int64_t nCh) {
   __shared__ int smI[4];
-  const int tid = (int)threadIdx.x;
   int c = 0;
-  for (int64_t k = tid; k < nCh; k += 256) c += v[k];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if ((tid & 63) == 0) smI[tid >> 6] = c;
-  __syncthreads();
-  return smI[0] + smI[1] + smI[2] + smI[3];
+  for (int64_t k = threadIdx.x; k < nCh; k += 256) c += v[k];
+  return blockSum(smI, c);
+}
+// stage i (i < 0: the inflation) leaves site s alone: not analysed, not inflated, or no observation i
+__device__ __forceinline__ bool stageSkipped(const EnkfArgs& a, int s, int i) {
+  if (splitCode(a, s) != kAnalysed) return true;
+  if (i < 0) return !(a.infl && a.infl[s] != 1.0);
+  return a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i];
 }
 
 template <typename T>
@@ -298,12 +310,8 @@ __global__ __launch_bounds__(256) void enkfLoadKernel(EnkfArgs a) {
     for (int q = 0; q < a.nA; q++) a.work[(int64_t)q * a.ncol + col] = a.state[(int64_t)a.pool[q] * a.ncol + col];
     for (int i = 0; i < a.nObs; i++) a.work[(int64_t)(a.nA + i) * a.ncol + col] = predicted<T>(a, i, col);
   }
-  int v = live ? 1 : 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((tid & 63) == 0) smI[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) a.cnt[(int64_t)s * a.nCh + blockIdx.y] = smI[0] + smI[1] + smI[2] + smI[3];
+  const int n = blockSum(smI, live ? 1 : 0);
+  if (tid == 0) a.cnt[(int64_t)s * a.nCh + blockIdx.y] = n;
 }
 
 // one workgroup per site, after the load: the live count and the site's code, once
@@ -325,9 +333,7 @@ __global__ __launch_bounds__(256) void enkfCodeKernel(EnkfArgs a) {
 __global__ __launch_bounds__(256) void enkfPartialKernel(EnkfArgs a, int i, int centred) {
   __shared__ double smW[4 * kMaxVars];
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x, c = (int)blockIdx.y;
-  if (splitCode(a, s) != kAnalysed) return;
-  if (i < 0 && !(a.infl && a.infl[s] != 1.0)) return;
-  if (i >= 0 && a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i]) return;
+  if (stageSkipped(a, s, i)) return;
   const int ii = i < 0 ? 0 : i, V = a.nv - ii;
   const int64_t j = (int64_t)c * 256 + tid, col = (int64_t)s * a.M + j;
   const bool live = liveAt(a, s, j);
@@ -350,9 +356,7 @@ __global__ __launch_bounds__(256) void enkfPartialKernel(EnkfArgs a, int i, int 
 // -> the means (centred = 0) or the gains (centred = 1)
 __global__ __launch_bounds__(256) void enkfFinalKernel(EnkfArgs a, int i, int centred) {
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
-  if (splitCode(a, s) != kAnalysed) return;
-  if (i < 0 && !(a.infl && a.infl[s] != 1.0)) return;
-  if (i >= 0 && a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i]) return;
+  if (stageSkipped(a, s, i)) return;
   __shared__ double tot[kMaxVars], seg[kMaxSegs][kMaxVars];
   const int ii = i < 0 ? 0 : i, V = a.nv - ii, n = a.site[2 * (int64_t)s + 1];
   const int L = segLen(a.nCh), nSeg = (a.nCh + L - 1) / L;
@@ -385,9 +389,7 @@ __global__ __launch_bounds__(256) void enkfFinalKernel(EnkfArgs a, int i, int ce
 // a chunk's members moved by observation i (i < 0: inflated)
 __global__ __launch_bounds__(256) void enkfUpdateKernel(EnkfArgs a, int i) {
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
-  if (splitCode(a, s) != kAnalysed) return;
-  if (i < 0 && !(a.infl && a.infl[s] != 1.0)) return;
-  if (i >= 0 && a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i]) return;
+  if (stageSkipped(a, s, i)) return;
   const int64_t j = (int64_t)blockIdx.y * 256 + tid, col = (int64_t)s * a.M + j;
   if (!liveAt(a, s, j)) return;
   const double* st = a.stat + (int64_t)s * kStat;
@@ -423,11 +425,8 @@ __global__ __launch_bounds__(256) void enkfLimitKernel(EnkfArgs a) {
       kept = 1;
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
-  if ((tid & 63) == 0) smI[tid >> 6] = kept;
-  __syncthreads();
-  if (tid == 0) a.kept[(int64_t)s * a.nCh + blockIdx.y] = smI[0] + smI[1] + smI[2] + smI[3];
+  kept = blockSum(smI, kept);
+  if (tid == 0) a.kept[(int64_t)s * a.nCh + blockIdx.y] = kept;
 }
 
 // one workgroup per site
@@ -764,6 +763,21 @@ __global__ __launch_bounds__(kBlockThreads) void enkfBlockKernel(EnkfArgs a, con
 
 }  // namespace
 
+// a localization: the level-ordered table of (slot, target) pairs and the in-neighbour lists, on the batch's device
+struct sipnet_enkf_local {
+  sipnet_batch* b = nullptr;
+  int32_t device = 0, nSites = 0, nObs = 0, nLevels = 0;
+  bool serial = false;                     // sipnet_debug_enkf_local_serial: one slot per launch, in serial order
+  std::vector<int64_t> levelOff;           // [nLevels + 1]: the pairs of level l are [levelOff[l], levelOff[l + 1])
+  std::vector<int64_t> slotOff;            // [n_sites][n_obs]: where slot (s, i)'s 1 + deg(s) pairs start
+  std::vector<int32_t> slotLen;
+  LocalPair* d_pair = nullptr;
+  int64_t* d_inPtr = nullptr;              // [n_sites + 1]: site t is a neighbour of the sites d_in[d_inPtr[t] ..)
+  int32_t* d_in = nullptr;
+  double* d_inRho = nullptr;               // the tapers rho_ut in d_in's order
+  int32_t maxRows = 0;                     // the block-local analysis: the largest n_obs x (1 + in-neighbours) of a site
+};
+
 void enkfRelease(sipnet_batch* b) {
   if (b->d_enkf) (void)hipFree(b->d_enkf);
   b->d_enkf = nullptr;
@@ -772,37 +786,39 @@ void enkfRelease(sipnet_batch* b) {
 
 namespace {
 
-// The checks and the arguments both analyses share, up to the scratch block: 0, or the error (the message names `name`).
+// a refusal: "`name`: `why`" is the thread's error
+int refuse(const char* name, const std::string& why) {
+  setError(std::string(name) + ": " + why);
+  return SIPNET_ERR_BAD_ARGUMENT;
+}
+
+// The checks and the arguments the three analyses share, up to the scratch block: 0, or the error (the message names `name`).
 // The synchronous form (no d_site_info) reads obs, sd and inflation back and refuses a bad site before anything is written.
 int enkfBegin(const char* name, sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
               const void* const d_planes[3], int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
               const double* d_inflation, int32_t* d_site_info, hipStream_t stream, EnkfArgs& a) {
   const int32_t allPools = (1 << kPools) - 1;
-  auto bad = [name](const std::string& why) {
-    setError(std::string(name) + ": " + why);
-    return SIPNET_ERR_BAD_ARGUMENT;
-  };
-  if (!b || !ops || !d_obs || !d_sd) return bad("a NULL batch, operators, observations or sds");
-  if (n_obs < 1 || n_obs > kMaxObs) return bad("n_obs must be 1..16");
-  if (analysed_mask == 0 || (analysed_mask & ~allPools)) return bad("analysed_mask must name pools 0..12");
+  if (!b || !ops || !d_obs || !d_sd) return refuse(name, "a NULL batch, operators, observations or sds");
+  if (n_obs < 1 || n_obs > kMaxObs) return refuse(name, "n_obs must be 1..16");
+  if (analysed_mask == 0 || (analysed_mask & ~allPools)) return refuse(name, "analysed_mask must name pools 0..12");
   bool planesUsed = false;
   for (int i = 0; i < n_obs; i++) {
     const sipnet_enkf_obs& o = ops[i];
     const std::string at = "operator " + std::to_string(i) + ": ";
-    if (o.param < -1 || o.param >= SIPNET_NPARAMS) return bad(at + "param is not a parameter index");
+    if (o.param < -1 || o.param >= SIPNET_NPARAMS) return refuse(name, at + "param is not a parameter index");
     if (o.kind == SIPNET_ENKF_POOLS) {
-      if (o.pool_mask == 0 || (o.pool_mask & ~allPools)) return bad(at + "pool_mask must name pools 0..12");
+      if (o.pool_mask == 0 || (o.pool_mask & ~allPools)) return refuse(name, at + "pool_mask must name pools 0..12");
     } else if (o.kind == SIPNET_ENKF_PLANE) {
-      if (o.plane < 0 || o.plane > 2) return bad(at + "plane must be 0 (NEE), 1 (GPP) or 2 (ET)");
-      if (!d_planes || !d_planes[o.plane]) return bad(at + "its plane pointer is NULL");
+      if (o.plane < 0 || o.plane > 2) return refuse(name, at + "plane must be 0 (NEE), 1 (GPP) or 2 (ET)");
+      if (!d_planes || !d_planes[o.plane]) return refuse(name, at + "its plane pointer is NULL");
       planesUsed = true;
     } else {
-      return bad(at + "unknown kind");
+      return refuse(name, at + "unknown kind");
     }
   }
-  if (planesUsed && (n_steps <= 0 || ld < b->ncol)) return bad("planes need n_steps > 0 and ld >= ncol");
-  if (b->ncol > (int64_t)1 << 22) return bad("at most 4194304 members");
-  if (b->pfPeers) return bad("this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
+  if (planesUsed && (n_steps <= 0 || ld < b->ncol)) return refuse(name, "planes need n_steps > 0 and ld >= ncol");
+  if (b->ncol > (int64_t)1 << 22) return refuse(name, "at most 4194304 members");
+  if (b->pfPeers) return refuse(name, "this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
   int rc = useDevice(b);
   if (rc) return rc;
   const int64_t nSites = b->n_sites, M = b->n_members, ncol = b->ncol;
@@ -815,8 +831,8 @@ int enkfBegin(const char* name, sipnet_batch* b, int32_t n_obs, const sipnet_enk
     for (int64_t s = 0; s < nSites; s++) {
       int used;
       if (siteInputs(obs.data(), sd.data(), d_inflation ? infl.data() : nullptr, n_obs, (int)s, &used) == kBadInput)
-        return bad("site " + std::to_string(s) + ": bad input (a finite obs needs a finite sd > 0; the inflation must be finite "
-                   "and >= 1); nothing was written");
+        return refuse(name, "site " + std::to_string(s) + ": bad input (a finite obs needs a finite sd > 0; the inflation must "
+                            "be finite and >= 1); nothing was written");
     }
   }
   b->pfPre.valid = false;
@@ -855,8 +871,22 @@ int enkfBegin(const char* name, sipnet_batch* b, int32_t n_obs, const sipnet_enk
   return 0;
 }
 
-// the batch's analysis scratch block, grown to at least `bytes`
-int enkfScratch(sipnet_batch* b, size_t bytes) {
+// The batch's scratch block sized, grown and carved, in this order: the working copies [nv][ncol] (workInGlobal: else they
+// live in LDS) | part [sites][chunks][kMaxVars] | stat [sites][kStat] | matPerSite doubles of matrices per site | info [sites][4]
+// (a.info is d_site_info where given) | cnt, kept [sites][chunks] | site [sites][2] | src [sites] (withSrc).  part, stat, cnt,
+// kept and site are the per-chunk launches' (perChunk: without them the regions are empty, and cnt, kept and site, which the
+// one-workgroup-per-site kernel never reads, all point at the end of info).  *mat, where asked for, gets the matrices' base.
+int enkfScratch(sipnet_batch* b, EnkfArgs& a, int32_t* d_site_info, bool workInGlobal, bool perChunk, bool withSrc,
+                size_t matPerSite, double** mat) {
+  const size_t nSites = (size_t)b->n_sites;
+  const size_t nWork = workInGlobal ? (size_t)a.nv * (size_t)b->ncol : 0;
+  const size_t nCnt = perChunk ? nSites * a.nCh : 0;
+  const size_t nPart = nCnt * kMaxVars;
+  const size_t nStat = perChunk ? nSites * kStat : 0;
+  const size_t nMat = nSites * matPerSite;
+  const size_t nSite = perChunk ? 2 * nSites : 0;
+  const size_t nInt = nSites * 4 + 2 * nCnt + nSite + (withSrc ? nSites : 0);
+  const size_t bytes = (nWork + nPart + nStat + nMat) * sizeof(double) + nInt * sizeof(int32_t);
   if (b->enkfBytes < bytes) {
     int rc = waitIdle(b);   // (the old block may still be read by a launch in flight)
     if (rc) return rc;
@@ -864,26 +894,78 @@ int enkfScratch(sipnet_batch* b, size_t bytes) {
     HIP_TRY(hipMalloc(&b->d_enkf, bytes));
     b->enkfBytes = bytes;
   }
+  a.work = (double*)b->d_enkf;
+  a.part = a.work + nWork;
+  a.stat = a.part + nPart;
+  double* matrices = a.stat + nStat;
+  int32_t* ints = (int32_t*)(matrices + nMat);
+  a.info = d_site_info ? d_site_info : ints;
+  a.cnt = ints + nSites * 4;
+  a.kept = a.cnt + nCnt;
+  a.site = a.kept + nCnt;
+  a.src = withSrc ? a.site + nSite : nullptr;
+  if (mat) *mat = matrices;
   return 0;
 }
 
-// the load, the codes and the inflation of the per-chunk launches (grid: sites x chunks, or sites)
-template <typename T>
-void splitFront(const EnkfArgs& a, dim3 chunks, dim3 sites, hipStream_t stream) {
-  hipLaunchKernelGGL(enkfLoadKernel<T>, chunks, dim3(256), 0, stream, a);
+// the grids of the per-chunk launches: sites x chunks of 256 members, and sites
+dim3 chunkGrid(const sipnet_batch* b, const EnkfArgs& a) { return dim3((unsigned)b->n_sites, (unsigned)a.nCh); }
+dim3 siteGrid(const sipnet_batch* b) { return dim3((unsigned)b->n_sites); }
+
+// the front of the per-chunk launches: the load (the planes' elements float or double), the codes, the sites that a
+// localization's sources reach (L), the inflation
+void enkfFront(const sipnet_batch* b, const EnkfArgs& a, int32_t elem_is_f32, const sipnet_enkf_local* L, hipStream_t stream) {
+  const dim3 chunks = chunkGrid(b, a), sites = siteGrid(b);
+  hipLaunchKernelGGL(elem_is_f32 ? enkfLoadKernel<float> : enkfLoadKernel<double>, chunks, dim3(256), 0, stream, a);
   hipLaunchKernelGGL(enkfCodeKernel, sites, dim3(256), 0, stream, a);
-}
-void splitInflation(const EnkfArgs& a, dim3 chunks, dim3 sites, hipStream_t stream) {
-  hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, -1, 0);
-  hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, -1, 0);
-  hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, -1);
+  if (L)
+    hipLaunchKernelGGL(enkfReachKernel, dim3((sites.x + 255) / 256), dim3(256), 0, stream, a, L->d_inPtr, L->d_in,
+                       (int64_t)b->n_sites);
+  if (a.infl) {
+    hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, -1, 0);
+    hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, -1, 0);
+    hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, -1);
+  }
 }
 
+// the tail of every analysis: the limits and the info of the per-chunk launches (perChunk: the one-workgroup-per-site kernel
+// has done its own), the launches' error, what sipnet_batch_pf_info reports, the batch busy on the stream
+int enkfEnd(sipnet_batch* b, const EnkfArgs& a, bool perChunk, int32_t fused, int32_t grid, hipStream_t stream) {
+  if (perChunk) {
+    hipLaunchKernelGGL(enkfLimitKernel, chunkGrid(b, a), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(enkfInfoKernel, siteGrid(b), dim3(256), 0, stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  b->pfInfo.fused = fused;
+  b->pfInfo.grid = grid;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = b->ncol;
+  return markBusy(b, stream);
+}
+
+// the checks of a localization's lists (withRho: and of its tapers)
+int localLists(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
+               bool withRho) {
+  if (nObs < 1 || nObs > kMaxObs) return refuse(name, "n_obs must be 1..16");
+  if (nSites < 1 || (int64_t)nSites * nObs > INT32_MAX) return refuse(name, "n_sites must be >= 1 (and n_sites x n_obs < 2^31)");
+  if (!ptr) return refuse(name, "a NULL nbr_ptr");
+  if (ptr[0] != 0) return refuse(name, "nbr_ptr[0] must be 0");
+  for (int32_t s = 0; s < nSites; s++)
+    if (ptr[s + 1] < ptr[s]) return refuse(name, "nbr_ptr must be non-decreasing (site " + std::to_string(s) + ")");
+  if (ptr[nSites] > 0 && (!nbr || (withRho && !rho))) return refuse(name, "a NULL nbr or rho with neighbours listed");
+  for (int32_t s = 0; s < nSites; s++)
+    for (int64_t k = ptr[s]; k < ptr[s + 1]; k++) {
+      const std::string at = "site " + std::to_string(s) + ", entry " + std::to_string(k - ptr[s]) + ": ";
+      if (nbr[k] < 0 || nbr[k] >= nSites) return refuse(name, at + "neighbour index out of range");
+      if (nbr[k] == s) return refuse(name, at + "a site is not its own neighbour");
+      if (k > ptr[s] && nbr[k] <= nbr[k - 1]) return refuse(name, at + "a row must be strictly ascending (no duplicates)");
+      if (withRho && !(rho[k] > 0.0 && rho[k] <= 1.0)) return refuse(name, at + "rho must be finite and in (0, 1]");
+    }
+  return 0;
+}
 // The localization's lists checked, and the greedy schedule of the slots (s, i) in serial order: level(s, i) = 1 + the last
 // level that touched a site of F(s) = {s} + nbr(s) (none: -1, so empty lists give level i).  Conflicting slots (footprints that
 // meet) are therefore in serial order, and the slots of one level have disjoint footprints.  level: [n_sites][n_obs].
-int localLists(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
-               bool withRho);
 int localSchedule(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
                   std::vector<int32_t>& level, int32_t* nLevels) {
   int rc = localLists(name, nSites, nObs, ptr, nbr, rho, true);
@@ -904,30 +986,6 @@ int localSchedule(const char* name, int32_t nSites, int32_t nObs, const int64_t*
   *nLevels = top + 1;
   return 0;
 }
-// the checks of a localization's lists (withRho: and of its tapers)
-int localLists(const char* name, int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr, const double* rho,
-               bool withRho) {
-  auto bad = [name](const std::string& why) {
-    setError(std::string(name) + ": " + why);
-    return SIPNET_ERR_BAD_ARGUMENT;
-  };
-  if (nObs < 1 || nObs > kMaxObs) return bad("n_obs must be 1..16");
-  if (nSites < 1 || (int64_t)nSites * nObs > INT32_MAX) return bad("n_sites must be >= 1 (and n_sites x n_obs < 2^31)");
-  if (!ptr) return bad("a NULL nbr_ptr");
-  if (ptr[0] != 0) return bad("nbr_ptr[0] must be 0");
-  for (int32_t s = 0; s < nSites; s++)
-    if (ptr[s + 1] < ptr[s]) return bad("nbr_ptr must be non-decreasing (site " + std::to_string(s) + ")");
-  if (ptr[nSites] > 0 && (!nbr || (withRho && !rho))) return bad("a NULL nbr or rho with neighbours listed");
-  for (int32_t s = 0; s < nSites; s++)
-    for (int64_t k = ptr[s]; k < ptr[s + 1]; k++) {
-      const std::string at = "site " + std::to_string(s) + ", entry " + std::to_string(k - ptr[s]) + ": ";
-      if (nbr[k] < 0 || nbr[k] >= nSites) return bad(at + "neighbour index out of range");
-      if (nbr[k] == s) return bad(at + "a site is not its own neighbour");
-      if (k > ptr[s] && nbr[k] <= nbr[k - 1]) return bad(at + "a row must be strictly ascending (no duplicates)");
-      if (withRho && !(rho[k] > 0.0 && rho[k] <= 1.0)) return bad(at + "rho must be finite and in (0, 1]");
-    }
-  return 0;
-}
 // n_obs x (1 + in-neighbours) of every site: the most rows a target of the block-local analysis can have
 std::vector<int32_t> localRows(int32_t nSites, int32_t nObs, const int64_t* ptr, const int32_t* nbr) {
   std::vector<int32_t> rows((size_t)nSites, nObs);
@@ -938,22 +996,16 @@ std::vector<int32_t> localRows(int32_t nSites, int32_t nObs, const int64_t* ptr,
   return rows;
 }
 
-}  // namespace
+// the checks the two analyses with a localization open with
+int localChecks(const char* name, const sipnet_batch* b, const sipnet_enkf_local* L, int32_t n_obs) {
+  if (!b || !L) return refuse(name, "a NULL batch or localization");
+  if (L->b != b) return refuse(name, "the localization belongs to another batch");
+  if (L->nObs != n_obs) return refuse(name, "the localization was made for n_obs = " + std::to_string(L->nObs));
+  if (b->n_members > 256 * kMaxGroupChunks) return refuse(name, "at most 4096 members per site");
+  return 0;
+}
 
-// a localization: the level-ordered table of (slot, target) pairs and the in-neighbour lists, on the batch's device
-struct sipnet_enkf_local {
-  sipnet_batch* b = nullptr;
-  int32_t device = 0, nSites = 0, nObs = 0, nLevels = 0;
-  bool serial = false;                     // sipnet_debug_enkf_local_serial: one slot per launch, in serial order
-  std::vector<int64_t> levelOff;           // [nLevels + 1]: the pairs of level l are [levelOff[l], levelOff[l + 1])
-  std::vector<int64_t> slotOff;            // [n_sites][n_obs]: where slot (s, i)'s 1 + deg(s) pairs start
-  std::vector<int32_t> slotLen;
-  LocalPair* d_pair = nullptr;
-  int64_t* d_inPtr = nullptr;              // [n_sites + 1]: site t is a neighbour of the sites d_in[d_inPtr[t] ..)
-  int32_t* d_in = nullptr;
-  double* d_inRho = nullptr;               // the tapers rho_ut in d_in's order
-  int32_t maxRows = 0;                     // the block-local analysis: the largest n_obs x (1 + in-neighbours) of a site
-};
+}  // namespace
 
 extern "C" {
 
@@ -966,7 +1018,7 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
   int rc = enkfBegin("sipnet_batch_enkf_analysis_sites", b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd,
                      d_inflation, d_site_info, stream, a);
   if (rc) return rc;
-  const int64_t nSites = b->n_sites, M = b->n_members, ncol = b->ncol;
+  const int64_t nSites = b->n_sites, M = b->n_members;
   // the per-chunk launches unless the sites outnumber the CUs four times over (profiles/r08_enkf_sites_time.txt: one
   // workgroup per site loses or ties at every shape up to 256 sites x 1 024 members -- 0.29 ms against 0.19); big sites or
   // SIPNET_KOPT_PF_MULTI_LAUNCH: always the launches
@@ -974,31 +1026,14 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
                      !(b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
   const size_t ldsBytes = (size_t)a.nv * (size_t)M * sizeof(double);
   a.useLds = group && ldsBytes <= (size_t)kLdsWork;
-  // scratch: working copies [nv][ncol] | part [sites][chunks][kMaxVars] | stat [sites][kStat] | info [sites][4],
-  // cnt, kept [sites][chunks], site [sites][2]
-  const size_t nWork = a.useLds ? 0 : (size_t)a.nv * (size_t)ncol;
-  const size_t nPart = group ? 0 : (size_t)nSites * a.nCh * kMaxVars, nStat = group ? 0 : (size_t)nSites * kStat;
-  const size_t nInt = (size_t)nSites * 4 + (group ? 0 : 2 * (size_t)nSites * a.nCh + 2 * (size_t)nSites);
-  rc = enkfScratch(b, (nWork + nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t));
+  rc = enkfScratch(b, a, d_site_info, /*workInGlobal=*/!a.useLds, /*perChunk=*/!group, /*withSrc=*/false, 0, nullptr);
   if (rc) return rc;
-  a.work = (double*)b->d_enkf;
-  a.part = a.work + nWork;
-  a.stat = a.part + nPart;
-  int32_t* ints = (int32_t*)(a.stat + nStat);
-  a.info = d_site_info ? d_site_info : ints;
-  a.cnt = ints + (size_t)nSites * 4;
-  a.kept = a.cnt + (size_t)nSites * a.nCh;
-  a.site = a.kept + (size_t)nSites * a.nCh;
-
   if (group) {
-    const size_t dyn = a.useLds ? ldsBytes : 0;
-    if (elem_is_f32) hipLaunchKernelGGL(enkfSiteKernel<float>, dim3((unsigned)nSites), dim3(256), dyn, stream, a);
-    else hipLaunchKernelGGL(enkfSiteKernel<double>, dim3((unsigned)nSites), dim3(256), dyn, stream, a);
+    hipLaunchKernelGGL(elem_is_f32 ? enkfSiteKernel<float> : enkfSiteKernel<double>, siteGrid(b), dim3(256),
+                       a.useLds ? ldsBytes : 0, stream, a);
   } else {
-    const dim3 chunks((unsigned)nSites, (unsigned)a.nCh), sites((unsigned)nSites);
-    if (elem_is_f32) splitFront<float>(a, chunks, sites, stream);
-    else splitFront<double>(a, chunks, sites, stream);
-    if (d_inflation) splitInflation(a, chunks, sites, stream);
+    const dim3 chunks = chunkGrid(b, a), sites = siteGrid(b);
+    enkfFront(b, a, elem_is_f32, nullptr, stream);
     for (int i = 0; i < n_obs; i++) {
       hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, i, 0);
       hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, i, 0);
@@ -1006,23 +1041,13 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
       hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, i, 1);
       hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, i);
     }
-    hipLaunchKernelGGL(enkfLimitKernel, chunks, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(enkfInfoKernel, sites, dim3(256), 0, stream, a);
   }
-  HIP_TRY(hipGetLastError());
-  b->pfInfo.fused = group ? 1 : 0;
-  b->pfInfo.grid = group ? (int32_t)nSites : 0;
-  b->pfInfo.budget = 0;
-  b->pfInfo.nSlots = ncol;
-  return markBusy(b, stream);
+  return enkfEnd(b, a, /*perChunk=*/!group, group ? 1 : 0, group ? (int32_t)b->n_sites : 0, stream);
 }
 
 int sipnet_enkf_local_schedule(int32_t n_sites, int32_t n_obs, const int64_t* nbr_ptr, const int32_t* nbr, const double* rho,
                                int32_t* level_of_slot, int32_t* n_levels) {
-  if (!n_levels) {
-    setError("sipnet_enkf_local_schedule: a NULL n_levels");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!n_levels) return refuse("sipnet_enkf_local_schedule", "a NULL n_levels");
   std::vector<int32_t> level;
   int rc = localSchedule("sipnet_enkf_local_schedule", n_sites, n_obs, nbr_ptr, nbr, rho, level, n_levels);
   if (rc) return rc;
@@ -1043,10 +1068,7 @@ void sipnet_enkf_local_destroy(sipnet_enkf_local* L) {
 int sipnet_batch_enkf_local_create(sipnet_batch* b, int32_t n_obs, const int64_t* nbr_ptr, const int32_t* nbr,
                                    const double* rho, sipnet_enkf_local** out) {
   const char* name = "sipnet_batch_enkf_local_create";
-  if (!b || !out) {
-    setError(std::string(name) + ": a NULL batch or out");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !out) return refuse(name, "a NULL batch or out");
   *out = nullptr;
   std::vector<int32_t> level;
   int32_t nLevels = 0;
@@ -1114,10 +1136,7 @@ int sipnet_batch_enkf_local_create(sipnet_batch* b, int32_t n_obs, const int64_t
 int32_t sipnet_enkf_local_levels(const sipnet_enkf_local* L) { return L ? L->nLevels : 0; }
 
 int sipnet_debug_enkf_local_serial(sipnet_enkf_local* L, int32_t on) {
-  if (!L) {
-    setError("sipnet_debug_enkf_local_serial: a NULL localization");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!L) return refuse("sipnet_debug_enkf_local_serial", "a NULL localization");
   L->serial = on != 0;
   return SIPNET_OK;
 }
@@ -1127,40 +1146,15 @@ int sipnet_batch_enkf_analysis_local(sipnet_batch* b, const sipnet_enkf_local* L
                                      int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
                                      const double* d_inflation, int32_t* d_site_info, void* hip_stream) {
   const char* name = "sipnet_batch_enkf_analysis_local";
-  auto bad = [name](const std::string& why) {
-    setError(std::string(name) + ": " + why);
-    return SIPNET_ERR_BAD_ARGUMENT;
-  };
-  if (!b || !L) return bad("a NULL batch or localization");
-  if (L->b != b) return bad("the localization belongs to another batch");
-  if (L->nObs != n_obs) return bad("the localization was made for n_obs = " + std::to_string(L->nObs));
-  if (b->n_members > 256 * kMaxGroupChunks) return bad("at most 4096 members per site");
+  int rc = localChecks(name, b, L, n_obs);
+  if (rc) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   EnkfArgs a;
-  int rc = enkfBegin(name, b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream, a);
+  rc = enkfBegin(name, b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream, a);
   if (rc) return rc;
-  const int64_t nSites = b->n_sites, ncol = b->ncol;
-  // scratch: the per-chunk launches' layout (working copies | part | stat | info, cnt, kept, site), then src [sites]
-  const size_t nWork = (size_t)a.nv * (size_t)ncol, nPart = (size_t)nSites * a.nCh * kMaxVars, nStat = (size_t)nSites * kStat;
-  const size_t nInt = (size_t)nSites * 4 + 2 * (size_t)nSites * a.nCh + 3 * (size_t)nSites;
-  rc = enkfScratch(b, (nWork + nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t));
+  rc = enkfScratch(b, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/true, 0, nullptr);
   if (rc) return rc;
-  a.work = (double*)b->d_enkf;
-  a.part = a.work + nWork;
-  a.stat = a.part + nPart;
-  int32_t* ints = (int32_t*)(a.stat + nStat);
-  a.info = d_site_info ? d_site_info : ints;
-  a.cnt = ints + (size_t)nSites * 4;
-  a.kept = a.cnt + (size_t)nSites * a.nCh;
-  a.site = a.kept + (size_t)nSites * a.nCh;
-  a.src = a.site + 2 * (size_t)nSites;
-
-  const dim3 chunks((unsigned)nSites, (unsigned)a.nCh), sites((unsigned)nSites);
-  if (elem_is_f32) splitFront<float>(a, chunks, sites, stream);
-  else splitFront<double>(a, chunks, sites, stream);
-  hipLaunchKernelGGL(enkfReachKernel, dim3((unsigned)((nSites + 255) / 256)), dim3(256), 0, stream, a, L->d_inPtr, L->d_in,
-                     nSites);
-  if (d_inflation) splitInflation(a, chunks, sites, stream);
+  enkfFront(b, a, elem_is_f32, L, stream);
   if (L->serial) {
     for (size_t k = 0; k < L->slotOff.size(); k++)
       hipLaunchKernelGGL(enkfLocalKernel, dim3((unsigned)L->slotLen[k]), dim3(256), 0, stream, a, L->d_pair, L->slotOff[k]);
@@ -1169,14 +1163,7 @@ int sipnet_batch_enkf_analysis_local(sipnet_batch* b, const sipnet_enkf_local* L
       hipLaunchKernelGGL(enkfLocalKernel, dim3((unsigned)(L->levelOff[l + 1] - L->levelOff[l])), dim3(256), 0, stream, a,
                          L->d_pair, L->levelOff[l]);
   }
-  hipLaunchKernelGGL(enkfLimitKernel, chunks, dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(enkfInfoKernel, sites, dim3(256), 0, stream, a);
-  HIP_TRY(hipGetLastError());
-  b->pfInfo.fused = 0;
-  b->pfInfo.grid = 0;
-  b->pfInfo.budget = 0;
-  b->pfInfo.nSlots = ncol;
-  return markBusy(b, stream);
+  return enkfEnd(b, a, /*perChunk=*/true, 0, 0, stream);
 }
 
 int sipnet_enkf_local_rows(int32_t n_sites, int32_t n_obs, const int64_t* nbr_ptr, const int32_t* nbr, int32_t* rows_of_site,
@@ -1194,22 +1181,15 @@ int sipnet_batch_enkf_analysis_block(sipnet_batch* b, const sipnet_enkf_local* L
                                      int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
                                      const double* d_inflation, int32_t* d_site_info, int32_t* d_rows, void* hip_stream) {
   const char* name = "sipnet_batch_enkf_analysis_block";
-  auto bad = [name](const std::string& why) {
-    setError(std::string(name) + ": " + why);
-    return SIPNET_ERR_BAD_ARGUMENT;
-  };
-  if (!b || !L) return bad("a NULL batch or localization");
-  if (L->b != b) return bad("the localization belongs to another batch");
-  if (L->nObs != n_obs) return bad("the localization was made for n_obs = " + std::to_string(L->nObs));
-  if (b->n_members > kBlockMembers) return bad("at most 4096 members per site");
+  int rc = localChecks(name, b, L, n_obs);
+  if (rc) return rc;
   if (L->maxRows > kBlockRows)
-    return bad("a site has " + std::to_string(L->maxRows) + " rows (n_obs x (1 + in-neighbours)); at most " +
-               std::to_string(kBlockRows) + " (SIPNET_ENKF_BLOCK_MAX_ROWS, sipnet_enkf_local_rows)");
+    return refuse(name, "a site has " + std::to_string(L->maxRows) + " rows (n_obs x (1 + in-neighbours)); at most " +
+                            std::to_string(kBlockRows) + " (SIPNET_ENKF_BLOCK_MAX_ROWS, sipnet_enkf_local_rows)");
   hipStream_t stream = (hipStream_t)hip_stream;
   EnkfArgs a;
-  int rc = enkfBegin(name, b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream, a);
+  rc = enkfBegin(name, b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream, a);
   if (rc) return rc;
-  const int64_t nSites = b->n_sites, ncol = b->ncol;
   // the matrices of every target in LDS, where the staging tile was, when the largest fits beside the kernel's own LDS
   const size_t matDoubles = blockMatSize(a.nA, L->maxRows), stageDoubles = (size_t)kTile * blockStagePitch(a.nA, L->maxRows);
   int ldsMax = 0;
@@ -1225,46 +1205,21 @@ int sipnet_batch_enkf_analysis_block(sipnet_batch* b, const sipnet_enkf_local* L
     (void)hipGetLastError();
     useLds = false;
   }
-  // scratch: the per-chunk launches' layout (working copies | part | stat | the matrices | info, cnt, kept, site, src)
-  const size_t nWork = (size_t)a.nv * (size_t)ncol, nPart = (size_t)nSites * a.nCh * kMaxVars, nStat = (size_t)nSites * kStat;
-  const size_t nMat = useLds ? 0 : (size_t)nSites * matDoubles;
-  const size_t nInt = (size_t)nSites * 4 + 2 * (size_t)nSites * a.nCh + 3 * (size_t)nSites;
-  rc = enkfScratch(b, (nWork + nPart + nStat + nMat) * sizeof(double) + nInt * sizeof(int32_t));
+  double* mat = nullptr;   // (a target's matrices in its block of the scratch, unless they are in LDS)
+  rc = enkfScratch(b, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/true, useLds ? 0 : matDoubles,
+                   &mat);
   if (rc) return rc;
-  a.work = (double*)b->d_enkf;
-  a.part = a.work + nWork;
-  a.stat = a.part + nPart;
-  double* mat = a.stat + nStat;
-  int32_t* ints = (int32_t*)(mat + nMat);
-  a.info = d_site_info ? d_site_info : ints;
-  a.cnt = ints + (size_t)nSites * 4;
-  a.kept = a.cnt + (size_t)nSites * a.nCh;
-  a.site = a.kept + (size_t)nSites * a.nCh;
-  a.src = a.site + 2 * (size_t)nSites;
-
-  const dim3 chunks((unsigned)nSites, (unsigned)a.nCh), sites((unsigned)nSites);
-  if (elem_is_f32) splitFront<float>(a, chunks, sites, stream);
-  else splitFront<double>(a, chunks, sites, stream);
-  hipLaunchKernelGGL(enkfReachKernel, dim3((unsigned)((nSites + 255) / 256)), dim3(256), 0, stream, a, L->d_inPtr, L->d_in,
-                     nSites);
-  if (d_inflation) splitInflation(a, chunks, sites, stream);
+  enkfFront(b, a, elem_is_f32, L, stream);
   const size_t dyn = useLds ? ldsWant : stageDoubles * sizeof(double);
   double* matArg = useLds ? nullptr : mat;
   const int64_t matPitch = useLds ? 0 : (int64_t)matDoubles;
   auto launch = [&](auto kernel, int threads) {
-    hipLaunchKernelGGL(kernel, sites, dim3(threads), dyn, stream, a, L->d_inPtr, L->d_in, L->d_inRho, matArg, matPitch,
+    hipLaunchKernelGGL(kernel, siteGrid(b), dim3(threads), dyn, stream, a, L->d_inPtr, L->d_in, L->d_inRho, matArg, matPitch,
                        d_rows);
   };
   if (small) launch(useLds ? enkfBlockKernel<true, 256> : enkfBlockKernel<false, 256>, 256);
   else launch(useLds ? enkfBlockKernel<true, 1024> : enkfBlockKernel<false, 1024>, 1024);
-  hipLaunchKernelGGL(enkfLimitKernel, chunks, dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(enkfInfoKernel, sites, dim3(256), 0, stream, a);
-  HIP_TRY(hipGetLastError());
-  b->pfInfo.fused = useLds ? 1 : 0;
-  b->pfInfo.grid = (int32_t)nSites;
-  b->pfInfo.budget = 0;
-  b->pfInfo.nSlots = ncol;
-  return markBusy(b, stream);
+  return enkfEnd(b, a, /*perChunk=*/true, useLds ? 1 : 0, (int32_t)b->n_sites, stream);
 }
 
 }  // extern "C"

@@ -3,10 +3,8 @@ reference (tests/enkf_block_reference.py) on a grid of sites with Gaspari-Cohn t
 are and are not multiples of 256, with the small matrices in LDS and in global memory; empty lists against
 sipnet_batch_enkf_analysis_sites and the complete graph with rho = 1 against sipnet_batch_enkf_analysis_local; repeatable, and
 independent of sites out of reach; dropped rows, untouched sites, the row cap, the refusals; a forecast that continues from the
-analysis.  The forecasts are built as tests/test_gpu_enkf_local.py builds them (its helpers are copied here)."""
+analysis.  The forecasts, observations and lists come from tests/enkf_gpu_common.py."""
 import ctypes as C
-import functools
-import os
 
 import numpy as np
 import pytest
@@ -16,113 +14,15 @@ import sipnet_amd as sa
 from sipnet_amd import _lib, synth
 from sipnet_amd.config import param_index as pi
 from tests import enkf_block_reference as br
-from tests import enkf_reference as er
-from tests import helpers
+from tests.enkf_gpu_common import (ANALYSED, BASE, DEV, OTHER, SLOTS, bits, carried_params, empty, forecast, grid, observe,
+                                   op_tuples, operators, sites_batch, within)
 
 pytestmark = pytest.mark.gpu
-BASE = os.path.join(helpers.REPO, "sipnet_amd", "data", "base_forest.param")
-DEV = "cuda"
-ANALYSED = ["plantWoodC", "plantLeafC", "soilC", "soilWater", "coarseRootC", "fineRootC", "plantCAccountingDelta"]
-SLOTS = [sa.POOLS.index(p) for p in ANALYSED]
-OTHER = [k for k in range(32) if k not in SLOTS]
 
 
 @pytest.fixture(scope="module")
 def base():
     return sa.read_params(BASE, sa.flags_from())[0]
-
-
-@functools.lru_cache(maxsize=None)
-def site_clim(s):
-    """every site its own forcing"""
-    return synth.convert_raw(synth.round_like_file(synth.half_hourly_year_raw(48 * 8, site=s)))
-
-
-def operators():
-    """LAI, above-ground wood, soil wetness, the NEE sum"""
-    return [sa.enkf_pools(["plantLeafC"], divide_by="leafCSpWt"),
-            sa.enkf_pools(["plantWoodC", "plantCAccountingDelta"]),
-            sa.enkf_pools(["soilWater"], divide_by="soilWHC"),
-            sa.enkf_plane("nee")]
-
-
-def op_tuples(ops):
-    return [(o.kind, o.pool_mask, o.plane, o.param, o.scale) for o in ops]
-
-
-def sites_batch(members, n_sites, prec, clim=site_clim):
-    M = members.shape[0] // n_sites
-    b = sa.Batch(sa.flags_from(), n_sites, M, prec, fast_math=True)
-    for s in range(n_sites):
-        b.set_climate(s, clim(s))
-        b.set_params(s, members[s * M:(s + 1) * M])
-    b.setup()
-    return b
-
-
-def carried_params(b):
-    w = 32 + (125 if b.precision == sa.F32_MIXED else 250)
-    idx = torch.arange(b.ncol, dtype=torch.int32, device=DEV)
-    return b.pack_members(idx, True)[w:].cpu().numpy().T        # [ncol][NPARAMS]
-
-
-def observe(state, planes, prm, n_sites, ops, rng, nan_sites=(), nan_obs=()):
-    """per site and operator: an observation near the live ensemble's mean, sd ~ the ensemble's spread"""
-    M = state.shape[0] // n_sites
-    obs = np.zeros((n_sites, len(ops)))
-    sd = np.zeros_like(obs)
-    for s in range(n_sites):
-        cols = np.arange(s * M, (s + 1) * M)
-        live = cols[state[cols, 29] == 0]
-        for i, op in enumerate(op_tuples(ops)):
-            h = er.predicted(op, state[live, :13], [p[:, live] for p in planes], lambda k: prm[live, k]) if len(live) else [0.0]
-            spread = float(np.std(h)) + 1e-3 * (abs(float(np.mean(h))) + 1e-3)
-            obs[s, i] = float(np.mean(h)) + spread * rng.normal()
-            sd[s, i] = spread * (0.5, 1.0, 2.0)[(s + i) % 3]
-    for s in nan_sites:
-        obs[s] = np.nan
-    for s, i in nan_obs:
-        obs[s, i] = np.nan
-    return obs, sd
-
-
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint64)
-
-
-def within(got, want, fc, n_sites, slots=SLOTS):
-    """|got - want| <= 1e-10 max(|x|, the site's ensemble sd) per analysed pool; the largest ratio is printed first"""
-    M = got.shape[0] // n_sites
-    worst = 0.0
-    for s in range(n_sites):
-        sl = slice(s * M, (s + 1) * M)
-        scale = np.maximum(np.abs(want[sl][:, slots]), fc[sl][:, slots].std(0) + 1e-300)
-        worst = max(worst, float((np.abs(got[sl][:, slots] - want[sl][:, slots]) / scale).max()))
-    print(f"largest |got - want| / max(|x|, site ensemble sd) over {n_sites} sites: {worst:.3e} (bound 1e-10)")
-    for s in range(n_sites):
-        sl = slice(s * M, (s + 1) * M)
-        scale = np.maximum(np.abs(want[sl][:, slots]), fc[sl][:, slots].std(0) + 1e-300)
-        assert (np.abs(got[sl][:, slots] - want[sl][:, slots]) <= 1e-10 * scale).all(), s
-
-
-def forecast(base, n_sites, M, prec, steps=96, seed=1, of=None):
-    """of: the members are the first n_sites * M of a batch of `of` sites (the same forecast, site for site)"""
-    members = synth.perturbed_params(base, (of or n_sites) * M, seed=seed)[:n_sites * M]
-    b = sites_batch(members, n_sites, prec)
-    planes, _ = b.run(0, steps)
-    return b, planes
-
-
-def grid(n_sites, far=()):
-    """sites on a 0.5 degree grid 8 wide; `far` sites moved 20 degrees north, out of everyone's reach"""
-    r, c = np.divmod(np.arange(n_sites), 8)
-    lat = 45.0 + 0.5 * r
-    lat[list(far)] += 20.0
-    return lat, -85.0 + 0.5 * c
-
-
-def empty(n_sites):
-    return np.zeros(n_sites + 1, dtype=np.int64), np.zeros(0, np.int32), np.zeros(0)
 
 
 def complete(n_sites, rho=1.0, of=None):

@@ -2,10 +2,8 @@
 against the numpy reference (tests/enkf_local_reference.py) on a grid of sites with Gaspari-Cohn tapers; empty lists bit for
 bit equal to sipnet_batch_enkf_analysis_sites; the levelled schedule bit for bit equal to one slot per launch, and repeatable;
 reached and unreached sites, dead members, bad input; the refusals; a forecast that continues from the analysis like one from
-set_state.  The forecasts are built as tests/test_gpu_enkf_sites.py builds them (its helpers are copied here)."""
+set_state.  The forecasts, observations and lists come from tests/enkf_gpu_common.py."""
 import ctypes as C
-import functools
-import os
 
 import numpy as np
 import pytest
@@ -15,106 +13,15 @@ import sipnet_amd as sa
 from sipnet_amd import _lib, synth
 from sipnet_amd.config import param_index as pi
 from tests import enkf_local_reference as lr
-from tests import enkf_reference as er
-from tests import helpers
+from tests.enkf_gpu_common import (ANALYSED, BASE, DEV, OTHER, SLOTS, bits, carried_params, empty, forecast, grid, observe,
+                                   op_tuples, operators, sites_batch, within)
 
 pytestmark = pytest.mark.gpu
-BASE = os.path.join(helpers.REPO, "sipnet_amd", "data", "base_forest.param")
-DEV = "cuda"
-ANALYSED = ["plantWoodC", "plantLeafC", "soilC", "soilWater", "coarseRootC", "fineRootC", "plantCAccountingDelta"]
-SLOTS = [sa.POOLS.index(p) for p in ANALYSED]
-OTHER = [k for k in range(32) if k not in SLOTS]
 
 
 @pytest.fixture(scope="module")
 def base():
     return sa.read_params(BASE, sa.flags_from())[0]
-
-
-@functools.lru_cache(maxsize=None)
-def site_clim(s):
-    """every site its own forcing"""
-    return synth.convert_raw(synth.round_like_file(synth.half_hourly_year_raw(48 * 8, site=s)))
-
-
-def operators():
-    """LAI, above-ground wood, soil wetness, the NEE sum"""
-    return [sa.enkf_pools(["plantLeafC"], divide_by="leafCSpWt"),
-            sa.enkf_pools(["plantWoodC", "plantCAccountingDelta"]),
-            sa.enkf_pools(["soilWater"], divide_by="soilWHC"),
-            sa.enkf_plane("nee")]
-
-
-def op_tuples(ops):
-    return [(o.kind, o.pool_mask, o.plane, o.param, o.scale) for o in ops]
-
-
-def sites_batch(members, n_sites, prec, clim=site_clim):
-    M = members.shape[0] // n_sites
-    b = sa.Batch(sa.flags_from(), n_sites, M, prec, fast_math=True)
-    for s in range(n_sites):
-        b.set_climate(s, clim(s))
-        b.set_params(s, members[s * M:(s + 1) * M])
-    b.setup()
-    return b
-
-
-def carried_params(b):
-    w = 32 + (125 if b.precision == sa.F32_MIXED else 250)
-    idx = torch.arange(b.ncol, dtype=torch.int32, device=DEV)
-    return b.pack_members(idx, True)[w:].cpu().numpy().T        # [ncol][NPARAMS]
-
-
-def observe(state, planes, prm, n_sites, ops, rng, nan_sites=(), nan_obs=()):
-    """per site and operator: an observation near the live ensemble's mean, sd ~ the ensemble's spread"""
-    M = state.shape[0] // n_sites
-    obs = np.zeros((n_sites, len(ops)))
-    sd = np.zeros_like(obs)
-    for s in range(n_sites):
-        cols = np.arange(s * M, (s + 1) * M)
-        live = cols[state[cols, 29] == 0]
-        for i, op in enumerate(op_tuples(ops)):
-            h = er.predicted(op, state[live, :13], [p[:, live] for p in planes], lambda k: prm[live, k]) if len(live) else [0.0]
-            spread = float(np.std(h)) + 1e-3 * (abs(float(np.mean(h))) + 1e-3)
-            obs[s, i] = float(np.mean(h)) + spread * rng.normal()
-            sd[s, i] = spread * (0.5, 1.0, 2.0)[(s + i) % 3]
-    for s in nan_sites:
-        obs[s] = np.nan
-    for s, i in nan_obs:
-        obs[s, i] = np.nan
-    return obs, sd
-
-
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint64)
-
-
-def within(got, want, fc, n_sites):
-    """|got - want| <= 1e-10 max(|x|, the site's ensemble sd) per analysed pool"""
-    M = got.shape[0] // n_sites
-    for s in range(n_sites):
-        sl = slice(s * M, (s + 1) * M)
-        scale = np.maximum(np.abs(want[sl][:, SLOTS]), fc[sl][:, SLOTS].std(0) + 1e-300)
-        assert (np.abs(got[sl][:, SLOTS] - want[sl][:, SLOTS]) <= 1e-10 * scale).all(), s
-
-
-def forecast(base, n_sites, M, prec, steps=96, seed=1):
-    members = synth.perturbed_params(base, n_sites * M, seed=seed)
-    b = sites_batch(members, n_sites, prec)
-    planes, _ = b.run(0, steps)
-    return b, planes
-
-
-def grid(n_sites, far=()):
-    """sites on a 0.5 degree grid 8 wide; `far` sites moved 20 degrees north, out of everyone's reach"""
-    r, c = np.divmod(np.arange(n_sites), 8)
-    lat = 45.0 + 0.5 * r
-    lat[list(far)] += 20.0
-    return lat, -85.0 + 0.5 * c
-
-
-def empty(n_sites):
-    return np.zeros(n_sites + 1, dtype=np.int64), np.zeros(0, np.int32), np.zeros(0)
 
 
 @pytest.mark.parametrize("prec", [sa.F64, sa.F32_MIXED], ids=["f64", "f32"])

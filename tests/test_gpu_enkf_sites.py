@@ -4,8 +4,6 @@ touched; a forecast that continues from the analysis like one from set_state; th
 per-chunk launches bit for bit; the limits, dead members, the biomass rule, parameters behind a resampled index; the
 refusals."""
 import ctypes as C
-import functools
-import os
 
 import numpy as np
 import pytest
@@ -15,13 +13,10 @@ import sipnet_amd as sa
 from sipnet_amd import _lib, synth
 from sipnet_amd.config import param_index as pi
 from tests import enkf_reference as er
-from tests import helpers
+from tests.enkf_gpu_common import (ANALYSED, BASE, DEV, SLOTS, bits, carried_params, forecast, observe, op_tuples, operators,
+                                   site_clim, sites_batch, within)
 
 pytestmark = pytest.mark.gpu
-BASE = os.path.join(helpers.REPO, "sipnet_amd", "data", "base_forest.param")
-DEV = "cuda"
-ANALYSED = ["plantWoodC", "plantLeafC", "soilC", "soilWater", "coarseRootC", "fineRootC", "plantCAccountingDelta"]
-SLOTS = [sa.POOLS.index(p) for p in ANALYSED]
 
 
 @pytest.fixture(scope="module")
@@ -29,87 +24,11 @@ def base():
     return sa.read_params(BASE, sa.flags_from())[0]
 
 
-@functools.lru_cache(maxsize=None)
-def site_clim(s):
-    """every site its own forcing"""
-    return synth.convert_raw(synth.round_like_file(synth.half_hourly_year_raw(48 * 8, site=s)))
-
-
-def operators():
-    """LAI, above-ground wood, soil wetness, the NEE sum"""
-    return [sa.enkf_pools(["plantLeafC"], divide_by="leafCSpWt"),
-            sa.enkf_pools(["plantWoodC", "plantCAccountingDelta"]),
-            sa.enkf_pools(["soilWater"], divide_by="soilWHC"),
-            sa.enkf_plane("nee")]
-
-
-def op_tuples(ops):
-    return [(o.kind, o.pool_mask, o.plane, o.param, o.scale) for o in ops]
-
-
-def sites_batch(members, n_sites, prec, clim=site_clim, events=None):
-    M = members.shape[0] // n_sites
-    b = sa.Batch(sa.flags_from(), n_sites, M, prec, fast_math=True)
-    for s in range(n_sites):
-        b.set_climate(s, clim(s))
-        if events is not None:
-            b.set_events(s, events)
-        b.set_params(s, members[s * M:(s + 1) * M])
-    b.setup()
-    return b
-
-
 def force_path(b, path):
     if path == "group":
         b.debug_set_num_cus(1)
     elif path == "split":
         b.set_kernel(sa.KERNEL_AUTO, sa.KOPT_PF_MULTI_LAUNCH)
-
-
-def carried_params(b):
-    w = 32 + (125 if b.precision == sa.F32_MIXED else 250)
-    idx = torch.arange(b.ncol, dtype=torch.int32, device=DEV)
-    return b.pack_members(idx, True)[w:].cpu().numpy().T        # [ncol][NPARAMS]
-
-
-def observe(state, planes, prm, n_sites, ops, rng, nan_sites=(), nan_obs=()):
-    """per site and operator: an observation near the live ensemble's mean, sd ~ the ensemble's spread"""
-    M = state.shape[0] // n_sites
-    obs = np.zeros((n_sites, len(ops)))
-    sd = np.zeros_like(obs)
-    for s in range(n_sites):
-        cols = np.arange(s * M, (s + 1) * M)
-        live = cols[state[cols, 29] == 0]
-        for i, op in enumerate(op_tuples(ops)):
-            h = er.predicted(op, state[live, :13], [p[:, live] for p in planes], lambda k: prm[live, k]) if len(live) else [0.0]
-            spread = float(np.std(h)) + 1e-3 * (abs(float(np.mean(h))) + 1e-3)
-            obs[s, i] = float(np.mean(h)) + spread * rng.normal()
-            sd[s, i] = spread * (0.5, 1.0, 2.0)[(s + i) % 3]
-    for s in nan_sites:
-        obs[s] = np.nan
-    for s, i in nan_obs:
-        obs[s, i] = np.nan
-    return obs, sd
-
-
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint64)
-
-
-def within(got, want, fc, n_sites):
-    """|got - want| <= 1e-10 max(|x|, the site's ensemble sd) per analysed pool"""
-    M = got.shape[0] // n_sites
-    for s in range(n_sites):
-        sl = slice(s * M, (s + 1) * M)
-        scale = np.maximum(np.abs(want[sl][:, SLOTS]), fc[sl][:, SLOTS].std(0) + 1e-300)
-        assert (np.abs(got[sl][:, SLOTS] - want[sl][:, SLOTS]) <= 1e-10 * scale).all(), s
-
-
-def forecast(base, n_sites, M, prec, steps=96, seed=1):
-    members = synth.perturbed_params(base, n_sites * M, seed=seed)
-    b = sites_batch(members, n_sites, prec)
-    planes, _ = b.run(0, steps)
-    return b, planes
 
 
 @pytest.mark.parametrize("path", ["auto", "group", "split"])

@@ -7,58 +7,15 @@ sites have at most 4096 particles and are at least as many as the CUs, else thre
 (SIPNET_KOPT_PF_MULTI_LAUNCH), and the reference.  HIP events around `calls` calls after a warm-up, median over `reps`
 repetitions, ms per call.
 usage: pf_sites_time.py [--calls K] [--reps R] [--out FILE] [--shapes 32x1024,256x1024,...]"""
-import argparse
-import os
-import sys
+import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import sipnet_amd as sa  # noqa: E402
-from sipnet_amd import synth  # noqa: E402
-
-T = 48
-
-
-def make(base, n_sites, M, prec):
-    b = sa.Batch(sa.flags_from(), n_sites, M, prec, fast_math=True)
-    for s in range(n_sites):
-        b.set_climate(s, synth.convert_raw(synth.round_like_file(synth.half_hourly_year_raw(T, site=s))))
-        b.set_params(s, synth.perturbed_params(base, M, seed=s))
-    b.setup()
-    planes, _ = b.run(0, T)
-    return b, planes[0]
-
-
-def median_ms(fn, calls, reps):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(calls):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / calls)
-    return float(np.median(out))
+import enkf_time_common as tc
+from enkf_time_common import sa
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=50)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shapes", default="32x1024,256x1024,16x8192,2x65536,64x4096")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("pf_sites_time.py needs a HIP device")
-    base, _ = sa.read_params(os.path.join(REPO, "sipnet_amd", "data", "base_forest.param"), sa.flags_from())
-    shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
+    args = tc.arguments(50, 7, "32x1024,256x1024,16x8192,2x65536,64x4096").parse_args()
+    base, shapes = tc.start("pf_sites_time.py", args.shapes)
     lines = ["# sipnet_batch_pf_analysis_sites vs sipnet_batch_pf_analysis over one site of the same particles; 48-step planes,",
              "# with_params (the parameter index is gathered), d_site_total / d_total given (no host synchronisation);",
              "# ms per call (weights + ancestors + gather), median of %d x %d calls after 5 warm-up calls" % (args.reps, args.calls),
@@ -75,7 +32,8 @@ def main():
                 if key == "group" and M > 4096:
                     res[key] = float("nan")
                     continue
-                b, nee = make(base, n_sites, M, prec)
+                b, planes = tc.make(base, n_sites, M, prec)
+                nee = planes[0]
                 if key == "group":
                     b.debug_set_num_cus(1)
                 elif key == "split":
@@ -85,26 +43,23 @@ def main():
                 sig = (tot.std(dim=1) * 1.5 + 1e-12).contiguous()
                 u0 = torch.rand(n_sites, dtype=torch.float64, device=nee.device)
                 total = torch.zeros(n_sites, dtype=torch.int64, device=nee.device)
-                res[key] = median_ms(lambda: b.pf_analysis_sites(nee, obs, sig, u0, True, total), args.calls, args.reps)
+                res[key] = tc.median_ms(lambda: b.pf_analysis_sites(nee, obs, sig, u0, True, total), args.calls, args.reps)
                 assert int(total.min().item()) > 0
                 if key == "default":
                     path = "group" if b.pf_info()["fused"] else "split"
                 b.close()
-            b, nee = make(base, 1, n, prec)
+            b, planes = tc.make(base, 1, n, prec)
+            nee = planes[0]
             tot = nee.double().sum(0)
             obs1, sig1 = float(tot.median()), float(tot.std()) * 1.5 + 1e-12
             total = torch.zeros(1, dtype=torch.int64, device=nee.device)
-            res["one"] = median_ms(lambda: b.pf_analysis_local(nee, obs1, sig1, 0.5, True, total), args.calls, args.reps)
+            res["one"] = tc.median_ms(lambda: b.pf_analysis_local(nee, obs1, sig1, 0.5, True, total), args.calls, args.reps)
             b.close()
             line = "%-10s %-9s %9d %11.4f %6s %11.4f %11.4f %11.4f %8.2f" % (
                 "%dx%d" % (n_sites, M), pname, n, res["default"], path, res["group"], res["split"], res["one"],
                 res["default"] / res["one"])
-            print(line, flush=True)
-            lines.append(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+            tc.emit(lines, line)
+    tc.write_out(lines, args.out)
 
 
 if __name__ == "__main__":
