@@ -692,6 +692,66 @@ int sipnet_batch_enkf_analysis_block(sipnet_batch *b, const sipnet_enkf_local *L
                                      const double *d_sd, const double *d_inflation, int32_t *d_site_info,
                                      int32_t *d_rows, void *hip_stream);
 
+/* ---- joint state-parameter ensemble Kalman filter: pools and parameters, a filter per site ------------------------
+ * The standard augmented-state update: some of a member's parameters are analysed variables next to its pools, moved
+ * through their sample covariance with the predicted observations.  Everything of sipnet_batch_enkf_analysis_sites
+ * holds (sites, live members, operators, codes, statistics with divisor n - 1, gains, alpha, serial order, NaN
+ * observations skipped, both paths and how one is chosen); what follows is what is added.
+ * A site's variables, in this order: the analysed pools (state-slot order), the analysed parameters (the order of
+ * params; the CONVERTED row of the member's own column), the h of the operators from the forecast.  An operator that
+ * divides by a parameter that is also analysed is not re-evaluated during the update: h is a linear variable.
+ * Which parameters: index must name a row whose converted value is the file value, or the file value / 365 (the nine
+ * rate rows: baseVegResp, baseSoilResp, litterBreakdownRate, the wood, leaf, fine-root and coarse-root turnover rates,
+ * baseFineRootResp, baseCoarseRootResp).  lo < hi are finite bounds in FILE units.
+ * sipnet_enkf_params_check: host only, no device.  SIPNET_ERR_BAD_ARGUMENT (sipnet_last_error says why): n_params
+ *   outside 0..SIPNET_ENKF_MAX_PARAMS; an index out of range; a derived row (psnTMax, coarseRootAllocation); an
+ *   initial condition, which only setup reads (plantWoodInit, laiInit, soilInit, soilWFracInit, litterInit, snowInit,
+ *   minNInit, soilOrgNInit, litterOrgNInit, plantStorageNInit); a phenology threshold (leafOnDay, leafOffDay,
+ *   gddLeafOn -- its row is overloaded by the leaf-on mode --, soilTempLeafOn); a row the conversion clamps (fAnoxia,
+ *   anaerobicDecompRate); an index listed twice; a bound that is not finite, or lo >= hi.  On success lo_converted /
+ *   hi_converted [n_params] (may be NULL) get the bounds in converted units by the conversion's own expression
+ *   (v / 365.0 for the rate rows): a file value at a bound maps to the converted bound exactly.
+ * Inflation: inflation[s] moves pools and h as before; param_inflation[s] (DEVICE [n_sites], NULL: 1) moves the
+ * parameter variables in the same stage by the same rule, mean + lambda (x - mean); a class whose lambda is 1 is left
+ * as it is.  It is checked like lambda: not finite or < 1 gives code -2.
+ * Limits and write-back, per live member of a code-1 site: the pools are clipped as before; every analysed parameter
+ * is clipped into [lo, hi] (converted units); the member keeps its forecast, pools AND parameters, when an analysed
+ * value is not finite, when hasSufficientBiomass fails, or when some allocation (leaf, wood, fineRoot) is analysed and
+ * the result fails ensureAllocation's test (one of the three >= 1, or 1 - leaf - wood - fineRoot < 0).  Otherwise its
+ * analysed pools and rows are written, and the derived rows that depend on analysed ones are rewritten by the
+ * conversion's own expressions: psnTMax = psnTOpt + (psnTOpt - psnTMin) when either is analysed, coarseRootAllocation
+ * = 1 - leaf - wood - fineRoot when an allocation is.  site_info is unchanged: {code, observations used, live members,
+ * members kept}.
+ * Bit-identical afterwards: every parameter row neither analysed nor derived from an analysed one; every parameter of
+ * a member that is not live or of a site whose code is not 1; every state slot outside analysed_mask.
+ * On a batch whose parameters are behind an index (after a resampling with_params) the call first gives every column
+ * its own rows.  With n_params = 0 and d_param_inflation NULL the state, site_info and all parameter rows equal
+ * sipnet_batch_enkf_analysis_sites' bit for bit, on both paths.
+ * Refusals (the parameter checks above among them, before any launch), the synchronous form (d_site_info NULL: the
+ * parameter inflation is read back and checked too) and the bookkeeping are sipnet_batch_enkf_analysis_sites'.
+ * Out of scope: parameters in sipnet_batch_enkf_analysis_local and _block (whether a neighbour's observation should
+ * move a site's parameters is a modelling decision), the node object and the CLI, a covariance-space form.
+ *
+ * sipnet_batch_get_params: the parameters each column carries (through the index if there is one, which it leaves as
+ * it is) to HOST memory, params[ncol][SIPNET_NPARAMS] like sipnet_batch_get_state.  file_units 0: the converted rows
+ * as the kernels read them; 1: the nine rate rows times 365.0, every other row as stored (derived and overloaded rows
+ * included).  Pending set_params rows are flushed first; the copy is ordered behind the batch's last launch on
+ * hip_stream, which is synchronised. */
+#define SIPNET_ENKF_MAX_PARAMS 16
+typedef struct sipnet_enkf_param {
+  int32_t index;      /* a sipnet_param_index */
+  int32_t reserved;
+  double lo, hi;      /* FILE units */
+} sipnet_enkf_param;
+int sipnet_enkf_params_check(int32_t n_params, const sipnet_enkf_param *params, double *lo_converted,
+                             double *hi_converted);
+int sipnet_batch_enkf_analysis_joint(sipnet_batch *b, int32_t n_obs, const sipnet_enkf_obs *ops, int32_t analysed_mask,
+                                     int32_t n_params, const sipnet_enkf_param *params,
+                                     const void *const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                     const double *d_obs, const double *d_sd, const double *d_inflation,
+                                     const double *d_param_inflation, int32_t *d_site_info, void *hip_stream);
+int sipnet_batch_get_params(sipnet_batch *b, double *params, int32_t file_units, void *hip_stream);
+
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its
  * range) and known on the device only; RCCL's send / receive sizes are host arguments, so an all-to-all

@@ -51,6 +51,14 @@ class EnkfObs(C.Structure):
                 ("scale", C.c_double)]
 
 
+ENKF_MAX_PARAMS = 16   # SIPNET_ENKF_MAX_PARAMS
+
+
+class EnkfParam(C.Structure):
+    """struct sipnet_enkf_param: one analysed parameter of sipnet_batch_enkf_analysis_joint (bounds in file units)"""
+    _fields_ = [("index", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
 class Event(C.Structure):
     """struct sipnet_event"""
     _fields_ = [("type", C.c_int32), ("year", C.c_int32), ("day", C.c_int32),
@@ -171,6 +179,10 @@ SIGNATURES = {
                                                  _P, _P, _P]),
     "sipnet_batch_enkf_analysis_sites": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
                                                    _P, _P, _P, _P]),
+    "sipnet_enkf_params_check": (C.c_int, [C.c_int32, _P, _P, _P]),
+    "sipnet_batch_enkf_analysis_joint": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32,
+                                                   C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "sipnet_batch_get_params": (C.c_int, [_P, _P, C.c_int32, _P]),
     "sipnet_enkf_local_schedule": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "sipnet_batch_enkf_local_create": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "sipnet_enkf_local_levels": (C.c_int32, [_P]),

@@ -378,6 +378,35 @@ class Batch:
         check(self.L.sipnet_batch_enkf_analysis_sites(self.h, *args, self._stream()), "enkf_analysis_sites")
         del keep
 
+    def enkf_analysis_joint(self, obs, sd, operators, analysed, params, planes=None, inflation=None, param_inflation=None,
+                            info_out=None):
+        """a joint state-parameter ensemble Kalman filter analysis, every site a filter of its own
+        (sipnet_batch_enkf_analysis_joint): enkf_analysis_sites with some of the members' parameters as analysed variables
+        next to the pools.  params: sa.enkf_param(name, lo, hi), at most sa.ENKF_MAX_PARAMS (bounds in file units; the
+        members' converted rows are clipped into them and rewritten); param_inflation: one value per site for the
+        parameter variables (None: 1); the other arguments as enkf_analysis_sites."""
+        from ._lib import EnkfParam
+        t = self._torch
+        args, keep = self._enkf_args("enkf_analysis_joint", obs, sd, operators, analysed, planes, inflation, info_out)
+        prm = list(params)
+        arr = (EnkfParam * max(len(prm), 1))(*prm)
+        pinfl = None
+        if param_inflation is not None:
+            pinfl = t.as_tensor(param_inflation, dtype=t.float64).reshape(-1).to(self.device).contiguous()
+            if pinfl.numel() != self.n_sites:
+                raise ValueError(f"enkf_analysis_joint: param_inflation needs {self.n_sites} values, got {pinfl.numel()}")
+        check(self.L.sipnet_batch_enkf_analysis_joint(
+            self.h, *args[:3], len(prm), arr, *args[3:10], C.c_void_p(pinfl.data_ptr()) if pinfl is not None else None,
+            args[10], self._stream()), "enkf_analysis_joint")
+        del keep
+
+    def get_params(self, file_units=False):
+        """the parameters every column carries (sipnet_batch_get_params) -> [ncol][80]: the converted rows as the kernels
+        read them, or with file_units the nine per-year rates back in file units (x 365)"""
+        p = np.zeros((self.ncol, NPARAMS))
+        check(self.L.sipnet_batch_get_params(self.h, p.ctypes.data, int(bool(file_units)), self._stream()), "get_params")
+        return p
+
     def enkf_localization(self, nbr_ptr, nbr, rho, n_obs):
         """a localization of this batch's sites for enkf_analysis_local (sipnet_batch_enkf_local_create): site s's neighbours
         nbr[nbr_ptr[s]:nbr_ptr[s + 1]] (strictly ascending, not s) with tapers rho in (0, 1] -- e.g. sa.gaspari_cohn's CSR

@@ -93,6 +93,15 @@ def enkf_plane(plane, divide_by=None, scale=1.0):
     return EnkfObs(ENKF_PLANE, 0, PLANES.index(plane), _param_or_none(divide_by), float(scale))
 
 
+def enkf_param(name, lo, hi):
+    """an analysed parameter of Batch.enkf_analysis_joint: its name (PARAM_NAMES) and its bounds lo < hi in FILE units"""
+    from ._lib import EnkfParam
+    i = param_index(name)
+    if i < 0:
+        raise ValueError(f"enkf_param: {name!r} is not a parameter name")
+    return EnkfParam(i, 0, float(lo), float(hi))
+
+
 def _param_or_none(name):
     if name is None:
         return -1

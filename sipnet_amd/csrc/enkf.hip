@@ -36,7 +36,8 @@ constexpr int kMaxVars = kPools + kMaxObs;
 constexpr int kMaxGroupChunks = 16;        // one workgroup per site: sites of at most 16 x 256 members
 constexpr int kLdsWork = 40 * 1024;        // ... whose working copies fit here stay in LDS, else in the scratch block
 constexpr double kTiny = 0.000001;         // TINY, common/util.h
-constexpr int kStat = 3 * kMaxVars;         // split path, per site: means | K | alpha K of every variable
+constexpr int kMaxPrm = SIPNET_ENKF_MAX_PARAMS;   // the joint analysis: analysed parameters, between the pools and the h
+constexpr int kJointVars = kMaxVars + kMaxPrm;
 constexpr int kAnalysed = 1, kNoObs = -1, kBadInput = -2, kTooFew = 0;
 
 struct EnkfOp {
@@ -44,6 +45,8 @@ struct EnkfOp {
   double scale;
 };
 struct EnkfArgs {
+  static constexpr int kCap = kMaxVars;    // variables a site can have: the pitch of smW, part and stat
+  static constexpr bool kJoint = false;
   EnkfOp op[kMaxObs];
   int32_t nObs, nA, nv, nCh;
   int32_t pool[kPools];                    // the analysed state slots, ascending
@@ -69,6 +72,18 @@ struct EnkfArgs {
   int32_t* src;                            // localized analysis: [n_sites] enkfCodeKernel's codes, kept (else null)
   int32_t useLds;                          // one workgroup per site: W in LDS ([nv][M])
 };
+// sipnet_batch_enkf_analysis_joint: the variables are the nPool analysed pools, the nPrm analysed parameters (nA = nPool +
+// nPrm: whatever is not an h), then the h.  The kernels are the per-site call's, instantiated for these arguments.
+struct JointArgs : EnkfArgs {
+  static constexpr int kCap = kJointVars;
+  static constexpr bool kJoint = true;
+  int32_t nPool, nPrm;
+  int32_t prmRow[kMaxPrm];                 // the analysed rows of prmOut, in the caller's order
+  double lo[kMaxPrm], hi[kMaxPrm];         // their bounds, converted units
+  const double* prmInfl;                   // [n_sites] or null: lambda of the parameter variables
+  double* prmOut;                          // d_prm [NPARAMS][ncol], every column its own rows: read by the load, written by the limits
+  int32_t leaf, wood, fineRoot, opt, tmin; // where leafAllocation .. psnTMin are among the analysed parameters, or -1
+};
 
 __device__ __forceinline__ bool liveAt(const EnkfArgs& a, int s, int64_t j) {
   return j < a.M && a.siteStatus[s] == 0 && a.state[(int64_t)ST_status * a.ncol + (int64_t)s * a.M + j] == 0.0;
@@ -90,6 +105,26 @@ __host__ __device__ inline int siteInputs(const double* obs, const double* sd, c
   }
   *used = u;
   return bad ? kBadInput : (u == 0 ? kNoObs : kAnalysed);
+}
+
+// ... and the joint analysis's lambda of the parameters, checked like the other
+template <class A>
+__device__ __forceinline__ int siteInputsOf(const A& a, int s, int* used) {
+  int code = siteInputs(a.obs, a.sd, a.infl, a.nObs, s, used);
+  if constexpr (A::kJoint)
+    if (a.prmInfl) {
+      const double l = a.prmInfl[s];
+      if (!(l >= 1.0) || !(l < INFINITY)) code = kBadInput;
+    }
+  return code;
+}
+// the joint analysis's lambda of variable q at site s: the parameters have their own
+__device__ __forceinline__ double lambdaOf(const JointArgs& a, int s, int q) {
+  if (q >= a.nPool && q < a.nA) return a.prmInfl ? a.prmInfl[s] : 1.0;
+  return a.infl ? a.infl[s] : 1.0;
+}
+__device__ __forceinline__ bool inflates(const JointArgs& a, int s) {
+  return (a.infl && a.infl[s] != 1.0) || (a.prmInfl && a.prmInfl[s] != 1.0);
 }
 
 // h of operator i for column col, from the forecast
@@ -124,8 +159,9 @@ __device__ __forceinline__ int blockSum(int* smI, int v) {
   __syncthreads();
   return smI[0] + smI[1] + smI[2] + smI[3];
 }
-__device__ __forceinline__ double combine4(const double* smW, int q) {   // smW [4][kMaxVars]: the waves in order
-  return ((smW[q] + smW[kMaxVars + q]) + smW[2 * kMaxVars + q]) + smW[3 * kMaxVars + q];
+template <int kCap>
+__device__ __forceinline__ double combine4(const double* smW, int q) {   // smW [4][kCap]: the waves in order
+  return ((smW[q] + smW[kCap + q]) + smW[2 * kCap + q]) + smW[3 * kCap + q];
 }
 // chunks per segment of a site of nCh chunks: at most 64 segments
 constexpr int kMaxSegs = 64;
@@ -154,11 +190,11 @@ __device__ __forceinline__ double inflated(double x, double mean, double lam) { 
 
 // the physical limits of one live member: its analysed pools clipped, then hasSufficientBiomass (sipnet.c:1530-1536) of
 // the result; false = the member keeps its forecast.  fin[v] gets the clipped values.
-__device__ bool limited(const EnkfArgs& a, int64_t col, const double* W, int64_t ldw, int64_t j, double* fin) {
+__device__ bool limited(const EnkfArgs& a, int nPool, int64_t col, const double* W, int64_t ldw, int64_t j, double* fin) {
   double f[kPools];
   for (int p = 0; p < kPools; p++) f[p] = a.state[(int64_t)p * a.ncol + col];
   bool finite = true;
-  for (int q = 0; q < a.nA; q++) {
+  for (int q = 0; q < nPool; q++) {
     double v = W[(int64_t)q * ldw + j];
     if (a.pool[q] != ST_plantCAccountingDelta && v < 0.0) v = 0.0;
     finite = finite && fabs(v) < INFINITY;
@@ -169,26 +205,78 @@ __device__ bool limited(const EnkfArgs& a, int64_t col, const double* W, int64_t
   return finite && f[ST_plantWoodC] > kTiny && totalWood > kTiny && totalRoot > kTiny;
 }
 
+// the joint analysis's limits of one live member's parameters, after limited(): every analysed parameter clipped into its
+// bounds, in place in W; false = one is not finite, or an allocation is analysed and the result fails ensureAllocation's test
+// (setupKernel, step_kernel.hip) -- the member keeps its forecast
+__device__ __forceinline__ double prmNow(const JointArgs& a, const double* W, int64_t ldw, int64_t j, int64_t col, int k, int row) {
+  return k >= 0 ? W[(int64_t)(a.nPool + k) * ldw + j] : a.prmOut[(int64_t)row * a.ncol + col];
+}
+__device__ bool limitedParams(const JointArgs& a, int64_t col, double* W, int64_t ldw, int64_t j) {
+  bool ok = true;
+  for (int k = 0; k < a.nPrm; k++) {
+    double* x = W + (int64_t)(a.nPool + k) * ldw + j;
+    double v = *x;
+    v = v < a.lo[k] ? a.lo[k] : (v > a.hi[k] ? a.hi[k] : v);
+    ok = ok && fabs(v) < INFINITY;
+    *x = v;
+  }
+  if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0) {
+    const double leaf = prmNow(a, W, ldw, j, col, a.leaf, SP_leafAllocation), wood = prmNow(a, W, ldw, j, col, a.wood, SP_woodAllocation),
+                 fine = prmNow(a, W, ldw, j, col, a.fineRoot, SP_fineRootAllocation);
+    if (leaf >= 1.0 || wood >= 1.0 || fine >= 1.0 || 1 - leaf - wood - fine < 0) ok = false;
+  }
+  return ok;
+}
+// ... and its rows written: the analysed ones, then the derived rows that depend on them, by convertParamsKernel's expressions
+__device__ void writeParams(const JointArgs& a, int64_t col, const double* W, int64_t ldw, int64_t j) {
+  for (int k = 0; k < a.nPrm; k++) a.prmOut[(int64_t)a.prmRow[k] * a.ncol + col] = W[(int64_t)(a.nPool + k) * ldw + j];
+  if (a.opt >= 0 || a.tmin >= 0) {
+    const double opt = prmNow(a, W, ldw, j, col, a.opt, SP_psnTOpt), tmin = prmNow(a, W, ldw, j, col, a.tmin, SP_psnTMin);
+    a.prmOut[(int64_t)SP_psnTMax * a.ncol + col] = opt + (opt - tmin);
+  }
+  if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0) {
+    const double leaf = prmNow(a, W, ldw, j, col, a.leaf, SP_leafAllocation), wood = prmNow(a, W, ldw, j, col, a.wood, SP_woodAllocation),
+                 fine = prmNow(a, W, ldw, j, col, a.fineRoot, SP_fineRootAllocation);
+    a.prmOut[(int64_t)SP_coarseRootAllocation * a.ncol + col] = 1 - leaf - wood - fine;
+  }
+}
+// one live member through the limits and, unless it keeps its forecast, written back: its analysed pools (and parameters)
+template <class A>
+__device__ __forceinline__ bool limitAndWrite(const A& a, int64_t col, double* W, int64_t ldw, int64_t j) {
+  double fin[kPools];
+  int nPool = a.nA;
+  if constexpr (A::kJoint) nPool = a.nPool;
+  bool ok = limited(a, nPool, col, W, ldw, j, fin);
+  if constexpr (A::kJoint) ok = limitedParams(a, col, W, ldw, j) && ok;
+  if (!ok) return false;
+  for (int q = 0; q < nPool; q++) a.state[(int64_t)a.pool[q] * a.ncol + col] = fin[q];
+  if constexpr (A::kJoint) writeParams(a, col, W, ldw, j);
+  return true;
+}
+
 // ---- one workgroup per site -------------------------------------------------------------------------------------------
-struct GroupLds {
-  double smW[kMaxGroupChunks][4 * kMaxVars];
-  double chunkTot[kMaxGroupChunks][kMaxVars];
-  double tot[kMaxVars];
-  double mean[kMaxVars];
-  double K[kMaxVars], aK[kMaxVars];
+template <int kCapacity>
+struct GroupLdsOf {
+  static constexpr int kCap = kCapacity;
+  double smW[kMaxGroupChunks][4 * kCap];
+  double chunkTot[kMaxGroupChunks][kCap];
+  double tot[kCap];
+  double mean[kCap];
+  double K[kCap], aK[kCap];
   int smI[4];
 };
+using GroupLds = GroupLdsOf<kMaxVars>;
 // the site's sums of val(j, q), q < V, in the fixed order -> g.tot
-template <class F>
-__device__ void siteSums(GroupLds& g, int V, int nCh, F val) {
+template <class G, class F>
+__device__ void siteSums(G& g, int V, int nCh, F val) {
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int q = 0; q < V; q++)
     for (int c = 0; c < nCh; c++) {
       const double v = waveSum(val((int64_t)c * 256 + tid, q));
-      if (lane == 0) g.smW[c][wave * kMaxVars + q] = v;
+      if (lane == 0) g.smW[c][wave * G::kCap + q] = v;
     }
   __syncthreads();
-  for (int k = tid; k < V * nCh; k += 256) g.chunkTot[k / V][k % V] = combine4(g.smW[k / V], k % V);
+  for (int k = tid; k < V * nCh; k += 256) g.chunkTot[k / V][k % V] = combine4<G::kCap>(g.smW[k / V], k % V);
   __syncthreads();
   if (tid < V) {
     double t = 0.0;
@@ -197,22 +285,23 @@ __device__ void siteSums(GroupLds& g, int V, int nCh, F val) {
   }
   __syncthreads();
 }
-__device__ int blockCount(GroupLds& g, int v) {
+template <class G>
+__device__ int blockCount(G& g, int v) {
   const int n = blockSum(g.smI, v);
   __syncthreads();
   return n;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void enkfSiteKernel(EnkfArgs a) {
+template <typename T, class A>
+__global__ __launch_bounds__(256) void enkfSiteKernel(A a) {
   extern __shared__ double ldsWork[];
-  __shared__ GroupLds g;
+  __shared__ GroupLdsOf<A::kCap> g;
   const int tid = (int)threadIdx.x, s = (int)blockIdx.x, nCh = a.nCh, nA = a.nA, nv = a.nv;
   const int64_t base = (int64_t)s * a.M;
   double* W = a.useLds ? ldsWork : a.work + base;
   const int64_t ldw = a.useLds ? a.M : a.ncol;
   int used;
-  int code = siteInputs(a.obs, a.sd, a.infl, a.nObs, s, &used);
+  int code = siteInputsOf(a, s, &used);
   int mine = 0;
   for (int64_t j = tid; j < a.M; j += 256) mine += liveAt(a, s, j) ? 1 : 0;
   const int n = blockCount(g, mine);
@@ -227,18 +316,32 @@ __global__ __launch_bounds__(256) void enkfSiteKernel(EnkfArgs a) {
   // the working copies: analysed pools and predicted observations of the live members (each member: its own thread throughout)
   for (int64_t j = tid; j < a.M; j += 256)
     if (liveAt(a, s, j)) {
-      for (int q = 0; q < nA; q++) W[(int64_t)q * ldw + j] = a.state[(int64_t)a.pool[q] * a.ncol + base + j];
+      if constexpr (A::kJoint) {
+        for (int q = 0; q < a.nPool; q++) W[(int64_t)q * ldw + j] = a.state[(int64_t)a.pool[q] * a.ncol + base + j];
+        for (int k = 0; k < a.nPrm; k++) W[(int64_t)(a.nPool + k) * ldw + j] = a.prmOut[(int64_t)a.prmRow[k] * a.ncol + base + j];
+      } else {
+        for (int q = 0; q < nA; q++) W[(int64_t)q * ldw + j] = a.state[(int64_t)a.pool[q] * a.ncol + base + j];
+      }
       for (int i = 0; i < a.nObs; i++) W[(int64_t)(nA + i) * ldw + j] = predicted<T>(a, i, base + j);
     }
   const double nd = (double)n;
   const double lam = a.infl ? a.infl[s] : 1.0;
-  if (lam != 1.0) {
+  bool inflate = lam != 1.0;
+  if constexpr (A::kJoint) inflate = inflates(a, s);
+  if (inflate) {
     siteSums(g, nv, nCh, [&](int64_t j, int q) { return liveAt(a, s, j) ? W[(int64_t)q * ldw + j] : 0.0; });
     if (tid < nv) g.mean[tid] = g.tot[tid] / nd;
     __syncthreads();
     for (int64_t j = tid; j < a.M; j += 256)
       if (liveAt(a, s, j))
-        for (int q = 0; q < nv; q++) W[(int64_t)q * ldw + j] = inflated(W[(int64_t)q * ldw + j], g.mean[q], lam);
+        for (int q = 0; q < nv; q++) {
+          if constexpr (A::kJoint) {   // (a lambda per variable class; a class at 1 is left as it is)
+            const double l = lambdaOf(a, s, q);
+            if (l != 1.0) W[(int64_t)q * ldw + j] = inflated(W[(int64_t)q * ldw + j], g.mean[q], l);
+          } else {
+            W[(int64_t)q * ldw + j] = inflated(W[(int64_t)q * ldw + j], g.mean[q], lam);
+          }
+        }
   }
   for (int i = 0; i < a.nObs; i++) {
     const double y = a.obs[(int64_t)s * a.nObs + i];
@@ -268,14 +371,7 @@ __global__ __launch_bounds__(256) void enkfSiteKernel(EnkfArgs a) {
   }
   int kept = 0;
   for (int64_t j = tid; j < a.M; j += 256)
-    if (liveAt(a, s, j)) {
-      double fin[kPools];
-      if (limited(a, base + j, W, ldw, j, fin)) {
-        for (int q = 0; q < nA; q++) a.state[(int64_t)a.pool[q] * a.ncol + base + j] = fin[q];
-      } else {
-        kept++;
-      }
-    }
+    if (liveAt(a, s, j) && !limitAndWrite(a, base + j, W, ldw, j)) kept++;
   kept = blockCount(g, kept);
   if (tid == 0) {
     int32_t* inf = a.info + 4 * (int64_t)s;
@@ -294,20 +390,28 @@ __device__ int siteCount(const int32_t* v, int64_t nCh) {
   return blockSum(smI, c);
 }
 // stage i (i < 0: the inflation) leaves site s alone: not analysed, not inflated, or no observation i
-__device__ __forceinline__ bool stageSkipped(const EnkfArgs& a, int s, int i) {
+template <class A>
+__device__ __forceinline__ bool stageSkipped(const A& a, int s, int i) {
   if (splitCode(a, s) != kAnalysed) return true;
+  if constexpr (A::kJoint)
+    if (i < 0) return !inflates(a, s);
   if (i < 0) return !(a.infl && a.infl[s] != 1.0);
   return a.obs[(int64_t)s * a.nObs + i] != a.obs[(int64_t)s * a.nObs + i];
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void enkfLoadKernel(EnkfArgs a) {
+template <typename T, class A>
+__global__ __launch_bounds__(256) void enkfLoadKernel(A a) {
   __shared__ int smI[4];
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int64_t j = (int64_t)blockIdx.y * 256 + tid, col = (int64_t)s * a.M + j;
   const bool live = liveAt(a, s, j);
   if (live) {
-    for (int q = 0; q < a.nA; q++) a.work[(int64_t)q * a.ncol + col] = a.state[(int64_t)a.pool[q] * a.ncol + col];
+    if constexpr (A::kJoint) {
+      for (int q = 0; q < a.nPool; q++) a.work[(int64_t)q * a.ncol + col] = a.state[(int64_t)a.pool[q] * a.ncol + col];
+      for (int k = 0; k < a.nPrm; k++) a.work[(int64_t)(a.nPool + k) * a.ncol + col] = a.prmOut[(int64_t)a.prmRow[k] * a.ncol + col];
+    } else {
+      for (int q = 0; q < a.nA; q++) a.work[(int64_t)q * a.ncol + col] = a.state[(int64_t)a.pool[q] * a.ncol + col];
+    }
     for (int i = 0; i < a.nObs; i++) a.work[(int64_t)(a.nA + i) * a.ncol + col] = predicted<T>(a, i, col);
   }
   const int n = blockSum(smI, live ? 1 : 0);
@@ -315,12 +419,13 @@ __global__ __launch_bounds__(256) void enkfLoadKernel(EnkfArgs a) {
 }
 
 // one workgroup per site, after the load: the live count and the site's code, once
-__global__ __launch_bounds__(256) void enkfCodeKernel(EnkfArgs a) {
+template <class A>
+__global__ __launch_bounds__(256) void enkfCodeKernel(A a) {
   const int s = (int)blockIdx.x;
   const int n = siteCount(a.cnt + (int64_t)s * a.nCh, a.nCh);
   if (threadIdx.x == 0) {
     int used;
-    int code = siteInputs(a.obs, a.sd, a.infl, a.nObs, s, &used);
+    int code = siteInputsOf(a, s, &used);
     if (code == kAnalysed && n < 2) code = kTooFew;
     a.site[2 * (int64_t)s] = code;
     a.site[2 * (int64_t)s + 1] = n;
@@ -330,7 +435,9 @@ __global__ __launch_bounds__(256) void enkfCodeKernel(EnkfArgs a) {
 
 // a chunk's sums for stage i (i < 0: the inflation's means over all variables): centred = 0 the variables,
 // 1 the centred products with h_i (means from stat)
-__global__ __launch_bounds__(256) void enkfPartialKernel(EnkfArgs a, int i, int centred) {
+template <class A>
+__global__ __launch_bounds__(256) void enkfPartialKernel(A a, int i, int centred) {
+  constexpr int kMaxVars = A::kCap, kStat = 3 * A::kCap;
   __shared__ double smW[4 * kMaxVars];
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x, c = (int)blockIdx.y;
   if (stageSkipped(a, s, i)) return;
@@ -349,12 +456,14 @@ __global__ __launch_bounds__(256) void enkfPartialKernel(EnkfArgs a, int i, int 
     if ((tid & 63) == 0) smW[(tid >> 6) * kMaxVars + q] = v;
   }
   __syncthreads();
-  if (tid < V) a.part[((int64_t)s * a.nCh + c) * kMaxVars + tid] = combine4(smW, tid);
+  if (tid < V) a.part[((int64_t)s * a.nCh + c) * kMaxVars + tid] = combine4<kMaxVars>(smW, tid);
 }
 
 // one workgroup per site: the chunks' sums (every segment of every variable in order; the segments by one wave's butterfly)
 // -> the means (centred = 0) or the gains (centred = 1)
-__global__ __launch_bounds__(256) void enkfFinalKernel(EnkfArgs a, int i, int centred) {
+template <class A>
+__global__ __launch_bounds__(256) void enkfFinalKernel(A a, int i, int centred) {
+  constexpr int kMaxVars = A::kCap, kStat = 3 * A::kCap;
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   if (stageSkipped(a, s, i)) return;
   __shared__ double tot[kMaxVars], seg[kMaxSegs][kMaxVars];
@@ -387,13 +496,23 @@ __global__ __launch_bounds__(256) void enkfFinalKernel(EnkfArgs a, int i, int ce
 }
 
 // a chunk's members moved by observation i (i < 0: inflated)
-__global__ __launch_bounds__(256) void enkfUpdateKernel(EnkfArgs a, int i) {
+template <class A>
+__global__ __launch_bounds__(256) void enkfUpdateKernel(A a, int i) {
+  constexpr int kMaxVars = A::kCap, kStat = 3 * A::kCap;
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   if (stageSkipped(a, s, i)) return;
   const int64_t j = (int64_t)blockIdx.y * 256 + tid, col = (int64_t)s * a.M + j;
   if (!liveAt(a, s, j)) return;
   const double* st = a.stat + (int64_t)s * kStat;
   if (i < 0) {
+    if constexpr (A::kJoint) {   // (a lambda per variable class; a class at 1 is left as it is)
+      for (int q = 0; q < a.nv; q++) {
+        const double l = lambdaOf(a, s, q);
+        double* x = a.work + (int64_t)q * a.ncol + col;
+        if (l != 1.0) *x = inflated(*x, st[q], l);
+      }
+      return;
+    }
     const double lam = a.infl[s];
     for (int q = 0; q < a.nv; q++) {
       double* x = a.work + (int64_t)q * a.ncol + col;
@@ -411,32 +530,27 @@ __global__ __launch_bounds__(256) void enkfUpdateKernel(EnkfArgs a, int i) {
     }
 }
 
-__global__ __launch_bounds__(256) void enkfLimitKernel(EnkfArgs a) {
+template <class A>
+__global__ __launch_bounds__(256) void enkfLimitKernel(A a) {
   __shared__ int smI[4];
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   if (splitCode(a, s) != kAnalysed) return;
   const int64_t j = (int64_t)blockIdx.y * 256 + tid, col = (int64_t)s * a.M + j;
   int kept = 0;
-  if (liveAt(a, s, j)) {
-    double fin[kPools];
-    if (limited(a, col, a.work + (int64_t)s * a.M, a.ncol, j, fin)) {
-      for (int q = 0; q < a.nA; q++) a.state[(int64_t)a.pool[q] * a.ncol + col] = fin[q];
-    } else {
-      kept = 1;
-    }
-  }
+  if (liveAt(a, s, j) && !limitAndWrite(a, col, a.work + (int64_t)s * a.M, a.ncol, j)) kept = 1;
   kept = blockSum(smI, kept);
   if (tid == 0) a.kept[(int64_t)s * a.nCh + blockIdx.y] = kept;
 }
 
 // one workgroup per site
-__global__ __launch_bounds__(256) void enkfInfoKernel(EnkfArgs a) {
+template <class A>
+__global__ __launch_bounds__(256) void enkfInfoKernel(A a) {
   const int s = (int)blockIdx.x;
   const int code = splitCode(a, s);
   const int kept = code == kAnalysed ? siteCount(a.kept + (int64_t)s * a.nCh, a.nCh) : 0;
   if (threadIdx.x == 0) {
     int used;
-    (void)siteInputs(a.obs, a.sd, a.infl, a.nObs, s, &used);
+    (void)siteInputsOf(a, s, &used);
     int32_t* inf = a.info + 4 * (int64_t)s;
     inf[0] = code; inf[1] = code == kAnalysed ? used : 0; inf[2] = a.site[2 * (int64_t)s + 1]; inf[3] = kept;
   }
@@ -872,17 +986,17 @@ int enkfBegin(const char* name, sipnet_batch* b, int32_t n_obs, const sipnet_enk
 }
 
 // The batch's scratch block sized, grown and carved, in this order: the working copies [nv][ncol] (workInGlobal: else they
-// live in LDS) | part [sites][chunks][kMaxVars] | stat [sites][kStat] | matPerSite doubles of matrices per site | info [sites][4]
+// live in LDS) | part [sites][chunks][cap] | stat [sites][3 cap] (cap: the kernels' A::kCap) | matPerSite doubles of matrices per site | info [sites][4]
 // (a.info is d_site_info where given) | cnt, kept [sites][chunks] | site [sites][2] | src [sites] (withSrc).  part, stat, cnt,
 // kept and site are the per-chunk launches' (perChunk: without them the regions are empty, and cnt, kept and site, which the
 // one-workgroup-per-site kernel never reads, all point at the end of info).  *mat, where asked for, gets the matrices' base.
 int enkfScratch(sipnet_batch* b, EnkfArgs& a, int32_t* d_site_info, bool workInGlobal, bool perChunk, bool withSrc,
-                size_t matPerSite, double** mat) {
+                size_t matPerSite, double** mat, int cap = kMaxVars) {
   const size_t nSites = (size_t)b->n_sites;
   const size_t nWork = workInGlobal ? (size_t)a.nv * (size_t)b->ncol : 0;
   const size_t nCnt = perChunk ? nSites * a.nCh : 0;
-  const size_t nPart = nCnt * kMaxVars;
-  const size_t nStat = perChunk ? nSites * kStat : 0;
+  const size_t nPart = nCnt * cap;
+  const size_t nStat = perChunk ? nSites * 3 * cap : 0;
   const size_t nMat = nSites * matPerSite;
   const size_t nSite = perChunk ? 2 * nSites : 0;
   const size_t nInt = nSites * 4 + 2 * nCnt + nSite + (withSrc ? nSites : 0);
@@ -914,26 +1028,30 @@ dim3 siteGrid(const sipnet_batch* b) { return dim3((unsigned)b->n_sites); }
 
 // the front of the per-chunk launches: the load (the planes' elements float or double), the codes, the sites that a
 // localization's sources reach (L), the inflation
-void enkfFront(const sipnet_batch* b, const EnkfArgs& a, int32_t elem_is_f32, const sipnet_enkf_local* L, hipStream_t stream) {
+template <class A>
+void enkfFront(const sipnet_batch* b, const A& a, int32_t elem_is_f32, const sipnet_enkf_local* L, hipStream_t stream) {
   const dim3 chunks = chunkGrid(b, a), sites = siteGrid(b);
-  hipLaunchKernelGGL(elem_is_f32 ? enkfLoadKernel<float> : enkfLoadKernel<double>, chunks, dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(enkfCodeKernel, sites, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL((elem_is_f32 ? enkfLoadKernel<float, A> : enkfLoadKernel<double, A>), chunks, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(enkfCodeKernel<A>, sites, dim3(256), 0, stream, a);
   if (L)
     hipLaunchKernelGGL(enkfReachKernel, dim3((sites.x + 255) / 256), dim3(256), 0, stream, a, L->d_inPtr, L->d_in,
                        (int64_t)b->n_sites);
-  if (a.infl) {
-    hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, -1, 0);
-    hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, -1, 0);
-    hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, -1);
+  bool inflation = a.infl != nullptr;
+  if constexpr (A::kJoint) inflation = inflation || a.prmInfl != nullptr;
+  if (inflation) {
+    hipLaunchKernelGGL(enkfPartialKernel<A>, chunks, dim3(256), 0, stream, a, -1, 0);
+    hipLaunchKernelGGL(enkfFinalKernel<A>, sites, dim3(256), 0, stream, a, -1, 0);
+    hipLaunchKernelGGL(enkfUpdateKernel<A>, chunks, dim3(256), 0, stream, a, -1);
   }
 }
 
 // the tail of every analysis: the limits and the info of the per-chunk launches (perChunk: the one-workgroup-per-site kernel
 // has done its own), the launches' error, what sipnet_batch_pf_info reports, the batch busy on the stream
-int enkfEnd(sipnet_batch* b, const EnkfArgs& a, bool perChunk, int32_t fused, int32_t grid, hipStream_t stream) {
+template <class A>
+int enkfEnd(sipnet_batch* b, const A& a, bool perChunk, int32_t fused, int32_t grid, hipStream_t stream) {
   if (perChunk) {
-    hipLaunchKernelGGL(enkfLimitKernel, chunkGrid(b, a), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(enkfInfoKernel, siteGrid(b), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(enkfLimitKernel<A>, chunkGrid(b, a), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(enkfInfoKernel<A>, siteGrid(b), dim3(256), 0, stream, a);
   }
   HIP_TRY(hipGetLastError());
   b->pfInfo.fused = fused;
@@ -941,6 +1059,50 @@ int enkfEnd(sipnet_batch* b, const EnkfArgs& a, bool perChunk, int32_t fused, in
   b->pfInfo.budget = 0;
   b->pfInfo.nSlots = b->ncol;
   return markBusy(b, stream);
+}
+
+// the per-site analysis between enkfBegin and the end of the call, for the per-site call's arguments or the joint call's
+template <class A>
+int enkfSites(sipnet_batch* b, A& a, int32_t n_obs, int32_t elem_is_f32, int32_t* d_site_info, hipStream_t stream) {
+  const int64_t nSites = b->n_sites, M = b->n_members;
+  // the per-chunk launches unless the sites outnumber the CUs four times over (profiles/r08_enkf_sites_time.txt: one
+  // workgroup per site loses or ties at every shape up to 256 sites x 1 024 members -- 0.29 ms against 0.19); big sites or
+  // SIPNET_KOPT_PF_MULTI_LAUNCH: always the launches
+  const bool group = M <= 256 * kMaxGroupChunks && nSites >= 4 * (int64_t)b->numCUs &&
+                     !(b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
+  const size_t ldsBytes = (size_t)a.nv * (size_t)M * sizeof(double);
+  a.useLds = group && ldsBytes <= (size_t)kLdsWork;
+  const auto siteKernel = elem_is_f32 ? enkfSiteKernel<float, A> : enkfSiteKernel<double, A>;
+  if constexpr (A::kJoint)
+    if (a.useLds) {   // (31 KB of static LDS and the working copies can pass 64 KB together: ask first, as the block-local analysis does)
+      int ldsMax = 0;
+      hipFuncAttributes attr;
+      HIP_TRY(hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, b->device));
+      HIP_TRY(hipFuncGetAttributes(&attr, (const void*)siteKernel));
+      if (ldsBytes + attr.sharedSizeBytes > (size_t)ldsMax) {
+        a.useLds = 0;
+      } else if (ldsBytes + attr.sharedSizeBytes > 64 * 1024 &&
+                 hipFuncSetAttribute((const void*)siteKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes) != hipSuccess) {
+        (void)hipGetLastError();
+        a.useLds = 0;
+      }
+    }
+  int rc = enkfScratch(b, a, d_site_info, /*workInGlobal=*/!a.useLds, /*perChunk=*/!group, /*withSrc=*/false, 0, nullptr, A::kCap);
+  if (rc) return rc;
+  if (group) {
+    hipLaunchKernelGGL(siteKernel, siteGrid(b), dim3(256), a.useLds ? ldsBytes : 0, stream, a);
+  } else {
+    const dim3 chunks = chunkGrid(b, a), sites = siteGrid(b);
+    enkfFront(b, a, elem_is_f32, nullptr, stream);
+    for (int i = 0; i < n_obs; i++) {
+      hipLaunchKernelGGL(enkfPartialKernel<A>, chunks, dim3(256), 0, stream, a, i, 0);
+      hipLaunchKernelGGL(enkfFinalKernel<A>, sites, dim3(256), 0, stream, a, i, 0);
+      hipLaunchKernelGGL(enkfPartialKernel<A>, chunks, dim3(256), 0, stream, a, i, 1);
+      hipLaunchKernelGGL(enkfFinalKernel<A>, sites, dim3(256), 0, stream, a, i, 1);
+      hipLaunchKernelGGL(enkfUpdateKernel<A>, chunks, dim3(256), 0, stream, a, i);
+    }
+  }
+  return enkfEnd(b, a, /*perChunk=*/!group, group ? 1 : 0, group ? (int32_t)b->n_sites : 0, stream);
 }
 
 // the checks of a localization's lists (withRho: and of its tapers)
@@ -1005,6 +1167,63 @@ int localChecks(const char* name, const sipnet_batch* b, const sipnet_enkf_local
   return 0;
 }
 
+
+// ---- the joint analysis's parameters ------------------------------------------------------------------------------------------
+const char* const kParamName[SIPNET_NPARAMS] = {
+#define SIPNET_PARAM(index, field, file_name, rule) #field,
+#include "../../include/sipnet_params.def"
+#undef SIPNET_PARAM
+};
+// convertParamsKernel's per-year -> per-day rows: the converted value is the file value / 365.0
+bool rateRow(int p) {
+  switch (p) {
+    case SP_baseVegResp: case SP_litterBreakdownRate: case SP_baseSoilResp: case SP_woodTurnoverRate:
+    case SP_leafTurnoverRate: case SP_fineRootTurnoverRate: case SP_coarseRootTurnoverRate:
+    case SP_baseCoarseRootResp: case SP_baseFineRootResp: return true;
+    default: return false;
+  }
+}
+// why row p cannot be analysed, or null: its converted value is neither the file value nor the file value / 365, or only
+// setup reads it
+const char* refusedRow(int p) {
+  switch (p) {
+    case SP_psnTMax: case SP_coarseRootAllocation:
+      return "a derived row (rewritten from the rows it depends on)";
+    case SP_plantWoodInit: case SP_laiInit: case SP_soilInit: case SP_soilWFracInit: case SP_litterInit: case SP_snowInit:
+    case SP_minNInit: case SP_soilOrgNInit: case SP_litterOrgNInit: case SP_plantStorageNInit:
+      return "an initial condition, which only setup reads";
+    case SP_leafOnDay: case SP_leafOffDay: case SP_gddLeafOn: case SP_soilTempLeafOn:
+      return "a phenology threshold (the gddLeafOn row is overloaded by the leaf-on mode)";
+    case SP_fAnoxia: case SP_anaerobicDecompRate:
+      return "a row the conversion clamps";
+    default: return nullptr;
+  }
+}
+// sipnet_enkf_params_check's checks; lo / hi (may be null): the bounds in converted units, by the conversion's own expression
+int paramsCheck(const char* name, int32_t n, const sipnet_enkf_param* params, double* lo, double* hi) {
+  if (n < 0 || n > kMaxPrm) return refuse(name, "n_params must be 0..16");
+  if (n > 0 && !params) return refuse(name, "NULL params with n_params > 0");
+  for (int k = 0; k < n; k++) {
+    const sipnet_enkf_param& q = params[k];
+    const std::string at = "parameter " + std::to_string(k) + ": ";
+    if (q.index < 0 || q.index >= SIPNET_NPARAMS) return refuse(name, at + "index is not a parameter index");
+    const std::string who = at + kParamName[q.index] + " ";
+    if (const char* why = refusedRow(q.index)) return refuse(name, who + "is " + why);
+    for (int e = 0; e < k; e++)
+      if (params[e].index == q.index) return refuse(name, who + "is listed twice");
+    if (!(fabs(q.lo) < INFINITY) || !(fabs(q.hi) < INFINITY)) return refuse(name, who + "has a bound that is not finite");
+    if (!(q.lo < q.hi)) return refuse(name, who + "needs lo < hi");
+    double l = q.lo, h = q.hi;
+    if (rateRow(q.index)) {
+      l /= 365.0;
+      h /= 365.0;
+    }
+    if (lo) lo[k] = l;
+    if (hi) hi[k] = h;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1018,31 +1237,88 @@ int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipne
   int rc = enkfBegin("sipnet_batch_enkf_analysis_sites", b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd,
                      d_inflation, d_site_info, stream, a);
   if (rc) return rc;
-  const int64_t nSites = b->n_sites, M = b->n_members;
-  // the per-chunk launches unless the sites outnumber the CUs four times over (profiles/r08_enkf_sites_time.txt: one
-  // workgroup per site loses or ties at every shape up to 256 sites x 1 024 members -- 0.29 ms against 0.19); big sites or
-  // SIPNET_KOPT_PF_MULTI_LAUNCH: always the launches
-  const bool group = M <= 256 * kMaxGroupChunks && nSites >= 4 * (int64_t)b->numCUs &&
-                     !(b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
-  const size_t ldsBytes = (size_t)a.nv * (size_t)M * sizeof(double);
-  a.useLds = group && ldsBytes <= (size_t)kLdsWork;
-  rc = enkfScratch(b, a, d_site_info, /*workInGlobal=*/!a.useLds, /*perChunk=*/!group, /*withSrc=*/false, 0, nullptr);
+  return enkfSites(b, a, n_obs, elem_is_f32, d_site_info, stream);
+}
+
+int sipnet_enkf_params_check(int32_t n_params, const sipnet_enkf_param* params, double* lo_converted, double* hi_converted) {
+  return paramsCheck("sipnet_enkf_params_check", n_params, params, lo_converted, hi_converted);
+}
+
+int sipnet_batch_enkf_analysis_joint(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                     int32_t n_params, const sipnet_enkf_param* params, const void* const d_planes[3],
+                                     int32_t elem_is_f32, int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
+                                     const double* d_inflation, const double* d_param_inflation, int32_t* d_site_info,
+                                     void* hip_stream) {
+  const char* name = "sipnet_batch_enkf_analysis_joint";
+  hipStream_t stream = (hipStream_t)hip_stream;
+  JointArgs a{};
+  int rc = paramsCheck(name, n_params, params, a.lo, a.hi);
   if (rc) return rc;
-  if (group) {
-    hipLaunchKernelGGL(elem_is_f32 ? enkfSiteKernel<float> : enkfSiteKernel<double>, siteGrid(b), dim3(256),
-                       a.useLds ? ldsBytes : 0, stream, a);
-  } else {
-    const dim3 chunks = chunkGrid(b, a), sites = siteGrid(b);
-    enkfFront(b, a, elem_is_f32, nullptr, stream);
-    for (int i = 0; i < n_obs; i++) {
-      hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, i, 0);
-      hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, i, 0);
-      hipLaunchKernelGGL(enkfPartialKernel, chunks, dim3(256), 0, stream, a, i, 1);
-      hipLaunchKernelGGL(enkfFinalKernel, sites, dim3(256), 0, stream, a, i, 1);
-      hipLaunchKernelGGL(enkfUpdateKernel, chunks, dim3(256), 0, stream, a, i);
+  if (b && d_param_inflation && !d_site_info && !b->pfPeers) {   // the synchronous form: checked before anything is launched
+    rc = useDevice(b);
+    if (rc) return rc;
+    std::vector<double> infl((size_t)b->n_sites);
+    HIP_TRY(hipMemcpyAsync(infl.data(), d_param_inflation, infl.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (size_t s = 0; s < infl.size(); s++)
+      if (!(infl[s] >= 1.0) || !(infl[s] < INFINITY))
+        return refuse(name, "site " + std::to_string(s) + ": bad input (the parameter inflation must be finite and >= 1); "
+                            "nothing was written");
+  }
+  // (enkfBegin fills the arguments the analyses share and leaves the bounds alone)
+  rc = enkfBegin(name, b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream, a);
+  if (rc) return rc;
+  rc = materializeParams(b, stream);   // (every column its own rows: the limits write them)
+  if (rc) return rc;
+  a.prm = b->d_prm;
+  a.prmPitch = b->ncol;
+  a.prmId = nullptr;
+  a.prmOut = b->d_prm;
+  a.prmInfl = d_param_inflation;
+  a.nPool = a.nA;
+  a.nPrm = n_params;
+  a.nA += n_params;
+  a.nv += n_params;
+  a.leaf = a.wood = a.fineRoot = a.opt = a.tmin = -1;
+  for (int k = 0; k < n_params; k++) {
+    const int p = params[k].index;
+    a.prmRow[k] = p;
+    if (p == SP_leafAllocation) a.leaf = k;
+    if (p == SP_woodAllocation) a.wood = k;
+    if (p == SP_fineRootAllocation) a.fineRoot = k;
+    if (p == SP_psnTOpt) a.opt = k;
+    if (p == SP_psnTMin) a.tmin = k;
+  }
+  return enkfSites(b, a, n_obs, elem_is_f32, d_site_info, stream);
+}
+
+int sipnet_batch_get_params(sipnet_batch* b, double* params, int32_t file_units, void* hip_stream) {
+  const char* name = "sipnet_batch_get_params";
+  if (!b || !params) return refuse(name, "a NULL batch or params");
+  int rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  rc = orderBehindBusy(b, stream);
+  if (rc) return rc;
+  rc = flushParams(b, stream);
+  if (rc) return rc;
+  // the rows a column carries: its own, or those of the column its index names (in the bank of a connected filter)
+  const bool indexed = b->prmIndexed;
+  const double* src = indexed && b->d_prmBank ? b->d_prmBank : b->d_prm;
+  const int64_t pitch = indexed && b->d_prmBank ? b->prmBankPitch : b->ncol, ncol = b->ncol;
+  std::vector<double> rows((size_t)pitch * SIPNET_NPARAMS);
+  std::vector<int32_t> id(indexed ? (size_t)ncol : 0);
+  HIP_TRY(hipMemcpyAsync(rows.data(), src, rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (indexed) HIP_TRY(hipMemcpyAsync(id.data(), b->d_prmId, id.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int p = 0; p < SIPNET_NPARAMS; p++) {
+    const bool rate = file_units && rateRow(p);
+    for (int64_t c = 0; c < ncol; c++) {
+      const double v = rows[(size_t)p * pitch + (indexed ? (int64_t)id[c] : c)];
+      params[c * SIPNET_NPARAMS + p] = rate ? v * 365.0 : v;
     }
   }
-  return enkfEnd(b, a, /*perChunk=*/!group, group ? 1 : 0, group ? (int32_t)b->n_sites : 0, stream);
+  return SIPNET_OK;
 }
 
 int sipnet_enkf_local_schedule(int32_t n_sites, int32_t n_obs, const int64_t* nbr_ptr, const int32_t* nbr, const double* rho,
