@@ -752,6 +752,54 @@ int sipnet_batch_enkf_analysis_joint(sipnet_batch *b, int32_t n_obs, const sipne
                                      const double *d_param_inflation, int32_t *d_site_info, void *hip_stream);
 int sipnet_batch_get_params(sipnet_batch *b, double *params, int32_t file_units, void *hip_stream);
 
+/* ---- ensemble Kalman smoother: the window's flux series analysed with the pools ------------------------------------
+ * The update a member's pools receive is linear in the ensemble, so the same update applied to any other per-member
+ * quantity of the forecast window is that quantity's analysis (Evensen & van Leeuwen 2000).  The call is
+ * sipnet_batch_enkf_analysis_joint with series (n_params = 0 and a NULL d_param_inflation: sipnet_batch_enkf_analysis_
+ * sites with series): state, parameters and site_info afterwards are what that call leaves with the same arguments, bit
+ * for bit, on both paths; the series stage adds to the call and changes nothing in it.
+ * A series is a DEVICE array [rows][ld], ld >= ncol, of doubles or floats (elem_is_f32), one value per row and column:
+ * a plane of sipnet_batch_run over the window, one of the three [groups][ncol] arrays of sipnet_batch_run_sums.  series
+ * is a HOST array of n_series descriptors; dst may equal src (in place).
+ * An element of a code-1 site s (n live members L, lambda = inflation[s], the pools' lambda, not the parameters'),
+ * z_j = src[r][s M + j] for j in L read as doubles, gets what the serial filter of sipnet_batch_enkf_analysis_sites
+ * does to an analysed variable whose forecast is z: first z = zbar + lambda (z - zbar) (lambda == 1: unchanged); then for
+ * every non-NaN observation i in index order, with the current h_i, K = cov(z, h_i) / (var(h_i) + R) and
+ * z += K (y - mean(h_i)) - alpha K (h_i - mean(h_i)); all statistics over L with divisor n - 1.  No clipping and no
+ * limits (NEE is signed; a caller who wants GPP >= 0 clips it), and a member that the pool limits keep on its forecast
+ * (site_info[.][3]) is STILL smoothed: its series follow the filter, its pools and parameters do not.
+ * Every other element -- a column that is not live, a site whose code is not 1 -- gets dst = src exactly (untouched in
+ * place, copied otherwise), so dst is always a complete series; columns ncol .. ld of dst are not written; values of
+ * members that are not live never enter a sum (they may be NaN).  Every h is formed before any series is written, so a
+ * series may be smoothed in place even when it is one of d_planes read by a PLANE operator.
+ * The arithmetic: with a_j member j's anomalies of the p used observations' inflated forecast h and
+ * c_z = lambda sum_j (z_j - zbar) a_j / (n - 1), z_a[j] = zbar + lambda (z_j - zbar) + c_z . g + (c_z G) . a_j, where
+ * g [p] and G [p][p] come from the covariance-space chain of sipnet_batch_enkf_analysis_block run on the rows' p x p
+ * covariance.  It equals the member-space update to rounding (tests: 1e-10 of max(|x|, ensemble sd)).  Sums are taken
+ * in one fixed order: a repeated call gives the same bits, in place and out of place give the same bits, and the series
+ * do not depend on the path the pool analysis takes, nor on whether the anomalies are staged in LDS (when
+ * n_obs x M x 8 bytes fit) or read from the scratch block (else, and always under SIPNET_KOPT_PF_MULTI_LAUNCH).
+ * Refusals in addition to the joint call's, SIPNET_ERR_BAD_ARGUMENT before any launch, sipnet_last_error naming the
+ * series: n_series outside 0..SIPNET_ENKF_MAX_SERIES; NULL series with n_series > 0; a NULL src or dst; rows < 1 or
+ * ld < ncol; two series with the same dst; a dst equal to another series' src; more than 4096 members per site when
+ * n_series > 0.  n_series = 0 is the joint call.
+ * Out of scope: series in sipnet_batch_enkf_analysis_local and _block, the node object and the CLI, statistics of the
+ * smoothed series. */
+#define SIPNET_ENKF_MAX_SERIES 8
+typedef struct sipnet_enkf_series {
+  const void *src;      /* DEVICE [rows][ld]: the forecast values */
+  void *dst;            /* DEVICE [rows][ld]: may equal src (in place) */
+  int32_t rows;         /* >= 1 */
+  int32_t elem_is_f32;  /* src and dst alike */
+  int64_t ld;
+} sipnet_enkf_series;   /* 32 bytes */
+int sipnet_batch_enkf_analysis_smooth(sipnet_batch *b, int32_t n_obs, const sipnet_enkf_obs *ops, int32_t analysed_mask,
+                                      int32_t n_params, const sipnet_enkf_param *params,
+                                      const void *const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                      const double *d_obs, const double *d_sd, const double *d_inflation,
+                                      const double *d_param_inflation, int32_t n_series,
+                                      const sipnet_enkf_series *series, int32_t *d_site_info, void *hip_stream);
+
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its
  * range) and known on the device only; RCCL's send / receive sizes are host arguments, so an all-to-all

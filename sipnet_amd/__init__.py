@@ -10,7 +10,7 @@ from ._lib import (KERNEL_AUTO, KERNEL_COOP_HBM, KERNEL_COOP_LDS, KERNEL_COOP_PA
                    KOPT_FULL_STATE, KOPT_NO_REGULAR_TILES, KOPT_ONE_WAVE_PER_SIMD, KOPT_RUNTIME_FLAGS,
                    KOPT_STATS_IN_KERNEL, KOPT_BOUNDED_WAITS, KOPT_WAIT_SELFTEST, KOPT_HOST_PLAN, KOPT_DEVICE_PLAN,
                    KOPT_PF_MULTI_LAUNCH, KOPT_PF_MOVE_PARAMS, PF_VOID_TOTAL)
-from ._lib import (ENKF_MAX_PARAMS, F32_MIXED, F64, NCLIM, NFLAGS, NPARAMS, NREC, NSTATE, RING_SLOTS,
+from ._lib import (ENKF_MAX_PARAMS, ENKF_MAX_SERIES, F32_MIXED, F64, NCLIM, NFLAGS, NPARAMS, NREC, NSTATE, RING_SLOTS,
                    Event, Restart, SipnetError, lib)
 from .config import (DEFAULT_FLAGS, FLAG_NAMES, PARAM_NAMES, POOLS, enkf_param, enkf_plane, enkf_pools, flags_from, read_config)
 from .io import (ClimTable, format_out_header, format_out_row, read_clim, read_events,
@@ -23,7 +23,7 @@ __all__ = [
     "Batch", "EnkfLocalization", "enkf_local_schedule", "enkf_local_rows", "ENKF_BLOCK_MAX_ROWS", "gaspari_cohn", "ClimTable", "Event", "Restart", "SipnetError", "read_restart", "write_restart",
     "check_restart", "lib", "read_clim", "read_params",
     "read_events", "write_out", "write_events_out", "write_debug_logs", "format_out_header", "format_out_row", "read_config",
-    "flags_from", "FLAG_NAMES", "POOLS", "enkf_pools", "enkf_plane", "enkf_param", "ENKF_MAX_PARAMS", "DEFAULT_FLAGS", "PARAM_NAMES", "F64", "F32_MIXED",
+    "flags_from", "FLAG_NAMES", "POOLS", "enkf_pools", "enkf_plane", "enkf_param", "ENKF_MAX_PARAMS", "ENKF_MAX_SERIES", "DEFAULT_FLAGS", "PARAM_NAMES", "F64", "F32_MIXED",
     "KERNEL_AUTO", "KERNEL_ONE_WAVE", "KERNEL_COOP_LDS", "KERNEL_COOP_HBM", "KERNEL_COOP_PAIR", "KERNEL_COOP_QUAD", "KERNEL_COOP_NCYCLE", "KERNEL_COOP_NCYCLE_PAIR", "KERNEL_STRICT",
     "KOPT_ONE_WAVE_PER_SIMD", "KOPT_RUNTIME_FLAGS", "KOPT_FULL_STATE", "KOPT_NO_REGULAR_TILES", "KOPT_STATS_IN_KERNEL", "KOPT_BOUNDED_WAITS", "KOPT_WAIT_SELFTEST", "KOPT_HOST_PLAN", "KOPT_DEVICE_PLAN", "KOPT_PF_MULTI_LAUNCH", "KOPT_PF_MOVE_PARAMS", "PF_VOID_TOTAL",
     "NPARAMS", "NFLAGS", "NCLIM", "NREC", "NSTATE", "RING_SLOTS",

@@ -59,6 +59,14 @@ class EnkfParam(C.Structure):
     _fields_ = [("index", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
 
 
+ENKF_MAX_SERIES = 8   # SIPNET_ENKF_MAX_SERIES
+
+
+class EnkfSeries(C.Structure):
+    """struct sipnet_enkf_series: one series of sipnet_batch_enkf_analysis_smooth (device arrays [rows][ld])"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("elem_is_f32", C.c_int32), ("ld", C.c_int64)]
+
+
 class Event(C.Structure):
     """struct sipnet_event"""
     _fields_ = [("type", C.c_int32), ("year", C.c_int32), ("day", C.c_int32),
@@ -182,6 +190,8 @@ SIGNATURES = {
     "sipnet_enkf_params_check": (C.c_int, [C.c_int32, _P, _P, _P]),
     "sipnet_batch_enkf_analysis_joint": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32,
                                                    C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "sipnet_batch_enkf_analysis_smooth": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32,
+                                                    C.c_int64, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "sipnet_batch_get_params": (C.c_int, [_P, _P, C.c_int32, _P]),
     "sipnet_enkf_local_schedule": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "sipnet_batch_enkf_local_create": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.POINTER(_P)]),

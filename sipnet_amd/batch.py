@@ -400,6 +400,51 @@ class Batch:
             args[10], self._stream()), "enkf_analysis_joint")
         del keep
 
+    def enkf_analysis_smooth(self, obs, sd, operators, analysed, series, params=(), planes=None, inflation=None,
+                             param_inflation=None, info_out=None):
+        """an ensemble Kalman smoother of the window's series (sipnet_batch_enkf_analysis_smooth): enkf_analysis_joint (with
+        params=() enkf_analysis_sites), and the same update applied to per-member series of the forecast window.  series: a
+        list of device tensors [rows][ld] (float64 or float32, unit column stride, ld >= ncol), smoothed in place, or of
+        (src, dst) pairs of the same shape, dtype and pitch; a 3-d tensor (run()'s [3][n_steps][ld] planes, run_sums()'s
+        [3][groups][ncol]) counts as one series per leading index.  At most sa.ENKF_MAX_SERIES.  Live members of analysed
+        sites get the filter's value, everything else dst = src.  Returns the list of dst tensors; the other arguments as
+        enkf_analysis_joint."""
+        from ._lib import EnkfParam, EnkfSeries
+        t = self._torch
+        what = "enkf_analysis_smooth"
+        args, keep = self._enkf_args(what, obs, sd, operators, analysed, planes, inflation, info_out)
+        prm = list(params)
+        arr = (EnkfParam * max(len(prm), 1))(*prm)
+        pinfl = None
+        if param_inflation is not None:
+            pinfl = t.as_tensor(param_inflation, dtype=t.float64).reshape(-1).to(self.device).contiguous()
+            if pinfl.numel() != self.n_sites:
+                raise ValueError(f"{what}: param_inflation needs {self.n_sites} values, got {pinfl.numel()}")
+        pairs = []
+        for item in series:
+            src, dst = item if isinstance(item, (tuple, list)) else (item, item)
+            if src.dim() == 3 and dst.dim() == 3 and src.shape[0] == dst.shape[0]:
+                pairs += [(src[k], dst[k]) for k in range(src.shape[0])]
+            else:
+                pairs.append((src, dst))
+        desc = (EnkfSeries * max(len(pairs), 1))()
+        for k, (src, dst) in enumerate(pairs):
+            for x in (src, dst):
+                if not x.is_cuda or x.dim() != 2 or x.dtype not in (t.float32, t.float64) or x.stride(1) != 1:
+                    raise ValueError(f"{what}: series {k} must be a [rows][ld] float32 / float64 device tensor with unit "
+                                     "column stride")
+            if src.dtype != dst.dtype or src.shape[0] != dst.shape[0] or src.stride(0) != dst.stride(0):
+                raise ValueError(f"{what}: series {k}: src and dst differ in dtype, rows or row pitch")
+            if src.shape[1] < self.ncol:
+                raise ValueError(f"{what}: series {k} has {src.shape[1]} columns, the batch {self.ncol}")
+            ld = src.stride(0) if src.shape[0] > 1 else src.shape[1]
+            desc[k] = EnkfSeries(src.data_ptr(), dst.data_ptr(), src.shape[0], int(src.dtype == t.float32), ld)
+        check(self.L.sipnet_batch_enkf_analysis_smooth(
+            self.h, *args[:3], len(prm), arr, *args[3:10], C.c_void_p(pinfl.data_ptr()) if pinfl is not None else None,
+            len(pairs), desc, args[10], self._stream()), what)
+        del keep
+        return [dst for _, dst in pairs]
+
     def get_params(self, file_units=False):
         """the parameters every column carries (sipnet_batch_get_params) -> [ncol][80]: the converted rows as the kernels
         read them, or with file_units the nine per-year rates back in file units (x 365)"""

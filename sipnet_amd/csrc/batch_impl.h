@@ -192,6 +192,9 @@ struct sipnet_batch {
   // statistics, the block-local matrices, counts and codes), grow-only
   void* d_enkf = nullptr;
   size_t enkfBytes = 0;
+  // sipnet_batch_enkf_analysis_smooth's series stage: a block of its own (the h, their anomalies, g and G), grow-only
+  void* d_smooth = nullptr;
+  size_t smoothBytes = 0;
 };
 int flushParams(sipnet_batch* b, hipStream_t stream);   // engine.hip: upload + convert what set_params left pending
 int materializeParams(sipnet_batch* b, hipStream_t stream);   // pf.hip: d_prm back into column order (no-op unless prmIndexed)

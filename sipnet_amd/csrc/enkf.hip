@@ -18,6 +18,8 @@
 // block (enkfScratch), the front of the per-chunk launches (enkfFront: load, codes, reach, inflation), a middle of its own, and
 // the tail (enkfEnd: limits, info, bookkeeping).  The per-site call may instead run its one-workgroup-per-site kernel between
 // scratch and tail.
+// sipnet_batch_enkf_analysis_smooth is the joint call around a series stage of its own (below: enkfSmoothPrepKernel,
+// enkfSmoothKernel): the update of the pools applied to the window's flux series, on a scratch block of its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -875,6 +877,227 @@ __global__ __launch_bounds__(kBlockThreads) void enkfBlockKernel(EnkfArgs a, con
     }
 }
 
+// ---- the smoother of a window's series (sipnet_batch_enkf_analysis_smooth) ------------------------------------------------
+// The serial update is linear in a variable's forecast covariance with the used observations' inflated forecast h (the p <= 16
+// rows).  With a_j member j's row anomalies (0 for a member that is not live) and c_z = lambda sum_j (z_j - zbar) a_j / (n - 1),
+// a series element z gets  z_a[j] = zbar + lambda (z_j - zbar) + c_z . g + (c_z G) . a_j.  g [p] and G [p][p] come from the
+// covariance-space chain of the block-local analysis, run on the rows' p x p covariance with p unit covariance vectors carried
+// as "pool rows": their mean shifts are g, their transforms the rows of G.  The rows come from enkfFront, run on a working
+// copy of their own that holds nothing but the h; enkfSmoothPrepKernel (a workgroup per site) leaves a, g, G, p and n;
+// enkfSmoothKernel (the hot path: a workgroup per site and run of rows) touches every element once.
+constexpr int kMaxSeries = SIPNET_ENKF_MAX_SERIES;
+constexpr int kMetaG = kMaxObs, kMetaP = kMaxObs + kMaxObs * kMaxObs, kMetaN = kMetaP + 1, kMeta = kMetaP + 8;   // doubles per site
+
+__global__ __launch_bounds__(256) void enkfSmoothPrepKernel(JointArgs a, double* meta) {
+  __shared__ GroupLds g;
+  __shared__ double sC[kMaxObs][kMaxObs + 1], sEc[kMaxObs][kMaxObs + 1], sT[kMaxObs][kMaxObs + 1], sMean[kMaxObs];
+  __shared__ int sUsed[kMaxObs], sP;
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x, nCh = a.nCh;
+  double* m = meta + (int64_t)s * kMeta;
+  if (splitCode(a, s) != kAnalysed) {
+    if (tid == 0) m[kMetaP] = m[kMetaN] = 0.0;
+    return;
+  }
+  if (tid == 0) {
+    int p = 0;
+    for (int i = 0; i < a.nObs; i++) {
+      const double y = a.obs[(int64_t)s * a.nObs + i];
+      if (y == y) sUsed[p++] = i;
+    }
+    sP = p;
+  }
+  __syncthreads();
+  const int p = sP;
+  const double nd = (double)a.site[2 * (int64_t)s + 1];
+  double* H = a.work + (int64_t)s * a.M;   // row i of member j: H[i ncol + j]; the anomalies of row w go to H[w ncol + j], w <= used[w]
+  siteSums(g, p, nCh, [&](int64_t j, int q) { return liveAt(a, s, j) ? H[(int64_t)sUsed[q] * a.ncol + j] : 0.0; });
+  if (tid < p) sMean[tid] = g.tot[tid] / nd;
+  __syncthreads();
+  for (int64_t j = tid; j < a.M; j += 256) {   // (a member is its own thread's: row w is written after row used[w] >= w was read)
+    const bool live = liveAt(a, s, j);
+    for (int w = 0; w < p; w++) {
+      const double v = live ? H[(int64_t)sUsed[w] * a.ncol + j] - sMean[w] : 0.0;
+      H[(int64_t)w * a.ncol + j] = v;
+    }
+  }
+  __syncthreads();
+  for (int l = 0; l < p; l++) {   // the rows' covariance, row l from the diagonal on
+    siteSums(g, p - l, nCh, [&](int64_t j, int q) {
+      return j < a.M ? H[(int64_t)l * a.ncol + j] * H[(int64_t)(l + q) * a.ncol + j] : 0.0;
+    });
+    if (tid < p - l) sC[l][l + tid] = sC[l + tid][l] = g.tot[tid] / (nd - 1.0);
+    __syncthreads();
+  }
+  // the chain: thread (k, w) owns entry [k][w] of C (the rows' covariance), Ec (the unit vectors' covariance with the rows),
+  // T (row k = sum_w T[k][w] a_w) and G; w = 0 also row k's mean and g[k]
+  const int k = tid >> 4, w = tid & 15;
+  const bool in = k < p && w < p;
+  double c = in ? sC[k][w] : 0.0, ec = k == w ? 1.0 : 0.0, tt = ec, et = 0.0, shift = 0.0, mean = k < p ? sMean[k] : 0.0;
+  __syncthreads();
+  for (int l = 0; l < p; l++) {
+    sC[k][w] = c; sEc[k][w] = ec; sT[k][w] = tt;
+    if (w == 0) sMean[k] = mean;
+    __syncthreads();
+    const int i = sUsed[l];
+    const double e = a.sd[(int64_t)s * a.nObs + i], R = e * e, D = sC[l][l] + R, alpha = 1.0 / (1.0 + sqrt(R / D));
+    const double innov = a.obs[(int64_t)s * a.nObs + i] - sMean[l];
+    const double Kz = sEc[k][l] / D, K = sC[k][l] / D, Tl = sT[l][w], Cl = sC[l][w];
+    et -= (alpha * Kz) * Tl;
+    ec -= Kz * Cl;
+    c -= K * Cl;
+    shift += Kz * innov;
+    if (k > l) {
+      tt -= (alpha * K) * Tl;
+      mean += K * innov;
+    }
+    __syncthreads();
+  }
+  if (w == 0) m[k] = in ? shift : 0.0;
+  m[kMetaG + tid] = in ? et : 0.0;
+  if (tid == 0) {
+    m[kMetaP] = (double)p;
+    m[kMetaN] = nd;
+  }
+}
+
+struct SmoothSeries {
+  const void* src;
+  void* dst;
+  int64_t ld;
+  int32_t rows, f32, firstBlock, pad;
+};
+struct SmoothArgs {
+  SmoothSeries ser[kMaxSeries];
+  int32_t nSeries, run;                    // rows a workgroup owns
+  const double* anom;                      // [nObs][ncol]: row w of site s's member j at anom[w ncol + s M + j]
+  const double* meta;                      // [n_sites][kMeta]
+  const int32_t* site;                     // [n_sites][2] code, live members
+  const double* infl;
+  const int32_t* siteStatus;
+  const double* status;                    // the state's status row
+  int64_t ncol, M;
+};
+__device__ __forceinline__ double seriesLoad(const SmoothSeries& q, int64_t at) {
+  return q.f32 ? (double)((const float*)q.src)[at] : ((const double*)q.src)[at];
+}
+__device__ __forceinline__ void seriesStore(const SmoothSeries& q, int64_t at, double v) {
+  if (q.f32) ((float*)q.dst)[at] = (float)v;
+  else ((double*)q.dst)[at] = v;
+}
+__device__ __forceinline__ void seriesCopy(const SmoothSeries& q, int64_t at) {   // (the bits, whatever they are)
+  if (q.f32) ((uint32_t*)q.dst)[at] = ((const uint32_t*)q.src)[at];
+  else ((uint64_t*)q.dst)[at] = ((const uint64_t*)q.src)[at];
+}
+
+// kLds: the site's anomalies staged in LDS ([p][M]); else read from the scratch block.  A row is reduced by a team of kWaves
+// waves: one wave (sites of at most 1 024 members: the four waves of a workgroup each take a row of their own, and a row costs
+// no barrier) or all sixteen of a 1 024-thread workgroup.  kCh: members a thread holds, 64 kWaves apart.  Every sum in one
+// order: a thread's members in order, the wave's butterfly, the team's waves in order; the team is a function of M alone.
+template <bool kLds, int kWaves, int kCh>
+__global__ __launch_bounds__(kWaves == 1 ? 256 : 64 * kWaves) void enkfSmoothKernel(SmoothArgs a) {
+  constexpr int kThreads = kWaves == 1 ? 256 : 64 * kWaves, kTeam = 64 * kWaves, kTeams = kThreads / kTeam;
+  extern __shared__ __attribute__((aligned(16))) double smA[];
+  __shared__ double part[kWaves][kMaxObs + 1], tz[kMaxObs + 1], sg[kMaxObs], sG[kMaxObs][kMaxObs];
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, team = tid / kTeam, tt = tid % kTeam;
+  SmoothSeries q = a.ser[0];   // (the series this workgroup's rows belong to; constant indices: the arguments stay in registers)
+#pragma unroll
+  for (int e = 1; e < kMaxSeries; e++)
+    if (e < a.nSeries && (int)blockIdx.y >= a.ser[e].firstBlock) q = a.ser[e];
+  const int r0 = ((int)blockIdx.y - q.firstBlock) * a.run, r1 = r0 + a.run < q.rows ? r0 + a.run : q.rows;
+  const int64_t M = a.M, col0 = (int64_t)s * M;
+  if (a.site[2 * (int64_t)s] != kAnalysed) {
+    if (q.dst != q.src)
+      for (int r = r0; r < r1; r++)
+        for (int64_t j = tid; j < M; j += kThreads) seriesCopy(q, (int64_t)r * q.ld + col0 + j);
+    return;
+  }
+  const double* m = a.meta + (int64_t)s * kMeta;
+  const int p = (int)m[kMetaP];
+  const double nd = m[kMetaN], lam = a.infl ? a.infl[s] : 1.0;
+  bool live[kCh], mine[kCh];
+#pragma unroll
+  for (int c = 0; c < kCh; c++) {
+    const int64_t j = (int64_t)c * kTeam + tt;
+    mine[c] = j < M;
+    live[c] = mine[c] && a.siteStatus[s] == 0 && a.status[col0 + j] == 0.0;
+  }
+  for (int k = tid; k < kMaxObs * kMaxObs; k += kThreads) sG[k >> 4][k & 15] = m[kMetaG + k];
+  if (tid < kMaxObs) sg[tid] = m[tid];
+  if constexpr (kLds)
+    for (int w = 0; w < p; w++)
+      for (int64_t j = tid; j < M; j += kThreads) smA[(int64_t)w * M + j] = a.anom[(int64_t)w * a.ncol + col0 + j];
+  __syncthreads();
+  auto A = [&](int w, int c) -> double {   // (only for a member of the site: mine[c])
+    const int64_t j = (int64_t)c * kTeam + tt;
+    if constexpr (kLds) return smA[(int64_t)w * M + j];
+    else return a.anom[(int64_t)w * a.ncol + col0 + j];
+  };
+  for (int r = r0 + team; r < r1; r += kTeams) {   // (kWaves > 1: one team, the workgroup's barriers are uniform)
+    const int64_t at0 = (int64_t)r * q.ld + col0 + tt;
+    double z[kCh], acc = 0.0;
+#pragma unroll
+    for (int c = 0; c < kCh; c++) {
+      z[c] = live[c] ? seriesLoad(q, at0 + c * kTeam) : 0.0;
+      acc += z[c];
+    }
+    acc = waveSum(acc);
+    if constexpr (kWaves > 1) {
+      if (lane == 0) part[wave][kMaxObs] = acc;
+      __syncthreads();
+      acc = part[0][kMaxObs];
+      for (int v = 1; v < kWaves; v++) acc += part[v][kMaxObs];
+    }
+    const double zbar = acc / nd;
+    double d[kCh];
+#pragma unroll
+    for (int c = 0; c < kCh; c++) d[c] = live[c] ? z[c] - zbar : 0.0;
+    double t = 0.0;   // thread w < p of the team: (c_z G)[w]; thread p: c_z . g
+    for (int w = 0; w < p; w++) {
+      double cs = 0.0;
+#pragma unroll
+      for (int c = 0; c < kCh; c++)
+        if (mine[c]) cs = fma(d[c], A(w, c), cs);
+      cs = waveSum(cs);
+      if constexpr (kWaves > 1) {
+        if (lane == 0) part[wave][w] = cs;
+      } else {
+        const double cz = lam * (cs / (nd - 1.0));
+        t = fma(cz, lane < p ? sG[w][lane] : sg[w], t);
+      }
+    }
+    if constexpr (kWaves > 1) {
+      __syncthreads();
+      if (tid <= p) {
+        for (int k = 0; k < p; k++) {
+          double cs = part[0][k];
+          for (int v = 1; v < kWaves; v++) cs += part[v][k];
+          const double cz = lam * (cs / (nd - 1.0));
+          t = fma(cz, tid < p ? sG[k][tid] : sg[k], t);
+        }
+        tz[tid] = t;
+      }
+      __syncthreads();
+    }
+    double mv[kCh] = {};
+    for (int w = 0; w < p; w++) {
+      const double tw = kWaves > 1 ? tz[w] : __shfl(t, w, 64);
+#pragma unroll
+      for (int c = 0; c < kCh; c++)
+        if (mine[c]) mv[c] = fma(tw, A(w, c), mv[c]);
+    }
+    const double shift = kWaves > 1 ? tz[p] : __shfl(t, p, 64);
+#pragma unroll
+    for (int c = 0; c < kCh; c++) {
+      if (live[c]) {
+        const double base = lam == 1.0 ? z[c] : fma(lam, d[c], zbar);
+        seriesStore(q, at0 + c * kTeam, (base + shift) + mv[c]);
+      } else if (mine[c] && q.dst != q.src) {
+        seriesCopy(q, at0 + c * kTeam);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // a localization: the level-ordered table of (slot, target) pairs and the in-neighbour lists, on the batch's device
@@ -896,6 +1119,9 @@ void enkfRelease(sipnet_batch* b) {
   if (b->d_enkf) (void)hipFree(b->d_enkf);
   b->d_enkf = nullptr;
   b->enkfBytes = 0;
+  if (b->d_smooth) (void)hipFree(b->d_smooth);
+  b->d_smooth = nullptr;
+  b->smoothBytes = 0;
 }
 
 namespace {
@@ -1004,7 +1230,9 @@ int enkfScratch(sipnet_batch* b, EnkfArgs& a, int32_t* d_site_info, bool workInG
   if (b->enkfBytes < bytes) {
     int rc = waitIdle(b);   // (the old block may still be read by a launch in flight)
     if (rc) return rc;
-    enkfRelease(b);
+    if (b->d_enkf) (void)hipFree(b->d_enkf);   // (this block alone: the smoother's may be in use by this very call)
+    b->d_enkf = nullptr;
+    b->enkfBytes = 0;
     HIP_TRY(hipMalloc(&b->d_enkf, bytes));
     b->enkfBytes = bytes;
   }
@@ -1224,36 +1452,144 @@ int paramsCheck(const char* name, int32_t n, const sipnet_enkf_param* params, do
   return 0;
 }
 
-}  // namespace
 
-extern "C" {
-
-int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
-                                     const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
-                                     const double* d_obs, const double* d_sd, const double* d_inflation,
-                                     int32_t* d_site_info, void* hip_stream) {
-  hipStream_t stream = (hipStream_t)hip_stream;
-  EnkfArgs a;
-  int rc = enkfBegin("sipnet_batch_enkf_analysis_sites", b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd,
-                     d_inflation, d_site_info, stream, a);
-  if (rc) return rc;
-  return enkfSites(b, a, n_obs, elem_is_f32, d_site_info, stream);
+// ---- the smoother's host side ----------------------------------------------------------------------------------------------
+// the refusals of the series, before any launch
+int smoothChecks(const char* name, const sipnet_batch* b, int32_t nSeries, const sipnet_enkf_series* series) {
+  if (nSeries < 0 || nSeries > kMaxSeries) return refuse(name, "n_series must be 0.." + std::to_string(kMaxSeries));
+  if (nSeries > 0 && !series) return refuse(name, "NULL series with n_series > 0");
+  if (nSeries > 0 && b->n_members > 256 * kMaxGroupChunks) return refuse(name, "series need at most 4096 members per site");
+  for (int k = 0; k < nSeries; k++) {
+    const sipnet_enkf_series& q = series[k];
+    const std::string at = "series " + std::to_string(k) + ": ";
+    if (!q.src || !q.dst) return refuse(name, at + "a NULL src or dst");
+    if (q.rows < 1) return refuse(name, at + "rows must be >= 1");
+    if (q.ld < b->ncol) return refuse(name, at + "ld must be >= ncol");
+    for (int e = 0; e < nSeries; e++) {
+      if (e < k && series[e].dst == q.dst) return refuse(name, at + "its dst is also the dst of series " + std::to_string(e));
+      if (e != k && series[e].src == q.dst) return refuse(name, at + "its dst is the src of series " + std::to_string(e));
+    }
+  }
+  return 0;
 }
 
-int sipnet_enkf_params_check(int32_t n_params, const sipnet_enkf_param* params, double* lo_converted, double* hi_converted) {
-  return paramsCheck("sipnet_enkf_params_check", n_params, params, lo_converted, hi_converted);
+// What the series stage keeps between its two halves.  The first half (smoothFront, before the pool analysis: it reads the
+// forecast state and planes) forms the inflated h by enkfFront on a working copy of the stage's own and reduces them to a, g
+// and G; the second (smoothSeries, after it: a series may be a plane the pool analysis reads) smooths the series.  The stage
+// has its own scratch block, so the pool analysis runs on exactly what it runs on without series.
+struct SmoothStage {
+  SmoothArgs k;
+  bool useLds = false;
+  size_t ldsBytes = 0;
+  int32_t blocks = 0;
+};
+// the kernel of a site of M members: teams of one wave up to 1 024 members (kCh = members a lane holds), else sixteen waves
+template <bool kLds>
+const void* smoothKernelOf(int64_t M) {
+  if (M <= 64) return (const void*)enkfSmoothKernel<kLds, 1, 1>;
+  if (M <= 128) return (const void*)enkfSmoothKernel<kLds, 1, 2>;
+  if (M <= 256) return (const void*)enkfSmoothKernel<kLds, 1, 4>;
+  if (M <= 512) return (const void*)enkfSmoothKernel<kLds, 1, 8>;
+  if (M <= 1024) return (const void*)enkfSmoothKernel<kLds, 1, 16>;
+  if (M <= 2048) return (const void*)enkfSmoothKernel<kLds, 16, 2>;
+  return (const void*)enkfSmoothKernel<kLds, 16, 4>;
 }
 
-int sipnet_batch_enkf_analysis_joint(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
-                                     int32_t n_params, const sipnet_enkf_param* params, const void* const d_planes[3],
-                                     int32_t elem_is_f32, int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
-                                     const double* d_inflation, const double* d_param_inflation, int32_t* d_site_info,
-                                     void* hip_stream) {
-  const char* name = "sipnet_batch_enkf_analysis_joint";
-  hipStream_t stream = (hipStream_t)hip_stream;
+int smoothFront(sipnet_batch* b, const JointArgs& joint, int32_t elem_is_f32, int32_t nSeries, const sipnet_enkf_series* series,
+                hipStream_t stream, SmoothStage& st) {
+  const size_t nSites = (size_t)b->n_sites, ncol = (size_t)b->ncol;
+  JointArgs a = joint;   // the h alone: no analysed pool, no analysed parameter (the codes still check both lambdas)
+  a.nPool = a.nPrm = a.nA = 0;
+  a.nv = a.nObs;
+  a.useLds = 0;
+  a.info = nullptr;
+  a.src = nullptr;
+  // the stage's block: the h, then their anomalies [n_obs][ncol] | part | stat | a site's g, G, p, n | cnt | site
+  constexpr size_t cap = JointArgs::kCap;
+  const size_t nWork = (size_t)a.nObs * ncol, nCnt = nSites * (size_t)a.nCh, nPart = nCnt * cap, nStat = nSites * 3 * cap,
+               nMeta = nSites * kMeta;
+  const size_t bytes = (nWork + nPart + nStat + nMeta) * sizeof(double) + (nCnt + 2 * nSites) * sizeof(int32_t);
+  if (b->smoothBytes < bytes) {
+    int rc = waitIdle(b);   // (the old block may still be read by a launch in flight)
+    if (rc) return rc;
+    if (b->d_smooth) HIP_TRY(hipFree(b->d_smooth));
+    b->d_smooth = nullptr;
+    b->smoothBytes = 0;
+    HIP_TRY(hipMalloc(&b->d_smooth, bytes));
+    b->smoothBytes = bytes;
+  }
+  a.work = (double*)b->d_smooth;
+  a.part = a.work + nWork;
+  a.stat = a.part + nPart;
+  double* meta = a.stat + nStat;
+  a.cnt = (int32_t*)(meta + nMeta);
+  a.kept = a.cnt;   // (never written: the stage has no limits)
+  a.site = a.cnt + nCnt;
+
+  SmoothArgs& k = st.k;
+  k = SmoothArgs{};
+  k.nSeries = nSeries;
+  int64_t totalRows = 0;
+  for (int e = 0; e < nSeries; e++) totalRows += series[e].rows;
+  // rows per workgroup: at least 16 (staging a site's anomalies costs about p / 2 rows' traffic, and a workgroup of one-wave
+  // teams has four rows in flight), more once that still leaves eight workgroups per CU
+  const int64_t want = totalRows * (int64_t)nSites / (8 * (int64_t)std::max(b->numCUs, 1));
+  k.run = (int32_t)std::min<int64_t>(64, std::max<int64_t>(16, want));
+  int64_t blocks = 0;
+  for (int e = 0; e < nSeries; e++) {
+    k.ser[e] = SmoothSeries{series[e].src, series[e].dst, series[e].ld, series[e].rows, series[e].elem_is_f32 ? 1 : 0, (int32_t)blocks, 0};
+    blocks += (series[e].rows + k.run - 1) / k.run;
+  }
+  if (blocks > 65535) return refuse("sipnet_batch_enkf_analysis_smooth", "the series have too many rows for one launch");
+  st.blocks = (int32_t)blocks;
+  k.anom = a.work;
+  k.meta = meta;
+  k.site = a.site;
+  k.infl = a.infl;
+  k.siteStatus = a.siteStatus;
+  k.status = a.state + (int64_t)ST_status * a.ncol;
+  k.ncol = a.ncol;
+  k.M = a.M;
+  // the anomalies in LDS when [n_obs][M] fits beside the kernel's tables (SIPNET_KOPT_PF_MULTI_LAUNCH: always from scratch)
+  st.ldsBytes = (size_t)a.nObs * (size_t)a.M * sizeof(double);
+  st.useLds = !(b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
+  if (st.useLds) {
+    int ldsMax = 0;
+    hipFuncAttributes attr;
+    const void* kernel = smoothKernelOf<true>(a.M);
+    HIP_TRY(hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, b->device));
+    HIP_TRY(hipFuncGetAttributes(&attr, kernel));
+    if (st.ldsBytes + attr.sharedSizeBytes > (size_t)ldsMax) {
+      st.useLds = false;
+    } else if (st.ldsBytes + attr.sharedSizeBytes > 48 * 1024 &&
+               hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st.ldsBytes) != hipSuccess) {
+      (void)hipGetLastError();
+      st.useLds = false;
+    }
+  }
+  enkfFront(b, a, elem_is_f32, nullptr, stream);
+  hipLaunchKernelGGL(enkfSmoothPrepKernel, siteGrid(b), dim3(256), 0, stream, a, meta);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int smoothSeries(sipnet_batch* b, const SmoothStage& st, hipStream_t stream) {
+  const dim3 grid((unsigned)b->n_sites, (unsigned)st.blocks);
+  void* args[] = {(void*)&st.k};
+  const void* kernel = st.useLds ? smoothKernelOf<true>(st.k.M) : smoothKernelOf<false>(st.k.M);
+  HIP_TRY(hipLaunchKernel(kernel, grid, dim3(st.k.M <= 1024 ? 256 : 1024), args, st.useLds ? st.ldsBytes : 0, stream));
+  return markBusy(b, stream);
+}
+
+// sipnet_batch_enkf_analysis_joint, and with series sipnet_batch_enkf_analysis_smooth
+int jointCall(const char* name, sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask, int32_t n_params,
+              const sipnet_enkf_param* params, const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+              const double* d_obs, const double* d_sd, const double* d_inflation, const double* d_param_inflation,
+              int32_t n_series, const sipnet_enkf_series* series, int32_t* d_site_info, hipStream_t stream) {
   JointArgs a{};
   int rc = paramsCheck(name, n_params, params, a.lo, a.hi);
   if (rc) return rc;
+  if (b && (rc = smoothChecks(name, b, n_series, series))) return rc;
   if (b && d_param_inflation && !d_site_info && !b->pfPeers) {   // the synchronous form: checked before anything is launched
     rc = useDevice(b);
     if (rc) return rc;
@@ -1289,7 +1625,51 @@ int sipnet_batch_enkf_analysis_joint(sipnet_batch* b, int32_t n_obs, const sipne
     if (p == SP_psnTOpt) a.opt = k;
     if (p == SP_psnTMin) a.tmin = k;
   }
+  if (n_series == 0) return enkfSites(b, a, n_obs, elem_is_f32, d_site_info, stream);
+  SmoothStage st;
+  rc = smoothFront(b, a, elem_is_f32, n_series, series, stream, st);
+  if (rc) return rc;
+  rc = enkfSites(b, a, n_obs, elem_is_f32, d_site_info, stream);
+  if (rc) return rc;
+  return smoothSeries(b, st, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sipnet_batch_enkf_analysis_sites(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                     const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                     const double* d_obs, const double* d_sd, const double* d_inflation,
+                                     int32_t* d_site_info, void* hip_stream) {
+  hipStream_t stream = (hipStream_t)hip_stream;
+  EnkfArgs a;
+  int rc = enkfBegin("sipnet_batch_enkf_analysis_sites", b, n_obs, ops, analysed_mask, d_planes, n_steps, ld, d_obs, d_sd,
+                     d_inflation, d_site_info, stream, a);
+  if (rc) return rc;
   return enkfSites(b, a, n_obs, elem_is_f32, d_site_info, stream);
+}
+
+int sipnet_enkf_params_check(int32_t n_params, const sipnet_enkf_param* params, double* lo_converted, double* hi_converted) {
+  return paramsCheck("sipnet_enkf_params_check", n_params, params, lo_converted, hi_converted);
+}
+
+int sipnet_batch_enkf_analysis_joint(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                     int32_t n_params, const sipnet_enkf_param* params, const void* const d_planes[3],
+                                     int32_t elem_is_f32, int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
+                                     const double* d_inflation, const double* d_param_inflation, int32_t* d_site_info,
+                                     void* hip_stream) {
+  return jointCall("sipnet_batch_enkf_analysis_joint", b, n_obs, ops, analysed_mask, n_params, params, d_planes, elem_is_f32, n_steps,
+                   ld, d_obs, d_sd, d_inflation, d_param_inflation, 0, nullptr, d_site_info, (hipStream_t)hip_stream);
+}
+
+int sipnet_batch_enkf_analysis_smooth(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                      int32_t n_params, const sipnet_enkf_param* params, const void* const d_planes[3],
+                                      int32_t elem_is_f32, int32_t n_steps, int64_t ld, const double* d_obs, const double* d_sd,
+                                      const double* d_inflation, const double* d_param_inflation, int32_t n_series,
+                                      const sipnet_enkf_series* series, int32_t* d_site_info, void* hip_stream) {
+  return jointCall("sipnet_batch_enkf_analysis_smooth", b, n_obs, ops, analysed_mask, n_params, params, d_planes, elem_is_f32, n_steps,
+                   ld, d_obs, d_sd, d_inflation, d_param_inflation, n_series, series, d_site_info, (hipStream_t)hip_stream);
 }
 
 int sipnet_batch_get_params(sipnet_batch* b, double* params, int32_t file_units, void* hip_stream) {
