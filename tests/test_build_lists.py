@@ -20,12 +20,18 @@ def test_every_source_is_built_and_every_step_kernel_file_is_hashed():
             assert "$(HERE)" + f.rsplit(".", 1)[0] + ".o" in objs, f + " has no object in the Makefile's OBJS"
     hdrs = re.search(r"^HDRS := (.*?)\n\n", mk, re.M | re.S).group(1)
     for f in sorted(os.listdir(CSRC)):
-        if f.endswith(".inc") and not f.startswith("coop_"):      # (coop_*.inc: a wildcard)
+        if f.endswith(".inc") and not f.startswith(("coop_", "enkf_")):      # (coop_*.inc, enkf_*.inc: wildcards)
             assert f in hdrs, f + " is not a prerequisite of the objects"
+    assert "$(wildcard $(HERE)coop_*.inc)" in hdrs and "$(wildcard $(HERE)enkf_*.inc)" in hdrs
     lib = open(os.path.join(helpers.REPO, "sipnet_amd", "_lib.py")).read()
     hashed = re.search(r"def kernel_source_sha16\(\):.*?for name in \((.*?)\):", lib, re.S).group(1)
+    # (enkf_*.inc are the parts of enkf.hip, a filter source around the step kernels: included there, and like it not hashed)
+    enkf = open(os.path.join(CSRC, "enkf.hip")).read()
     for f in sorted(os.listdir(CSRC)):
-        if f.endswith(".inc") or f in ("step_kernel.hip", "step_fast.hip", "step_coop.hip", "step_kernel.h", "fast_math.h"):
+        if f.endswith(".inc") and f.startswith("enkf_"):
+            assert '#include "%s"' % f in enkf, f + " is not included by enkf.hip"
+            assert '"%s"' % f not in hashed, f + " is no step kernel source"
+        elif f.endswith(".inc") or f in ("step_kernel.hip", "step_fast.hip", "step_coop.hip", "step_kernel.h", "fast_math.h"):
             assert '"%s"' % f in hashed, f + " is not in kernel_source_sha16's list"
     # (step_coop_bounded.hip / step_coop_sums.hip / step_fast_sums.hip are two-line wrappers around hashed sources)
     for f in ("step_coop_bounded.hip", "step_coop_sums.hip", "step_fast_sums.hip"):
