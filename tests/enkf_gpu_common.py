@@ -79,19 +79,20 @@ def bits(x):
     return np.ascontiguousarray(x).view(np.uint64)
 
 
-def within(got, want, fc, n_sites, slots=SLOTS):
-    """|got - want| <= 1e-10 max(|x|, the site's ensemble sd) per analysed pool; the largest ratio is printed first"""
+def within(got, want, fc, n_sites, slots=SLOTS, bound=1e-10):
+    """|got - want| <= bound (1e-10) max(|x|, the site's ensemble sd) per analysed pool; the largest ratio is printed first"""
     M = got.shape[0] // n_sites
     worst = 0.0
     for s in range(n_sites):
         sl = slice(s * M, (s + 1) * M)
         scale = np.maximum(np.abs(want[sl][:, slots]), fc[sl][:, slots].std(0) + 1e-300)
         worst = max(worst, float((np.abs(got[sl][:, slots] - want[sl][:, slots]) / scale).max()))
-    print(f"largest |got - want| / max(|x|, site ensemble sd) over {n_sites} sites: {worst:.3e} (bound 1e-10)")
+    print(f"largest |got - want| / max(|x|, site ensemble sd) over {n_sites} sites: {worst:.3e} (bound {bound:g})")
     for s in range(n_sites):
         sl = slice(s * M, (s + 1) * M)
         scale = np.maximum(np.abs(want[sl][:, slots]), fc[sl][:, slots].std(0) + 1e-300)
-        assert (np.abs(got[sl][:, slots] - want[sl][:, slots]) <= 1e-10 * scale).all(), s
+        assert (np.abs(got[sl][:, slots] - want[sl][:, slots]) <= bound * scale).all(), s
+    return worst
 
 
 def forecast(base, n_sites, M, prec, steps=96, seed=1, of=None):
@@ -100,6 +101,18 @@ def forecast(base, n_sites, M, prec, steps=96, seed=1, of=None):
     b = sites_batch(members, n_sites, prec)
     planes, _ = b.run(0, steps)
     return b, planes
+
+
+def crafted(base, n_sites, M, prec, pools, dead=()):
+    """a batch whose pools are given, not forecast: set up from perturbed parameters, its state read, slots 0..12 of every
+    column overwritten with pools [n_sites * M][13], the columns `dead` given a non-zero status, and written back
+    -> (batch, the state it now holds).  No run() is needed before an analysis."""
+    b = sites_batch(synth.perturbed_params(base, n_sites * M, seed=1), n_sites, prec)
+    st = b.get_state()
+    st[:, :13] = pools
+    st[list(dead), 29] = 3.0
+    b.set_state(st)
+    return b, b.get_state()
 
 
 def grid(n_sites, far=()):
