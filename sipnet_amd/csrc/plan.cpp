@@ -3,6 +3,7 @@
 
 #include <cstring>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 
@@ -112,8 +113,12 @@ void fillFastRec(const StepRec& s, const RingOp* ops, bool tsoilSame, int phenMo
 }
 
 // the narrow fields of an fp32-mixed batch's records (plan.h): float in the low word, quiet-NaN tag in the high one
+// A value too small for a normal float keeps its sign class: +-FLT_MIN instead of a zero (or a denormal the flux arithmetic may
+// flush), because the fp32 kernels compare the narrowed tsoil with a member's frozenSoilThreshold -- a soil at -1e-300 C is
+// frozen for a threshold of 0, a soil at -0.0f is not.
 double narrowSlot(double v) {
-  const float f = (float)v;   // round to nearest even, as v_cvt_f32_f64 does
+  float f = (float)v;   // round to nearest even, as v_cvt_f32_f64 does
+  if (v != 0.0 && std::fabs(f) < FLT_MIN) f = v < 0.0 ? -FLT_MIN : FLT_MIN;
   uint32_t lo;
   std::memcpy(&lo, &f, sizeof lo);
   const uint64_t bits = 0x7FF8000000000000ull | lo;

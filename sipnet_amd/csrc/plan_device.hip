@@ -2,6 +2,7 @@
 // Compiled with -ffp-contract=off like plan.cpp: every operation below is the IEEE operation the host performs.
 #include "plan_device.h"
 
+#include <cfloat>
 #include <climits>
 
 namespace sipnet {
@@ -243,7 +244,9 @@ __global__ __launch_bounds__(256) void planRunsKernel(DevPlanArgs a) {
 
 // ---- the records ---------------------------------------------------------------------------------------------------
 __device__ inline double narrowSlotDev(double v) {   // plan.cpp narrowSlot: the rounded float under a quiet-NaN tag
-  return __hiloint2double(0x7FF80000, __float_as_int(__double2float_rn(v)));
+  float f = __double2float_rn(v);
+  if (v != 0.0 && fabsf(f) < FLT_MIN) f = v < 0.0 ? -FLT_MIN : FLT_MIN;   // (too small for a normal float: the sign class stays)
+  return __hiloint2double(0x7FF80000, __float_as_int(f));
 }
 
 __global__ __launch_bounds__(256) void planExpandKernel(DevPlanArgs a) {

@@ -1,0 +1,242 @@
+"""Deterministic forcing regimes outside the one temperate climate of synth.half_hourly_year_raw.
+
+The throughput kernels branch on what that generator never varies: the sign bits of the plan (tair > 0, par > 0,
+tsoil < 0, tsoil equal to the previous record's), the tile's packed par > 0 flags, the regular-tile classification
+(step lengths only), the snow / frozen-soil / dry-soil branches, divisions whose denominators sit at their floors and
+Q10 exponents far from +-20 C.  Each regime below returns raw `.clim` columns in the dict form of
+synth.half_hourly_year_raw, so synth.round_like_file, synth.convert_raw and synth.write_clim apply unchanged:
+
+  polar      a polar night of whole days, then a polar day; air down to -40 C, soil to -25 C and different on every
+             step; a deep snow pack that a short summer melts to exactly 0
+  arid       air to 45 C and more, VPD to 8 kPa and more, no precipitation for 220 days and then single steps of
+             100 mm and more, file wind speed 0 (the TINY floor) on a tenth of the steps
+  threshold  air and soil temperature in whole degrees with exact +0.0 and -0.0, soil at the whole-degree values a
+             member's frozenSoilThreshold can be set to, night PAR alternating between 0 and the smallest value the
+             file format prints, file VPD 0, soil constant for ten days and then changing on every step
+  lengths    four files: 12-hour steps, alternating 0.6-day / 0.4-day steps, 3-hour steps, and a half-hourly file with
+             sixty days of 12-hour steps in its middle, both switches off a 16-step tile boundary
+  tiny       `threshold` converted, with some of its exact zeros replaced by +-1e-300 and +-5e-324 (in memory only:
+             a file cannot print them): positive or negative in fp64, zero once narrowed to fp32
+
+Everything is generated here from seeds; nothing is copied from any input file.  tests/test_forcing_regimes.py asserts
+the properties above (a regime that degenerates into the temperate climate fails there) and holds the conditioning
+yardstick that lets tests/test_gpu_forcing_regimes.py use the fuzzer's tight bounds on these inputs.
+"""
+import numpy as np
+
+from sipnet_amd import synth
+from sipnet_amd.io import ClimTable
+
+SEED = 20261018
+YEAR = 2021
+NARROW = ("tair", "tsoil", "par", "precip", "vpd", "vpdSoil", "vPress", "wspd")
+FILE_REGIMES = ("polar", "arid", "threshold", "lengths_12h", "lengths_alternating", "lengths_3h", "lengths_switching")
+# steps at which the switching file changes its step length (both off a 16-step tile boundary)
+SWITCH_STEPS = (1927, 2047)
+
+
+def _es(t):
+    """saturation vapour pressure [Pa] over water, Tetens"""
+    return 611.0 * np.exp(17.27 * t / (t + 237.3))
+
+
+def _frame(lengths_days, raw_lengths):
+    """year / day / time columns of consecutive steps of the given lengths [days], starting at day 1, 00:00
+    (time in hours, rounded as a file prints it)"""
+    ticks = np.round(np.asarray(lengths_days) * 240.0).astype(np.int64)     # 1/240 day = 0.1 h: every length used here is whole
+    assert np.all(ticks / 240.0 == lengths_days)
+    start = np.concatenate([[0], np.cumsum(ticks)[:-1]])                    # since day 1, 00:00
+    d = start // 240
+    time = (start % 240) / 10.0
+    yr = YEAR + d // 365
+    doy = 1 + d % 365
+    return dict(year=yr.astype(np.int32), day=doy.astype(np.int32), time=time,
+                length=np.asarray(raw_lengths, dtype=np.float64)), start / 240.0
+
+
+def _half_hourly(n_steps):
+    return _frame(np.full(n_steps, 1.0 / 48.0), np.full(n_steps, -1800.0))
+
+
+def _sun(start, lengths_days, lat_deg):
+    """sine of the solar elevation at the middle of each step"""
+    mid = start + 0.5 * lengths_days
+    doy = 1.0 + np.mod(mid, 365.0)
+    hour = np.mod(mid, 1.0) * 24.0
+    decl = 23.45 * np.pi / 180 * np.sin(2 * np.pi * (doy - 81) / 365.0)
+    lat = lat_deg * np.pi / 180
+    return np.sin(lat) * np.sin(decl) + np.cos(lat) * np.cos(decl) * np.cos(2 * np.pi * (hour - 12.0) / 24.0), doy, hour
+
+
+def _finish(cols, tair, tsoil, par, precip, rh, wspd, vpd_floor=1.0):
+    es = _es(tair)
+    cols.update(tair=tair, tsoil=tsoil, par=par, precip=precip, vpd=np.maximum(vpd_floor, es * (1 - rh)),
+                vpdSoil=np.maximum(vpd_floor, _es(tsoil) * (1 - rh)), vPress=es * rh, wspd=wspd)
+    return cols
+
+
+def polar(n_steps=17520, site=0, seed=SEED):
+    """85 N: PAR exactly 0 on every step of the first sixty days and more, on all 48 steps of the day through the summer"""
+    rng = np.random.default_rng(seed + 101 * site)
+    cols, start = _half_hourly(n_steps)
+    L = np.full(n_steps, 1.0 / 48.0)
+    elev, doy, hour = _sun(start, L, 85.0)
+    season = -16.0 + 26.0 * np.sin(2 * np.pi * (doy - 115.0) / 365.0 + 0.1 * site)       # -42 .. +10
+    tair = season + 3.0 * np.sin(2 * np.pi * (hour - 9.0) / 24.0) + rng.normal(0, 1.5, n_steps)
+    tsoil = 0.7 * (-16.0 + 26.0 * np.sin(2 * np.pi * (doy - 125.0) / 365.0)) + 1.0 * np.sin(2 * np.pi * (hour - 14.0) / 24.0) \
+        + rng.normal(0, 0.3, n_steps)
+    tsoil = np.round(tsoil, 4)
+    for i in range(1, n_steps):                     # different on every step, after the file's rounding too
+        if tsoil[i] == tsoil[i - 1]:
+            tsoil[i] = np.round(tsoil[i] + 0.0003, 4)
+    par = np.maximum(0.0, elev) * 0.9 * rng.uniform(0.4, 1.0, n_steps)
+    precip = np.where(rng.random(n_steps) < 0.10, rng.exponential(1.0, n_steps), 0.0)     # ~175 cm a year, most of it snow
+    rh = rng.uniform(0.5, 0.95, n_steps)
+    wspd = np.maximum(0.1, rng.lognormal(-1.8, 0.4, n_steps))       # (calm air: sublimation leaves most of the snow)
+    return _finish(cols, tair, tsoil, par, precip, rh, wspd)
+
+
+def arid(n_steps=17520, site=0, seed=SEED):
+    """a hot desert year: no precipitation for 220 days, then six cloudbursts of single steps"""
+    rng = np.random.default_rng(seed + 1 + 101 * site)
+    cols, start = _half_hourly(n_steps)
+    L = np.full(n_steps, 1.0 / 48.0)
+    elev, doy, hour = _sun(start, L, 25.0)
+    tair = 28.0 + 10.0 * np.sin(2 * np.pi * (doy - 110.0) / 365.0 + 0.1 * site) + 9.0 * np.sin(2 * np.pi * (hour - 9.0) / 24.0) \
+        + rng.normal(0, 1.5, n_steps)
+    tsoil = 26.0 + 9.0 * np.sin(2 * np.pi * (doy - 120.0) / 365.0) + 4.0 * np.sin(2 * np.pi * (hour - 13.0) / 24.0) \
+        + rng.normal(0, 0.3, n_steps)
+    par = np.maximum(0.0, elev) * 0.9 * rng.uniform(0.8, 1.0, n_steps)
+    precip = np.zeros(n_steps)
+    t = np.arange(n_steps)
+    for k, day in enumerate((221, 236, 250, 279, 301, 340)):
+        hit = (t == (day - 1) * 48 + 7 + 5 * k)
+        precip = np.where(hit, 100.0 + 11.0 * k + rng.uniform(0, 5), precip)
+    rh = rng.uniform(0.04, 0.35, n_steps)
+    wspd = np.where(rng.random(n_steps) < 0.10, 0.0, np.maximum(0.1, rng.lognormal(0.5, 0.6, n_steps)))
+    return _finish(cols, tair, tsoil, par, precip, rh, wspd)
+
+
+def threshold(n_steps=17520, site=0, seed=SEED):
+    """a year that hovers around 0 C in whole degrees"""
+    rng = np.random.default_rng(seed + 2 + 101 * site)
+    cols, start = _half_hourly(n_steps)
+    L = np.full(n_steps, 1.0 / 48.0)
+    elev, doy, hour = _sun(start, L, 45.0)
+    t = np.arange(n_steps)
+    # np.round keeps the sign of what it rounds to zero: -0.3 -> -0.0, 0.3 -> 0.0
+    tair = np.round(4.0 + 7.0 * np.sin(2 * np.pi * (doy - 110.0) / 365.0 + 0.1 * site) + 5.0 * np.sin(2 * np.pi * (hour - 9.0) / 24.0)
+                    + rng.normal(0, 2.0, n_steps))
+    slow = np.round(1.0 + 3.5 * np.sin(2 * np.pi * (doy - 120.0) / 365.0) + rng.normal(0, 0.4, n_steps))
+    tsoil = np.where(t % 2 == 1, slow + 1.0, slow)              # (np.where: -0.0 stays -0.0)
+    tsoil[:480] = 1.0                                           # constant for ten days
+    for i in range(480, n_steps):                               # ... then changing on every step
+        if tsoil[i] == tsoil[i - 1]:
+            tsoil[i] += 1.0
+    par = np.maximum(0.0, elev) * 0.9 * rng.uniform(0.4, 1.0, n_steps)
+    night = np.round(par, 4) == 0.0
+    flicker = night & (doy >= 60) & (doy < 300) & (t % 2 == 1)
+    par = np.where(flicker, 0.0001, np.where(night, 0.0, par))
+    precip = np.where(rng.random(n_steps) < 0.08, rng.exponential(1.5, n_steps), 0.0)
+    rh = rng.uniform(0.4, 0.95, n_steps)
+    wspd = np.maximum(0.1, rng.lognormal(0.5, 0.5, n_steps))
+    cols = _finish(cols, tair, tsoil, par, precip, rh, wspd)
+    cols["vpd"] = np.where(rng.random(n_steps) < 0.10, 0.0, cols["vpd"])
+    return cols
+
+
+def _by_lengths(lengths_days, raw_lengths, site, seed):
+    """a temperate-to-cold year (snow in winter, 40 N) sampled at steps of the given lengths; PAR and precipitation
+    are per-step totals"""
+    rng = np.random.default_rng(seed + 3 + 101 * site)
+    n = len(lengths_days)
+    cols, start = _frame(lengths_days, raw_lengths)
+    elev, doy, hour = _sun(start, lengths_days, 40.0)
+    tair = 3.0 + 13.0 * np.sin(2 * np.pi * (doy - 110.0) / 365.0 + 0.1 * site) + 5.0 * np.sin(2 * np.pi * (hour - 9.0) / 24.0) \
+        + rng.normal(0, 1.5, n)
+    tsoil = 0.7 * (3.0 + 13.0 * np.sin(2 * np.pi * (doy - 120.0) / 365.0)) + rng.normal(0, 0.3, n)
+    # a long step's light: its mid-point's for short steps, the daylight share for half-day steps
+    light = np.where(lengths_days >= 0.3, np.maximum(0.0, elev + 0.35) * 0.5, np.maximum(0.0, elev))
+    par = light * 43.2 * lengths_days * rng.uniform(0.4, 1.0, n)
+    wet = rng.random(n) < np.minimum(0.9, 0.06 * 48.0 * lengths_days)
+    precip = np.where(wet, rng.exponential(1.2, n) * np.maximum(1.0, 6.0 * lengths_days), 0.0)
+    rh = rng.uniform(0.4, 0.95, n)
+    wspd = np.maximum(0.1, rng.lognormal(0.5, 0.5, n))
+    return _finish(cols, tair, tsoil, par, precip, rh, wspd, vpd_floor=10.0)
+
+
+def lengths_12h(site=0, seed=SEED):
+    return _by_lengths(np.full(730, 0.5), np.full(730, -43200.0), site, seed)
+
+
+def lengths_alternating(site=0, seed=SEED):
+    """0.6-day | 0.4-day records (lengths given in days, as positive file values)"""
+    L = np.tile([0.6, 0.4], 365)
+    return _by_lengths(L, L, site, seed + 10)
+
+
+def lengths_3h(site=0, seed=SEED):
+    return _by_lengths(np.full(2920, 0.125), np.full(2920, -10800.0), site, seed + 20)
+
+
+def lengths_switching(site=0, seed=SEED):
+    """half-hourly for 40 days and seven steps, 12-hourly for 60 days, half-hourly for the rest of the year"""
+    a, b = SWITCH_STEPS
+    n3 = (365 - 100) * 48 - a % 48
+    L = np.concatenate([np.full(a, 1.0 / 48.0), np.full(b - a, 0.5), np.full(n3, 1.0 / 48.0)])
+    raw = np.where(L == 0.5, -43200.0, -1800.0)
+    return _by_lengths(L, raw, site, seed + 30)
+
+
+RAW = {"polar": polar, "arid": arid, "threshold": threshold, "lengths_12h": lengths_12h,
+       "lengths_alternating": lengths_alternating, "lengths_3h": lengths_3h, "lengths_switching": lengths_switching}
+
+
+def raw(name, site=0, seed=SEED):
+    """the raw columns of a file regime, rounded like a file"""
+    return synth.round_like_file(RAW[name](site=site, seed=seed))
+
+
+TINY_VALUES = (1e-300, -1e-300, 5e-324, -5e-324)
+
+
+def tiny(site=0, seed=SEED, gdd=1):
+    """`threshold` converted, some of its exact zeros in tair, tsoil and PAR replaced by +-1e-300 and +-5e-324"""
+    clim = synth.convert_raw(raw("threshold", site, seed), gdd)
+    d = clim.data.copy()
+    rng = np.random.default_rng(seed + 4 + 101 * site)
+    for col in (1, 2, 3):
+        zeros = np.nonzero(d[:, col] == 0.0)[0]
+        pick = zeros[rng.random(len(zeros)) < 0.5]
+        d[pick, col] = np.asarray(TINY_VALUES)[rng.integers(0, 4, len(pick))]
+    if gdd:
+        d[:, 9] = np.maximum(d[:, 1] * d[:, 0], 0.0)            # convert_raw's growing degree days of the new tair
+    return ClimTable(d, clim.year, clim.day)
+
+
+def clim(name, site=0, seed=SEED, gdd=1):
+    """a regime as the converted ClimTable a batch or the oracle takes"""
+    if name == "tiny":
+        return tiny(site, seed, gdd)
+    return synth.convert_raw(raw(name, site, seed), gdd)
+
+
+def slice_raw(cols, a, b):
+    return {k: v[a:b] for k, v in cols.items()}
+
+
+def hard_members(base, n=130, frozen_whole=True):
+    """the member set of the regime tests: synth.perturbed_params(base, n, scale=3.0) plus the fuzzer's three hard
+    members (wood x 0.001, soilWFracInit 0.02, leafTurnoverRate 0.9); a few members' frozenSoilThreshold set to whole
+    degrees, so that `threshold`'s soil sits on it exactly"""
+    from sipnet_amd.config import param_index as pi
+    members = synth.perturbed_params(base, n, scale=3.0)
+    hard = np.tile(np.asarray(base, dtype=np.float64), (3, 1))
+    hard[0, pi("plantWoodInit")] *= 0.001
+    hard[1, pi("soilWFracInit")] = 0.02
+    hard[2, pi("leafTurnoverRate")] = 0.9
+    members = np.concatenate([members, hard])
+    if frozen_whole:
+        for m, v in ((1, 0.0), (2, 1.0), (3, 3.0), (65, 2.0), (66, -0.0), (129, 1.0)):
+            members[m, pi("frozenSoilThreshold")] = v
+    return members

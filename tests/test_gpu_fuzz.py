@@ -115,6 +115,18 @@ def test_fuzz_sites_of_different_lengths(campaign):
     assert "30 trials ok" in r.stdout
 
 
+def test_fuzz_forcing_regimes():
+    """a fixed-seed slice with FUZZ_FORCING=1: every site's forcing a piece of one of the regimes of tests/forcing_regimes.py
+    (polar, arid, whole degrees around 0 C, other and changing step lengths, zeros of +-1e-300) from a random record on,
+    random flag sets, events, kernels and launch cuts as in the plain campaign"""
+    env = dict(os.environ, FUZZ_FORCING="1", FUZZ_BOUNDED="1")
+    r = subprocess.run([sys.executable, os.path.join(helpers.REPO, "tools", "fuzz_gpu.py"), "12", "23"],
+                       capture_output=True, text=True, timeout=900, env=env)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "12 trials ok" in r.stdout and r.stdout.count(" forcing ") == 12
+
+
 def test_fuzz_in_kernel_sums_on_the_cooperative_layouts():
     """a fixed-seed slice of the round-6 campaign (FUZZ_COOP=1 FUZZ_SUMS=1): every eligible trial (fp64, lean) is run again
     through sipnet_batch_run_sums -- random group lengths, launches cut at random multiples of the group -- and its sums must

@@ -29,6 +29,13 @@ OPT_ONLY = bool(os.environ.get("FUZZ_OPT"))
 # FUZZ_RAGGED=1 (on top of any of the above, or alone): every trial has several sites and the sites' forcings end at
 # different records (a site's members stop at ITS last record; the launch cuts fall before, at and after those ends)
 RAGGED = bool(os.environ.get("FUZZ_RAGGED"))
+# FUZZ_FORCING=1 (on top of any of the above, or alone): every site's forcing is a piece of one of the regimes of
+# tests/forcing_regimes.py -- polar, arid, whole degrees around 0 C, 12-hour / 0.6|0.4-day / 3-hour / switching step lengths,
+# zeros of +-1e-300 -- instead of the temperate synthetic year; the sites of a trial start on the same day of the year (the event
+# schedule is one for all of them) at a random record of it, and a regime with fewer records left ends its site early
+FORCING = bool(os.environ.get("FUZZ_FORCING"))
+if FORCING:
+    from tests import forcing_regimes      # (only this campaign needs the regimes)
 trials = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 12345
 only = int(sys.argv[3]) if len(sys.argv) > 3 else -1      # rerun one trial with details
@@ -109,9 +116,25 @@ for trial in range(trials):
         site_T[int(rng_r.integers(1, S))] = T          # the batch is as long as its longest site
     clims = []
     for sidx in range(S):
+        if FORCING:
+            continue
         raw = synth.half_hourly_year_raw(start + T, site=site0 + sidx)
         raw = {k: v[start:start + site_T[sidx]] for k, v in raw.items()}
         clims.append(synth.convert_raw(synth.round_like_file(raw)))
+    if FORCING:     # (a generator of its own again)
+        rng_f = np.random.default_rng(seed0 * 15485863 + trial)
+        names = list(forcing_regimes.FILE_REGIMES) + ["tiny"]
+        day0 = 1 + int(rng_f.integers(0, 365 - T // 48))
+        picked = []
+        for sidx in range(S):
+            name = names[int(rng_f.integers(len(names)))]
+            c = forcing_regimes.clim(name, site=site0 + sidx)
+            a = int(np.argmax(c.day == day0))
+            a += int(rng_f.integers(0, max(1, min(48, int((c.day == day0).sum())))))
+            site_T[sidx] = min(site_T[sidx], c.n_steps - a)
+            clims.append(c.slice(a, a + site_T[sidx]))
+            picked.append(name)
+        T = max(site_T)
     clim = clims[int(np.argmax(site_T))]     # (the longest: the event schedule spans it)
     members = synth.perturbed_params(base, M, seed=int(rng.integers(1 << 30)), scale=float(rng.choice([1.0, 3.0])))
     if M > 3:      # a few hard cases
@@ -319,7 +342,8 @@ for trial in range(trials):
         err = 0.0
     flag_s = "+".join(k for k, v in kw.items() if v != sa.DEFAULT_FLAGS.get(k)) or "default"
     print(f"trial {trial:3d}: S={S} M={M:3d} T={T:5d} segs={len(cuts)-1} {'f32' if prec else 'f64'} {'fast' if fast else 'strict'} "
-          f"ev={0 if ev is None else len(ev):2d} [{flag_s}]{forced} {b_kernel.split('<')[0]} planes {err:.2e} pools {perr:.2e}", flush=True)
+          f"ev={0 if ev is None else len(ev):2d} [{flag_s}]{forced} {b_kernel.split('<')[0]} planes {err:.2e} pools {perr:.2e}"
+          + (" forcing " + ",".join(picked) if FORCING else ""), flush=True)
     assert np.isfinite(got[:, :, ok]).all()
     if only >= 0 and prec == sa.F64 and ok.any():   # where a mismatch starts
         rel = np.abs(got[:, :, ok] - want[:, :, ok]) / scale
