@@ -804,6 +804,54 @@ int sipnet_batch_enkf_analysis_smooth(sipnet_batch *b, int32_t n_obs, const sipn
                                       const double *d_param_inflation, int32_t n_series,
                                       const sipnet_enkf_series *series, int32_t *d_site_info, void *hip_stream);
 
+/* ---- the per-site filter of an ensemble sharded by member across ranks ------------------------------------------------
+ * Rank r's batch has the n_sites, flags and climate of every other rank's and its own M_r members per site (M_r may differ
+ * between ranks).  Site s's ensemble is the union over the ranks, in rank order, of each rank's LIVE members of site s (live
+ * as in sipnet_batch_enkf_analysis_sites), and the analysis is that call's filter over the union: its operators and codes,
+ * its inflation about the union's means, its serial order with NaN observations skipped, divisor n - 1, gains and alpha,
+ * its clipping and hasSufficientBiomass rule per member, and its write-back of the analysed slots of live members only.  It
+ * is carried out in covariance space as sipnet_batch_enkf_analysis_block carries its update out, so it equals the member-
+ * space update to rounding (tests: 1e-10 of max(|x|, ensemble sd)).  No member crosses ranks: a rank contributes, per
+ * site, a moment block of W = sipnet_enkf_moment_words(n_analysed_pools, n_obs) = 2 + V + V n_obs doubles, V =
+ * n_analysed_pools + n_obs (at most 495), the caller gathers every rank's blocks with ONE all-gather, and every rank runs
+ * the same small chain redundantly, from the same bytes in the same order, then moves its own members.
+ * sipnet_batch_enkf_shard_moments: the variables are the analysed pools in slot order, then the h of ALL n_obs operators
+ * from the forecast (observed or not).  d_moments (DEVICE, [n_sites][W]) gets per site {n_r the live count, 0 (reserved),
+ * the shard's means of the V variables over its live members [V], C_r [V][n_obs] row-major: C_r[v][i] = the sum over the
+ * shard's live members of (x_v - mean_r[v]) (h_i - mean_r[h_i]), NOT divided}; a site without a live member gets zeros.
+ * The products are centred on the shard's own means (raw sums would lose the spread at pool means of 1e6).  Every sum is
+ * taken in one fixed order (chunks of 256 members, a fixed tree inside a chunk, the chunk totals in order), without an
+ * atomic, a grid barrier or a spin: a repeated call gives the same bits.  Any M_r up to the batch's 4 194 304 columns.  The
+ * batch is left bit-identical (pending set_params rows are flushed first; armed log-weights are kept).
+ * sipnet_batch_enkf_analysis_sharded: d_gathered (DEVICE, [world][n_sites][W]) holds every rank's blocks in rank order;
+ * obs, sd and inflation must be the same on every rank (the caller's duty).  The call forms its working copies itself, by
+ * the same load, so the two calls share nothing but the blocks.  Per site the blocks are merged in rank order, blocks with
+ * n_r = 0 skipped; with a the merged part and b the next block: n = n_a + n_b, d = mean_b - mean_a,
+ * C += C_b + d_v d_i (n_a n_b / n), mean = mean_a + d (n_b / n).  Then the codes of sipnet_batch_enkf_analysis_sites from the
+ * union's n; the covariance C / (n - 1), times lambda^2 where the site inflates; the chain over the non-NaN observations
+ * (a step takes C to its Schur complement and accumulates the means' shifts and the transform T); per live member of this
+ * rank: forecast, inflated about the union's means, + the mean's shift + T x (its rows' anomalies about the union's
+ * forecast means); the limits; the write-back.  site_info[s] = {code, observations used, live members of the UNION,
+ * members of THIS rank kept on their forecast}; the first three are the same on every rank.  A site any of whose gathered
+ * counts is not a finite integer 0 .. 4 194 304 (a foreign or torn buffer) gets code -2 and is untouched.  Swapping blocks
+ * in the buffer changes the merge order and so the last bits, nothing more.
+ * d_site_info NULL: obs, sd, inflation and the counts are read back and checked first; a -2 site gives
+ * SIPNET_ERR_BAD_ARGUMENT naming it, and nothing is written.  Refusals, flush of pending parameters, dropped log-weights and
+ * bookkeeping otherwise as sipnet_batch_enkf_analysis_sites (the moments call needs no obs or sd); in addition, before any
+ * launch: world outside 1..64; a NULL d_moments or d_gathered.  sipnet_enkf_moment_words is host only and returns -1 for
+ * n_analysed_pools outside 1..13 or n_obs outside 1..16.  With world = 1 the pair is a per-site filter whose launch count
+ * does not grow with n_obs, for any member count.
+ * Out of scope: analysed parameters and series over shards, a localization over shards, the node object and the CLI. */
+int32_t sipnet_enkf_moment_words(int32_t n_analysed_pools, int32_t n_obs);
+int sipnet_batch_enkf_shard_moments(sipnet_batch *b, int32_t n_obs, const sipnet_enkf_obs *ops, int32_t analysed_mask,
+                                    const void *const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                    double *d_moments /* DEVICE [n_sites][W] */, void *hip_stream);
+int sipnet_batch_enkf_analysis_sharded(sipnet_batch *b, int32_t n_obs, const sipnet_enkf_obs *ops, int32_t analysed_mask,
+                                       const void *const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                       const double *d_obs, const double *d_sd, const double *d_inflation,
+                                       int32_t world, const double *d_gathered /* DEVICE [world][n_sites][W] */,
+                                       int32_t *d_site_info, void *hip_stream);
+
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its
  * range) and known on the device only; RCCL's send / receive sizes are host arguments, so an all-to-all

@@ -203,6 +203,10 @@ SIGNATURES = {
     "sipnet_enkf_local_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "sipnet_batch_enkf_analysis_block": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64,
                                                    _P, _P, _P, _P, _P, _P]),
+    "sipnet_enkf_moment_words": (C.c_int32, [C.c_int32, C.c_int32]),
+    "sipnet_batch_enkf_shard_moments": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),
+    "sipnet_batch_enkf_analysis_sharded": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
+                                                     _P, _P, C.c_int32, _P, _P, _P]),
     "sipnet_batch_pf_publish": (C.c_int, [_P, C.c_int32, _P]),
     "sipnet_batch_pf_connect": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "sipnet_batch_pf_block_len": (C.c_int64, [_P]),

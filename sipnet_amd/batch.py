@@ -493,6 +493,50 @@ class Batch:
                                                       self._stream()), "enkf_analysis_block")
         del keep
 
+    def enkf_moment_words(self, operators, analysed):
+        """doubles in one site's moment block of enkf_shard_moments (sipnet_enkf_moment_words)"""
+        from .config import pool_mask
+        return int(self.L.sipnet_enkf_moment_words(bin(pool_mask(analysed)).count("1"), len(list(operators))))
+
+    def enkf_shard_moments(self, operators, analysed, planes=None, out=None):
+        """this batch's share of a per-site EnKF analysis over an ensemble sharded by member across ranks
+        (sipnet_batch_enkf_shard_moments): per site the live count, the means and the centred products of the analysed pools
+        and predicted observations over this batch's live members -> a float64 device tensor [n_sites][W], W =
+        enkf_moment_words(operators, analysed).  out: a contiguous float64 device tensor of that size to write into (a rank's
+        slice of the all-gather's buffer).  The batch is not changed; operators, analysed and planes as enkf_analysis_sites."""
+        t = self._torch
+        what = "enkf_shard_moments"
+        ops = list(operators)
+        args, keep = self._enkf_args(what, None, None, ops, analysed, planes, None, None)
+        W = self.enkf_moment_words(ops, analysed)
+        if W < 0:
+            raise ValueError(f"{what}: needs 1..16 operators and 1..13 analysed pools")
+        if out is None:
+            out = t.empty((self.n_sites, W), dtype=t.float64, device=self.device)
+        elif out.dtype != t.float64 or not out.is_contiguous() or not out.is_cuda or out.numel() != self.n_sites * W:
+            raise ValueError(f"{what}: out must be a contiguous float64 device tensor of n_sites x {W}")
+        check(self.L.sipnet_batch_enkf_shard_moments(self.h, *args[:7], C.c_void_p(out.data_ptr()), self._stream()), what)
+        del keep
+        return out.view(self.n_sites, W)
+
+    def enkf_analysis_sharded(self, gathered, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
+        """the per-site EnKF analysis of an ensemble sharded by member across ranks, this batch's members moved
+        (sipnet_batch_enkf_analysis_sharded).  gathered: every rank's enkf_shard_moments in rank order, a contiguous float64
+        device tensor [world][n_sites][W]; obs, sd and inflation must be the same on every rank.  info_out[s] = {code,
+        observations used, live members of the union, members of this batch kept on their forecast}; the other arguments as
+        enkf_analysis_sites.  dist.enkf_analysis_sharded does the moments, the all-gather and this call."""
+        t = self._torch
+        what = "enkf_analysis_sharded"
+        ops = list(operators)
+        W = self.enkf_moment_words(ops, analysed)
+        if (gathered.dtype != t.float64 or not gathered.is_contiguous() or not gathered.is_cuda or gathered.dim() != 3
+                or tuple(gathered.shape[1:]) != (self.n_sites, W)):
+            raise ValueError(f"{what}: gathered must be a contiguous float64 device tensor [world][{self.n_sites}][{W}]")
+        args, keep = self._enkf_args(what, obs, sd, ops, analysed, planes, inflation, info_out)
+        check(self.L.sipnet_batch_enkf_analysis_sharded(self.h, *args[:10], int(gathered.shape[0]),
+                                                        C.c_void_p(gathered.data_ptr()), args[10], self._stream()), what)
+        del keep
+
     @staticmethod
     def _open_localization(what, local):
         """the handle of an EnkfLocalization that has not been closed"""
@@ -515,7 +559,8 @@ class Batch:
                 raise ValueError(f"{what}: {name} needs {n} values, got {x.numel()}")
             return x
 
-        obs, sd = dev(obs, self.n_sites * n_obs, "obs"), dev(sd, self.n_sites * n_obs, "sd")
+        if obs is not None:                              # (None: a call without observations, enkf_shard_moments)
+            obs, sd = dev(obs, self.n_sites * n_obs, "obs"), dev(sd, self.n_sites * n_obs, "sd")
         infl = dev(inflation, self.n_sites, "inflation") if inflation is not None else None
         arr = (EnkfObs * max(n_obs, 1))(*ops)
         ptrs = (C.c_void_p * 3)()
@@ -539,7 +584,8 @@ class Batch:
                                      or info_out.numel() != 4 * self.n_sites):
             raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x 4")
         args = (n_obs, arr, pool_mask(analysed), ptrs if planes is not None else None, f32, n_steps, ld,
-                C.c_void_p(obs.data_ptr()), C.c_void_p(sd.data_ptr()), C.c_void_p(infl.data_ptr()) if infl is not None else None,
+                C.c_void_p(obs.data_ptr()) if obs is not None else None, C.c_void_p(sd.data_ptr()) if sd is not None else None,
+                C.c_void_p(infl.data_ptr()) if infl is not None else None,
                 C.c_void_p(info_out.data_ptr()) if info_out is not None else None)
         return args, (obs, sd, infl, arr, ptrs)
 

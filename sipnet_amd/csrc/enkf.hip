@@ -1,7 +1,8 @@
-// enkf.hip -- the five ensemble Kalman filter analyses of the member pools: sipnet_batch_enkf_analysis_sites (a filter per
+// enkf.hip -- the ensemble Kalman filter analyses of the member pools: sipnet_batch_enkf_analysis_sites (a filter per
 // site), _local (the localized serial filter across sites), _block (the block-local filter: every site on its own, in one
-// pass), _joint (the filter per site with analysed parameters among its variables) and _smooth (the joint call, and its update
-// applied to the window's flux series).
+// pass), _joint (the filter per site with analysed parameters among its variables), _smooth (the joint call, and its update
+// applied to the window's flux series) and _sharded (the filter per site of an ensemble sharded by member across ranks, from
+// the moment blocks of sipnet_batch_enkf_shard_moments).
 //
 // Site s owns columns [s M, (s + 1) M).  Its live members' analysed pools and predicted observations are the analysis's
 // variables: working copies W[v][member], v < nA the analysed pools (in state-slot order; the joint analysis: then the
@@ -23,6 +24,8 @@
 //                     target site): a launch per level of the host schedule (sipnet_batch_enkf_analysis_local)
 //   enkf_block.inc    enkfBlockKernel, a workgroup per target site running its serial update on its small sample covariance:
 //                     ONE launch (sipnet_batch_enkf_analysis_block)
+//   enkf_sharded.inc  the moments of a rank's members (enkfShardSum / Product / TotalKernel), the merge of the ranks' blocks and
+//                     the chain (enkfShardChainKernel, a workgroup per site), the transform applied (enkfShardApplyKernel)
 //   enkf_smooth.inc   enkfSmoothPrepKernel (smoothFront, before the pool analysis) and enkfSmoothKernel (smoothSeries, after)
 //
 // The host side: every entry point fills an EnkfCall and is its checks (localChecks for the two with a localization, then
@@ -46,6 +49,7 @@ namespace {
 #include "enkf_sites.inc"
 #include "enkf_local.inc"
 #include "enkf_block.inc"
+#include "enkf_sharded.inc"
 #include "enkf_smooth.inc"
 
 }  // namespace
@@ -94,6 +98,7 @@ struct EnkfCall {
   const double *d_obs, *d_sd, *d_inflation;
   int32_t* d_site_info;
   hipStream_t stream;
+  bool momentsOnly = false;                // sipnet_batch_enkf_shard_moments: no observations, nothing of the batch written
 };
 
 // The checks and the arguments the analyses share, up to the scratch block: 0, or the error (the message names `name`).
@@ -103,7 +108,7 @@ int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a) {
   const int32_t n_obs = c.n_obs;
   const hipStream_t stream = c.stream;
   const int32_t allPools = (1 << kPools) - 1;
-  if (!b || !c.ops || !c.d_obs || !c.d_sd) return refuse(name, "a NULL batch, operators, observations or sds");
+  if (!b || !c.ops || (!c.momentsOnly && (!c.d_obs || !c.d_sd))) return refuse(name, "a NULL batch, operators, observations or sds");
   if (n_obs < 1 || n_obs > kMaxObs) return refuse(name, "n_obs must be 1..16");
   if (c.analysed_mask == 0 || (c.analysed_mask & ~allPools)) return refuse(name, "analysed_mask must name pools 0..12");
   bool planesUsed = false;
@@ -127,7 +132,7 @@ int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a) {
   int rc = useDevice(b);
   if (rc) return rc;
   const int64_t nSites = b->n_sites, M = b->n_members, ncol = b->ncol;
-  if (!c.d_site_info) {   // the synchronous form: the inputs are checked before anything is launched
+  if (!c.d_site_info && !c.momentsOnly) {   // the synchronous form: the inputs are checked before anything is launched
     std::vector<double> obs((size_t)(nSites * n_obs)), sd(obs.size()), infl(c.d_inflation ? (size_t)nSites : 0);
     HIP_TRY(hipMemcpyAsync(obs.data(), c.d_obs, obs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(sd.data(), c.d_sd, sd.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -140,8 +145,10 @@ int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a) {
                             "be finite and >= 1); nothing was written");
     }
   }
-  b->pfPre.valid = false;
-  b->pfArm.set = false;
+  if (!c.momentsOnly) {
+    b->pfPre.valid = false;
+    b->pfArm.set = false;
+  }
   rc = orderBehindBusy(b, stream);
   if (rc) return rc;
   rc = flushParams(b, stream);
@@ -824,6 +831,74 @@ int sipnet_batch_enkf_analysis_block(sipnet_batch* b, const sipnet_enkf_local* L
   if (small) launch(useLds ? enkfBlockKernel<true, 256> : enkfBlockKernel<false, 256>, 256);
   else launch(useLds ? enkfBlockKernel<true, 1024> : enkfBlockKernel<false, 1024>, 1024);
   return enkfEnd(c, a, /*perChunk=*/true, useLds ? 1 : 0, (int32_t)b->n_sites);
+}
+
+int32_t sipnet_enkf_moment_words(int32_t n_analysed_pools, int32_t n_obs) {
+  if (n_analysed_pools < 1 || n_analysed_pools > kPools || n_obs < 1 || n_obs > kMaxObs) return -1;
+  return shardWords(n_analysed_pools, n_obs);
+}
+
+int sipnet_batch_enkf_shard_moments(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                    const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                    double* d_moments, void* hip_stream) {
+  const char* name = "sipnet_batch_enkf_shard_moments";
+  if (!d_moments) return refuse(name, "a NULL d_moments");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const EnkfCall c{b, n_obs, ops, analysed_mask, d_planes, elem_is_f32, n_steps, ld, nullptr, nullptr, nullptr, nullptr, stream,
+                   /*momentsOnly=*/true};
+  EnkfArgs a;
+  int rc = enkfBegin(name, c, a);
+  if (rc) return rc;
+  const int cap = a.nv * a.nObs, W = shardWords(a.nA, a.nObs);   // (part: a chunk's sums [nv], then its products [nv][n_obs])
+  rc = enkfScratch(b, &b->d_enkf, &b->enkfBytes, a, nullptr, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false, 0,
+                   nullptr, cap);
+  if (rc) return rc;
+  const dim3 chunks = chunkGrid(b, a);
+  const auto totals = [&](int entries) { return dim3((unsigned)b->n_sites, (unsigned)((entries + 3) / 4)); };
+  hipLaunchKernelGGL((elem_is_f32 ? enkfLoadKernel<float, EnkfArgs> : enkfLoadKernel<double, EnkfArgs>), chunks, dim3(256), 0,
+                     stream, a);
+  hipLaunchKernelGGL(enkfShardSumKernel, chunks, dim3(256), 0, stream, a, cap);
+  hipLaunchKernelGGL(enkfShardTotalKernel, totals(a.nv), dim3(256), 0, stream, a, cap, d_moments, W, 0);
+  hipLaunchKernelGGL(enkfShardProductKernel, chunks, dim3(256), 0, stream, a, cap, (const double*)d_moments, W);
+  hipLaunchKernelGGL(enkfShardTotalKernel, totals(cap), dim3(256), 0, stream, a, cap, d_moments, W, 1);
+  HIP_TRY(hipGetLastError());
+  return markBusy(b, stream);
+}
+
+int sipnet_batch_enkf_analysis_sharded(sipnet_batch* b, int32_t n_obs, const sipnet_enkf_obs* ops, int32_t analysed_mask,
+                                       const void* const d_planes[3], int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                       const double* d_obs, const double* d_sd, const double* d_inflation, int32_t world,
+                                       const double* d_gathered, int32_t* d_site_info, void* hip_stream) {
+  const char* name = "sipnet_batch_enkf_analysis_sharded";
+  if (world < 1 || world > 64) return refuse(name, "world must be 1..64");
+  if (!d_gathered) return refuse(name, "a NULL d_gathered");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const EnkfCall c{b, n_obs, ops, analysed_mask, d_planes, elem_is_f32, n_steps, ld, d_obs, d_sd, d_inflation, d_site_info, stream};
+  EnkfArgs a;
+  int rc = enkfBegin(name, c, a);
+  if (rc) return rc;
+  const int64_t nSites = b->n_sites;
+  const int W = shardWords(a.nA, a.nObs);
+  if (!d_site_info) {   // the synchronous form: the blocks' counts are checked before anything is launched
+    std::vector<double> counts((size_t)world * (size_t)nSites);
+    HIP_TRY(hipMemcpy2DAsync(counts.data(), sizeof(double), d_gathered, (size_t)W * sizeof(double), sizeof(double), counts.size(),
+                             hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int32_t r = 0; r < world; r++)
+      for (int64_t s = 0; s < nSites; s++)
+        if (!shardCountOk(counts[(size_t)r * nSites + s]))
+          return refuse(name, "site " + std::to_string(s) + ": bad input (the count of rank " + std::to_string(r) +
+                              "'s moment block is not an integer 0..4194304); nothing was written");
+  }
+  double* plan = nullptr;
+  rc = enkfScratch(b, &b->d_enkf, &b->enkfBytes, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false,
+                   kShardPlan, &plan);
+  if (rc) return rc;
+  hipLaunchKernelGGL((elem_is_f32 ? enkfLoadKernel<float, EnkfArgs> : enkfLoadKernel<double, EnkfArgs>), chunkGrid(b, a), dim3(256),
+                     0, stream, a);
+  hipLaunchKernelGGL(enkfShardChainKernel, siteGrid(b), dim3(256), 0, stream, a, d_gathered, world, nSites, W, plan);
+  hipLaunchKernelGGL(enkfShardApplyKernel, chunkGrid(b, a), dim3(256), 0, stream, a, (const double*)plan);
+  return enkfEnd(c, a, /*perChunk=*/true, 0, 0);
 }
 
 }  // extern "C"

@@ -378,3 +378,33 @@ def pf_analysis_peers(batch, plane, obs, sigma, u0, rank=0, world=1, group=None,
             "exchange": "peer reads", "params_by_index": pinfo["params_by_index"], "analysis_one_launch": pinfo["fused"],
             "analysis_grid": pinfo["grid"], "analysis_slots": pinfo["n_slots"]}
     return anc, info
+
+
+def enkf_analysis_sharded(batch, obs, sd, operators, analysed, planes=None, inflation=None, rank=0, world=1, group=None,
+                          collectives=None, info_out=None):
+    """One per-site EnKF analysis of an ensemble sharded by member across ranks: this rank's moment blocks
+    (Batch.enkf_shard_moments, written into its slice of the [world][n_sites][W] buffer) -> ONE all-gather of the blocks ->
+    the merge, the chain and this rank's members moved (Batch.enkf_analysis_sharded).  No member crosses ranks.  obs, sd and
+    inflation must be the same on every rank.  collectives: a DirectComm -- the all-gather then goes through the engine's own
+    RCCL communicator on the batch's stream -- else torch.distributed's process group; with world 1 and no group there is no
+    collective.  Returns the gathered blocks."""
+    import torch
+    import torch.distributed as dist
+    ops = list(operators)
+    W = batch.enkf_moment_words(ops, analysed)
+    gathered = getattr(batch, "_enkf_gathered", None)
+    if gathered is None or gathered.shape != (world, batch.n_sites, W):
+        gathered = batch._enkf_gathered = torch.empty((world, batch.n_sites, W), dtype=torch.float64, device=batch.device)
+    mine = gathered[rank]
+    batch.enkf_shard_moments(ops, analysed, planes=planes, out=mine)
+    if isinstance(collectives, DirectComm):
+        collectives.all_gather(mine.view(-1), gathered.view(world, -1), batch._stream())
+    elif world > 1 or group is not None:
+        if _host_staged(mine, group):
+            out = torch.empty((world, batch.n_sites, W), dtype=torch.float64)
+            dist.all_gather_into_tensor(out.view(-1), mine.cpu().view(-1), group=group)
+            gathered.copy_(out)
+        else:   # in place: rank r's input is its own slice of the output
+            dist.all_gather_into_tensor(gathered.view(-1), mine.view(-1), group=group)
+    batch.enkf_analysis_sharded(gathered, obs, sd, ops, analysed, planes=planes, inflation=inflation, info_out=info_out)
+    return gathered
