@@ -852,6 +852,63 @@ int sipnet_batch_enkf_analysis_sharded(sipnet_batch *b, int32_t n_obs, const sip
                                        int32_t world, const double *d_gathered /* DEVICE [world][n_sites][W] */,
                                        int32_t *d_site_info, void *hip_stream);
 
+/* ---- order statistics of a series per (row, site): quantiles, the rank histogram's counts, the CRPS ----------------------
+ * d_series (DEVICE, [rows][ld], floats or doubles by elem_is_f32) is a plane of sipnet_batch_run, one of
+ * sipnet_batch_run_sums' arrays or a series sipnet_batch_enkf_analysis_smooth has analysed.  A CELL is (row r, site s); its
+ * sample is d_series[r][s M + j] over the site's used members, read as doubles (a float is widened: exact and monotone).
+ * live_only = 1: the used members are the site's LIVE members as in sipnet_batch_enkf_analysis_sites (state[29] == 0 and the
+ * site's plan status OK), and the batch must have been set up; live_only = 0: all M members, on any created batch.  A value
+ * of a member that is not used never enters a result and may be NaN; columns ncol .. ld are not read.  count[r][s] = n, the
+ * sample size.
+ * Order: numeric, -inf and +inf as numbers; -0.0 and +0.0 compare equal, and which of the two a result carries is
+ * unspecified.  A NaN among the used values (numpy's rule): every floating-point output of the cell is NaN and rank =
+ * {-1, -1}; count is still n.
+ * Quantiles: Hyndman & Fan's type 7 (numpy's "linear", R's default).  h = (n - 1) q, lo = floor(h), g = h - lo; Q = x_(lo)
+ * when g == 0, else Q = x_(lo) + g (x_(lo+1) - x_(lo)), every operation rounded once, no fused multiply-add (so between
+ * -inf and +inf, or two equal infinities, with g > 0: NaN, as IEEE has it).  sipnet_quantile_positions (host only, no
+ * device) returns exactly the lo and g the device uses, from the same expressions: host and device cannot disagree on an
+ * index.  n = 0: NaN; n = 1: the value.  q[n_q] (HOST) need not be sorted and may repeat; d_quant[i][r][s] is q[i]'s.
+ * Scores, against d_obs[r][s] = y (required when d_crps or d_rank is given): rank[r][s] = {#(x < y), #(x == y)}, the rank
+ * histogram's bin and its ties; crps[r][s] = (1/n) sum |d_i| - (1/n^2) sum_i (2 i - n - 1) d_(i), d = x - y in sorted order,
+ * i = 1 .. n -- the energy form (1/n) sum |x - y| - (1/2n^2) sum sum |x_i - x_j|, centred on y so that a large mean cancels
+ * nothing.  Both sums are taken in one fixed order (a thread its elements in order, the threads by a fixed tree): a repeated
+ * call gives the same bits.  y NaN: not scored, crps NaN and rank {-1, -1}, the quantiles as without it.  Any other
+ * non-finite y is a bad argument for that cell: its quantiles and crps are NaN and rank = {-2, -2} (count is still n).
+ * n = 0 with a finite y: crps NaN, rank {0, 0}.
+ * Paths: one 256-thread workgroup per cell on either.  The SORT path holds the cell's keys (order-preserving 64-bit
+ * integers of the doubles) in LDS, reads every element from HBM once and sorts with a bitonic network; it takes at most
+ * sipnet_quantile_lds_members(elem_is_f32) members per site (16 384 for either element type: 128 KiB of LDS at the most,
+ * sized to the call's M).  The SELECTION path takes any M: a radix select of the at most 2 n_q order statistics, eight reads
+ * of the cell's row.  path = 0: the sort path up to its capacity, else selection; 1 / 2 force one.  Quantiles, counts and
+ * ranks are the same bits on both.  The CRPS needs the sorted sample, so d_crps is refused on the selection path, forced
+ * or by size.  sipnet_quantile_path (host only) is the rule itself: the path a call with this M, element type and path
+ * argument runs (1 or 2), -1 where the call would refuse them.  The call also overwrites two HOST fields of what
+ * sipnet_batch_pf_info reports of the batch's last analysis: fused (1: the sort path ran) and grid (the cells, at most
+ * INT32_MAX); budget, n_slots and the rest keep what the last filter or EnKF analysis left.
+ * Refused with SIPNET_ERR_BAD_ARGUMENT before any launch (sipnet_last_error says why): a NULL batch, series, q or d_quant;
+ * rows < 1 or ld < ncol; n_q outside 1..SIPNET_QUANTILES_MAX; a q that is not finite or
+ * outside [0, 1]; d_crps or d_rank without d_obs; path outside 0..2; path = 1 with M above the capacity; d_crps on the
+ * selection path; live_only on a batch that is not set up.  sipnet_quantile_positions: n < 1, the same n_q and q, a NULL
+ * lo or g.  A batch connected by sipnet_batch_pf_connect is fine: nothing of the batch is written.
+ * The batch's device state (state, rings, parameters) is left bit-identical, as by sipnet_batch_enkf_shard_moments; pending set_params rows are NOT flushed (no
+ * parameter is read).  Everything is enqueued on hip_stream; nothing is synchronised.  No grid barrier, no spin, no
+ * floating-point atomic.
+ * Out of scope: the CLI and the node object; quantiles across ranks (order statistics do not merge from moments); the
+ * CRPS beyond the sort path's capacity; weighted samples; quantiles inside the step kernels' launches. */
+#define SIPNET_QUANTILES_MAX 16
+int32_t sipnet_quantile_lds_members(int32_t elem_is_f32);          /* host only: largest n the one-pass path sorts */
+int32_t sipnet_quantile_path(int32_t n_members, int32_t elem_is_f32, int32_t path); /* host only: 1 sort, 2 selection, -1 refused */
+int sipnet_quantile_positions(int32_t n, int32_t n_q, const double *q,
+                              int32_t *lo, double *g);             /* host only, no device */
+int sipnet_batch_plane_quantiles(sipnet_batch *b, const void *d_series, int32_t elem_is_f32, int32_t rows, int64_t ld,
+                                 int32_t n_q, const double *q /* HOST */, int32_t live_only, int32_t path,
+                                 double *d_quant   /* DEVICE [n_q][rows][n_sites] */,
+                                 int32_t *d_count  /* DEVICE [rows][n_sites], may be NULL */,
+                                 const double *d_obs /* DEVICE [rows][n_sites], may be NULL */,
+                                 double *d_crps    /* DEVICE [rows][n_sites], may be NULL */,
+                                 int32_t *d_rank   /* DEVICE [rows][n_sites][2], may be NULL */,
+                                 void *hip_stream);
+
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------
  * After systematic resampling the ancestors a rank needs from another rank are few (the two ends of its
  * range) and known on the device only; RCCL's send / receive sizes are host arguments, so an all-to-all

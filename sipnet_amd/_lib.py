@@ -207,6 +207,11 @@ SIGNATURES = {
     "sipnet_batch_enkf_shard_moments": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),
     "sipnet_batch_enkf_analysis_sharded": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
                                                      _P, _P, C.c_int32, _P, _P, _P]),
+    "sipnet_quantile_lds_members": (C.c_int32, [C.c_int32]),
+    "sipnet_quantile_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "sipnet_quantile_positions": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P]),
+    "sipnet_batch_plane_quantiles": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32,
+                                               _P, _P, _P, _P, _P, _P]),
     "sipnet_batch_pf_publish": (C.c_int, [_P, C.c_int32, _P]),
     "sipnet_batch_pf_connect": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "sipnet_batch_pf_block_len": (C.c_int64, [_P]),

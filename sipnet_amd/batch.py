@@ -5,12 +5,32 @@ initModel / initEvents / setupModel / runModelOutput / cleanupModel -- for many
 members and sites at once.  Outputs live in torch CUDA tensors that the caller
 (or this class) allocates; the C-ABI only ever sees their raw device pointers.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from ._lib import (F32_MIXED, F64, KERNEL_AUTO, NPARAMS, NREC, NSTATE, RING_SLOTS, Event, LaunchInfo,
                    check, lib)
+
+
+PlaneQuantiles = collections.namedtuple("PlaneQuantiles", "quant count crps rank path")
+
+
+def quantile_lds_members(f32=False):
+    """the largest member count per site that Batch.plane_quantiles' sort path takes (sipnet_quantile_lds_members)"""
+    return int(lib().sipnet_quantile_lds_members(int(bool(f32))))
+
+
+def quantile_positions(n, q):
+    """where the type-7 quantiles q of n sorted values lie (sipnet_quantile_positions, host only): (lo int32 [n_q], g
+    float64 [n_q]) -- Q = x[lo] when g == 0, else x[lo] + g (x[lo + 1] - x[lo]); the expressions the device uses"""
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+    lo = np.zeros(qs.size, dtype=np.int32)
+    g = np.zeros(qs.size)
+    check(lib().sipnet_quantile_positions(int(n), int(qs.size), C.c_void_p(qs.ctypes.data), C.c_void_p(lo.ctypes.data),
+                                          C.c_void_p(g.ctypes.data)), "quantile_positions")
+    return lo, g
 
 
 class Batch:
@@ -204,6 +224,58 @@ class Batch:
                                                C.c_void_p(stats.data_ptr()), self._stream()),
               "reduce_plane")
         return stats
+
+    def plane_quantiles(self, series, q, live_only=True, obs=None, want_crps=None, want_rank=None, path=0, out=None):
+        """Per (row, site) order statistics of a series over each site's members (sipnet_batch_plane_quantiles): the type-7
+        quantiles q (numpy's "linear"), the sample size, and against obs[rows][n_sites] the rank histogram's counts
+        {#(x < y), #(x == y)} and the CRPS.  series: a plane of run(), one of run_sums' arrays or a smoothed series -- any
+        2-D contiguous float32 / float64 device tensor [rows][ld], ld >= ncol.  live_only: only the sites' live members
+        (the batch must have been set up); else all members, and the batch need only exist.  want_crps / want_rank: None =
+        whenever obs is given (the CRPS: and the sort path runs).  path: 0 auto, 1 the sort path (at most
+        quantile_lds_members() members per site), 2 the selection path (any size, no CRPS).  out: a PlaneQuantiles (or a
+        tuple quant, count, crps, rank) of an earlier call to write into.  -> PlaneQuantiles(quant[n_q][rows][n_sites] f64,
+        count[rows][n_sites] i32, crps[rows][n_sites] f64 or None, rank[rows][n_sites][2] i32 or None, path: the one that
+        ran), tensors on the device.  The batch is not changed."""
+        t = self._torch
+        what = "plane_quantiles"
+        if (not t.is_tensor(series) or not series.is_cuda or series.dim() != 2 or series.dtype not in (t.float32, t.float64)
+                or not series.is_contiguous() or series.shape[1] < self.ncol):
+            raise ValueError(f"{what}: series must be a contiguous 2-D float32 / float64 device tensor [rows][ld >= {self.ncol}]")
+        rows, ld = int(series.shape[0]), int(series.shape[1])
+        qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+        n_q = int(qs.size)
+        f32 = int(series.dtype == t.float32)
+        ran = int(self.L.sipnet_quantile_path(self.n_members, f32, int(path)))      # (host only: the library's own rule; -1: the call refuses)
+        if want_crps is None:
+            want_crps = obs is not None and ran == 1
+        if want_rank is None:
+            want_rank = obs is not None
+        if obs is not None:
+            obs = t.as_tensor(obs, dtype=t.float64).to(self.device).contiguous()
+            if obs.numel() != rows * self.n_sites:
+                raise ValueError(f"{what}: obs needs rows x n_sites = {rows * self.n_sites} values, got {obs.numel()}")
+        cells = (rows, self.n_sites)
+        parts = [None] * 4 if out is None else list(out)[:4]
+
+        def part(k, wanted, shape, dtype, name):
+            x = parts[k]
+            if not wanted:
+                return None
+            if x is None:
+                return t.empty(shape, dtype=dtype, device=self.device)
+            if x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or tuple(x.shape) != tuple(shape):
+                raise ValueError(f"{what}: out's {name} must be a contiguous device tensor {tuple(shape)} of {dtype}")
+            return x
+
+        quant = part(0, True, (n_q,) + cells, t.float64, "quant")
+        count = part(1, True, cells, t.int32, "count")
+        crps = part(2, want_crps, cells, t.float64, "crps")
+        rank = part(3, want_rank, cells + (2,), t.int32, "rank")
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
+        check(self.L.sipnet_batch_plane_quantiles(self.h, ptr(series), f32, rows, ld, n_q, C.c_void_p(qs.ctypes.data),
+                                                  int(bool(live_only)), int(path), ptr(quant), ptr(count), ptr(obs),
+                                                  ptr(crps), ptr(rank), self._stream()), what)
+        return PlaneQuantiles(quant, count, crps, rank, ran)
 
     def time_next_launch(self):
         """bracket the next run()'s step kernel with the timing events whatever its length (launches of 512 steps and
