@@ -1203,6 +1203,11 @@ int sipnet_debug_pf_barrier(sipnet_batch *b, int32_t spin_budget, int32_t absent
 /* sipnet_debug_enkf_local_serial: on != 0 makes sipnet_batch_enkf_analysis_local launch one slot at a time in serial
  * order instead of one launch per level (the test of the schedule: the results must not change). */
 int sipnet_debug_enkf_local_serial(sipnet_enkf_local *L, int32_t on);
+/* sipnet_debug_live_bytes: the device memory and the pinned host memory that the library's own objects (batches, nodes,
+ * localizations, the particle filter's per-thread scratch) hold at this moment, process-wide, in bytes as requested from
+ * the runtime -- what sipnet_dev_alloc hands out is the caller's and is not counted.  Either pointer may be NULL.  Back at
+ * its earlier value once everything made since has been destroyed: a leak check that other users of the device do not disturb. */
+int sipnet_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
 
 /* Device buffer helpers for callers without their own allocator (the CLI). */
 void *sipnet_dev_alloc(size_t bytes);

@@ -16,11 +16,11 @@ from .config import (DEFAULT_FLAGS, FLAG_NAMES, PARAM_NAMES, POOLS, enkf_param, 
 from .io import (ClimTable, format_out_header, format_out_row, read_clim, read_events,
                  read_params, read_restart, check_restart, write_debug_logs, write_events_out, write_out,
                  write_restart)
-from .batch import Batch, PlaneQuantiles, quantile_lds_members, quantile_positions
+from .batch import Batch, PlaneQuantiles, debug_live_bytes, quantile_lds_members, quantile_positions
 from .enkf_local import ENKF_BLOCK_MAX_ROWS, EnkfLocalization, enkf_local_rows, enkf_local_schedule, gaspari_cohn
 
 __all__ = [
-    "Batch", "PlaneQuantiles", "quantile_positions", "quantile_lds_members", "EnkfLocalization", "enkf_local_schedule", "enkf_local_rows", "ENKF_BLOCK_MAX_ROWS", "gaspari_cohn", "ClimTable", "Event", "Restart", "SipnetError", "read_restart", "write_restart",
+    "Batch", "PlaneQuantiles", "debug_live_bytes", "quantile_positions", "quantile_lds_members", "EnkfLocalization", "enkf_local_schedule", "enkf_local_rows", "ENKF_BLOCK_MAX_ROWS", "gaspari_cohn", "ClimTable", "Event", "Restart", "SipnetError", "read_restart", "write_restart",
     "check_restart", "lib", "read_clim", "read_params",
     "read_events", "write_out", "write_events_out", "write_debug_logs", "format_out_header", "format_out_row", "read_config",
     "flags_from", "FLAG_NAMES", "POOLS", "enkf_pools", "enkf_plane", "enkf_param", "ENKF_MAX_PARAMS", "ENKF_MAX_SERIES", "DEFAULT_FLAGS", "PARAM_NAMES", "F64", "F32_MIXED",

@@ -281,6 +281,7 @@ SIGNATURES = {
     "sipnet_batch_sums_in_kernel": (C.c_int32, [_P]),
     "sipnet_debug_set_num_cus": (C.c_int, [_P, C.c_int32]),
     "sipnet_debug_pf_barrier": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "sipnet_debug_live_bytes": (C.c_int, [_P, _P]),
     "sipnet_batch_set_device_share": (C.c_int, [_P, C.c_int32]),
     "sipnet_batch_pf_info": (C.c_int, [_P, _P, _P]),
     "sipnet_stream_sync": (C.c_int, [_P]),

@@ -753,3 +753,11 @@ class Batch:
         check(self.L.sipnet_batch_get_site_series(self.h, site, g.ctypes.data, d.ctypes.data),
               "site_series")
         return g, d
+
+
+def debug_live_bytes():
+    """test hook (sipnet_debug_live_bytes): -> (device bytes, pinned host bytes) that the library's own objects hold right now,
+    process-wide; back at an earlier reading once everything made since has been closed"""
+    dev, pin = C.c_int64(0), C.c_int64(0)
+    check(lib().sipnet_debug_live_bytes(C.byref(dev), C.byref(pin)), "debug_live_bytes")
+    return dev.value, pin.value

@@ -9,13 +9,11 @@
 #include <vector>
 
 #include "../../include/sipnet_amd.h"
+#include "dev_buf.h"
 #include "plan.h"
 #include "plan_device.h"
 #include "step_kernel.h"
 
-namespace sipnet {
-void setError(const std::string& s);
-}
 using namespace sipnet;  // internal header: only engine.hip, pf.hip and enkf.hip include it
 
 #define HIP_TRY(expr)                                                         \
@@ -34,19 +32,18 @@ struct PfPeers;
 // that the plan can be rebuilt in any call order and so that the block can leave for the device by an asynchronous copy
 // straight out of sipnet_batch_set_climate (device-built plans, plan_device.h); grow-only.
 struct SiteClim {
-  unsigned char* host = nullptr;
-  unsigned char* dev = nullptr;
-  size_t hostCap = 0, devCap = 0;   // bytes
+  PinnedBuf<unsigned char> host;    // (both blocks: an eighth more than the forcing that made them grow needs)
+  DevBuf<unsigned char> dev;
   int32_t n = 0;                    // records
   bool onDevice = false;            // the device block holds this forcing (a copy is at least queued on upStream)
   hipEvent_t evCopied = nullptr;    // behind that copy: the host may write the pinned block again once it has fired
   bool copyQueued = false;
   static size_t bytesFor(int32_t n) { return (size_t)n * (SIPNET_NCLIM * sizeof(double) + 2 * sizeof(int32_t)); }
-  const double* clim() const { return (const double*)host; }
-  const int32_t* year() const { return (const int32_t*)(host + (size_t)n * SIPNET_NCLIM * sizeof(double)); }
+  const double* clim() const { return (const double*)host.get(); }
+  const int32_t* year() const { return (const int32_t*)(host.get() + (size_t)n * SIPNET_NCLIM * sizeof(double)); }
   const int32_t* day() const { return year() + n; }
-  const double* devClim() const { return (const double*)dev; }
-  const int32_t* devYear() const { return (const int32_t*)(dev + (size_t)n * SIPNET_NCLIM * sizeof(double)); }
+  const double* devClim() const { return (const double*)dev.get(); }
+  const int32_t* devYear() const { return (const int32_t*)(dev.get() + (size_t)n * SIPNET_NCLIM * sizeof(double)); }
   const int32_t* devDay() const { return devYear() + n; }
 };
 
@@ -77,15 +74,11 @@ struct sipnet_batch {
   std::vector<uint8_t> devSite;
   int32_t nDevSites = 0;
   DevPlanArgs devPlan{};
-  unsigned char* d_planScratch = nullptr;
-  size_t planScratchCap = 0;
+  DevBuf<unsigned char> d_planScratch;
   double* d_devLog2 = nullptr;   // [nDevSites][n_steps] inside d_planScratch
-  double* hostLog2 = nullptr;    // pinned staging of the host-computed log2(vpd)
-  size_t hostLog2Cap = 0;
-  double* hostGdd = nullptr;     // pinned [n_sites][n_steps]: trackers.gdd after every record, the plan threads' chain (engine.hip deviceEligible)
-  size_t hostGddCap = 0;
-  unsigned char* hostEv = nullptr;   // pinned, only while a site has events: per site evFirst[n_steps] evCount[n_steps] (int32), dTill[n_steps] tillAfter[n_steps]
-  size_t hostEvCap = 0;
+  PinnedBuf<double> hostLog2;    // pinned staging of the host-computed log2(vpd)
+  PinnedBuf<double> hostGdd;     // pinned [n_sites][n_steps]: trackers.gdd after every record, the plan threads' chain (engine.hip deviceEligible)
+  PinnedBuf<unsigned char> hostEv;   // pinned, only while a site has events: per site evFirst[n_steps] evCount[n_steps] (int32), dTill[n_steps] tillAfter[n_steps]
   std::vector<PlanLight> planLight;  // per site: the plan threads' pass before the records are built (engine.hip devicePrepass)
   bool devLog2Done = false;
   int32_t devPlanMaxSteps = 0;
@@ -93,28 +86,27 @@ struct sipnet_batch {
   bool planKernelsQueued = false;
 
   // HBM
-  double* d_rawStage = nullptr;  // [rawStageCap][NPARAMS] raw rows of the set_params calls since the last launch
-  size_t rawStageCap = 0;
+  DevBuf<double> d_rawStage;     // [rows][NPARAMS] raw rows of the set_params calls since the last launch
   // set_params is host-only: the raw rows go into PINNED staging and a list of pending conversions; the next
   // stream-taking entry point (setup, run, the particle filter's) uploads and converts them on ITS stream -- no
   // kernel of this batch then runs, and nothing of it blocks, while another batch's step kernel fills the device
   // (a conversion kernel on a stream of its own, and synchronous copies, were measured stuck behind that kernel)
-  double* hostRaw = nullptr;     // pinned [hostRawCap][NPARAMS]
-  size_t hostRawCap = 0, hostRawUsed = 0;
+  PinnedBuf<double> hostRaw;     // pinned [rows][NPARAMS]
+  size_t hostRawUsed = 0;        // rows
   struct PendingParams { size_t row0; int64_t col0; int32_t count, nRep; };
   std::vector<PendingParams> pendingParams;
-  double* d_prm = nullptr;     // [NPARAMS][ncol] converted parameters: the one copy on the device
-  double* d_state = nullptr;   // [NSTATE][ncol]
-  double* d_ring = nullptr;    // [RING_SLOTS][ncol] doubles; fp32-mixed batches: floats (ringElemBytes)
+  DevBuf<double> d_prm;        // [NPARAMS][ncol] converted parameters: the one copy on the device
+  DevBuf<double> d_state;      // [NSTATE][ncol]
+  DevBuf<double> d_ring;       // [RING_SLOTS][ncol] doubles; fp32-mixed batches: floats (ringElemBytes)
   // second copies for particle-filter resampling (gather into the spare, then swap); lazily made
-  double* d_prm2 = nullptr;
+  DevBuf<double> d_prm2;
   // Particle filter (round 5): converted parameters are read-only during a forecast, so a resampling of a filter whose
   // particles carry their parameters need not MOVE 640 bytes per particle -- it moves an index.  prmIndexed: column c's
   // parameters are column d_prmId[c] of d_prm (the parameter BANK: a row set once by set_params, never copied);
   // the one-wave step kernel dereferences the index at launch start (FastArgs::prmId), every other reader of d_prm
   // first gets the bank gathered back into column order (materializeParams).  Not indexed: d_prmId is unused.
-  int32_t* d_prmId = nullptr;
-  int32_t* d_prmId2 = nullptr;
+  DevBuf<int32_t> d_prmId;
+  DevBuf<int32_t> d_prmId2;
   bool prmIndexed = false;
   // A filter spread over ranks whose particles carry their parameters (round 6): every rank holds a copy of ALL ranks'
   // converted parameters, [NPARAMS][world * nmax] (slot = rank * nmax + particle; sipnet_batch_pf_connect fills it once
@@ -122,7 +114,7 @@ struct sipnet_batch {
   // across ranks moves 4 bytes of index per particle instead of 640 bytes of rows, and the forecast reads local HBM.
   // While d_prmBank is set, d_prmId / d_prmId2 are always maintained (peers read them); prmIndexed then only says that
   // d_prm, the column-order copy every kernel but the one-wave kernel reads, is behind the index.
-  double* d_prmBank = nullptr;
+  DevBuf<double> d_prmBank;
   int64_t prmBankPitch = 0;
   // how many filters may run their one-launch analysis on this device at the same time (a node's shards on one device):
   // the spinning grid is sized to 1 / deviceShare of what the device holds (pf.hip fusedBudget)
@@ -130,29 +122,26 @@ struct sipnet_batch {
   int32_t pfSpinBudget = 0;      // polls a barrier waits before it declares the launch void (0: SIPNET_PF_SPIN_BUDGET)
   int32_t pfDebugAbsent = -1;    // test hook: this workgroup of the NEXT fused launch leaves without arriving
   struct PfInfo { int32_t fused = 0, grid = 0, budget = 0; int64_t nSlots = 0, cycles = 0; } pfInfo;
-  unsigned long long* d_pfCrossing = nullptr;   // particles this rank has copied from ANOTHER rank's slot, all cycles
-  double* d_state2 = nullptr;
-  double* d_ring2 = nullptr;
-  StepRec* d_plan = nullptr;   // [n_sites][n_steps]
-  FastRec* d_fast = nullptr;   // [n_sites][n_steps] + kFastTile padding records
-  double* d_scratchRow = nullptr;  // [ncol]
-  RingOp* d_ringOps = nullptr;
-  EvRec* d_events = nullptr;
-  int32_t* d_siteStatus = nullptr;
-  double* d_statsPart = nullptr;     // [3][chunks][n_steps of the launch][2]: per-chunk plane statistics
-  size_t statsPartCap = 0;           //   (sipnet_batch_run_stats on a cooperative kernel), doubles
-  double* d_diag = nullptr;          // [4][ncol] per-member diagnostics, allocated on request
-  SiteStart* d_siteStart = nullptr;  // [n_sites] what setupModel() reads of a site's first record
-  size_t planCap = 0, fastCap = 0, ringOpCap = 0, evCap = 0;
+  DevBuf<unsigned long long> d_pfCrossing;      // particles this rank has copied from ANOTHER rank's slot, all cycles
+  DevBuf<double> d_state2;
+  DevBuf<double> d_ring2;
+  DevBuf<StepRec> d_plan;      // [n_sites][n_steps]
+  DevBuf<FastRec> d_fast;      // [n_sites][n_steps] + kFastTile padding records
+  DevBuf<double> d_scratchRow;     // [ncol]
+  DevBuf<RingOp> d_ringOps;
+  DevBuf<EvRec> d_events;
+  DevBuf<int32_t> d_siteStatus;
+  DevBuf<double> d_statsPart;        // [3][chunks][n_steps of the launch][2]: per-chunk plane statistics
+                                     //   (sipnet_batch_run_stats on a cooperative kernel)
+  DevBuf<double> d_diag;             // [4][ncol] per-member diagnostics, allocated on request
+  DevBuf<SiteStart> d_siteStart;     // [n_sites] what setupModel() reads of a site's first record
   // host staging of the flat per-step records, kept between hand-overs of a forcing: a fresh buffer
   // costs its first touch (143 MB at c4: 24 ms of page faults, more than building the records)
   // (pinned: the sites' records leave by hipMemcpyAsync on the setup's stream as the worker threads finish them)
-  FastRec* hostFast = nullptr;
-  StepRec* hostSteps = nullptr;
-  size_t hostFastCap = 0, hostStepsCap = 0;
-  unsigned char* hostMisc = nullptr;   // pinned staging of the small per-plan arrays (ring evictions, events, site tables)
-  size_t hostMiscCap = 0;
-  int32_t* d_siteBase = nullptr;  // [n_sites][3]: offset of a site's ring ops / events in the flat arrays, its number of records
+  PinnedBuf<FastRec> hostFast;
+  PinnedBuf<StepRec> hostSteps;
+  PinnedBuf<unsigned char> hostMisc;   // pinned staging of the small per-plan arrays (ring evictions, events, site tables)
+  DevBuf<int32_t> d_siteBase;     // [n_sites][3]: offset of a site's ring ops / events in the flat arrays, its number of records
   bool stepRecsUploaded = false, fastRecsUploaded = false;  // per-step records: uploaded on first use
   // last boundary a checkpoint was exported at (sipnet_batch_export_restart)
   int32_t exportCacheSite = -1, exportCacheN = -1;
@@ -171,8 +160,7 @@ struct sipnet_batch {
   struct PfArm { bool set = false; double obs = 0.0, sigma = 0.0; double* d_logw = nullptr; } pfArm;
   struct PfPre { bool valid = false; const void* plane = nullptr; int32_t nSteps = 0, nMax = 0; int64_t ld = 0; double obs = 0.0, sigma = 0.0;
                  double* d_logw = nullptr; } pfPre;
-  double* d_pfPreMax = nullptr;   // [workgroups of the one-wave launch]: their columns' largest log-weight
-  size_t pfPreMaxCap = 0;
+  DevBuf<double> d_pfPreMax;      // [workgroups of the one-wave launch]: their columns' largest log-weight
   bool timeNext = false;   // sipnet_batch_time_next_launch: the next step kernel is bracketed by the timing events whatever its length
   double lastMs = -1.0;
   // recorded behind every launch of this batch that reads its inputs (setupModel, a step kernel): what an upload
@@ -190,16 +178,13 @@ struct sipnet_batch {
   hipStream_t upStream = nullptr;
   // the three sipnet_batch_enkf_analysis_* calls (enkf.hip): their scratch block (working copies, partial sums, site
   // statistics, the block-local matrices, counts and codes), grow-only
-  void* d_enkf = nullptr;
-  size_t enkfBytes = 0;
+  DevBuf<unsigned char> d_enkf;
   // sipnet_batch_enkf_analysis_smooth's series stage: a block of its own (the h, their anomalies, g and G), grow-only
-  void* d_smooth = nullptr;
-  size_t smoothBytes = 0;
+  DevBuf<unsigned char> d_smooth;
 };
 int flushParams(sipnet_batch* b, hipStream_t stream);   // engine.hip: upload + convert what set_params left pending
 int materializeParams(sipnet_batch* b, hipStream_t stream);   // pf.hip: d_prm back into column order (no-op unless prmIndexed)
 void pfDropBank(sipnet_batch* b);   // pf.hip: a connected filter's bank of all ranks' parameters is void (new parameters, moved rows)
-void enkfRelease(sipnet_batch* b);   // enkf.hip: frees the analysis scratch (called by sipnet_batch_destroy)
 
 // "This batch has work in flight on `stream`."  The event itself is recorded only when somebody needs it (a wait from
 // another stream, a host-side wait or query): work queued later on the SAME stream is ordered behind it anyway, and an
@@ -286,8 +271,13 @@ inline int waitStaged(sipnet_batch* b) {
 inline size_t ringElemBytes(const sipnet_batch* b) {
   return b->precision == SIPNET_F32_MIXED ? sizeof(float) : sizeof(double);
 }
+// the ring block (d_ring, d_ring2) in the doubles its buffer counts: [RING_SLOTS][ncol] elements of either width
+static_assert(SIPNET_RING_SLOTS % 2 == 0, "a ring of floats fills whole doubles");
+inline size_t ringDoubles(const sipnet_batch* b) {
+  return (size_t)b->ncol * SIPNET_RING_SLOTS * ringElemBytes(b) / sizeof(double);
+}
 
-void pfRelease(sipnet_batch* b);   // pf.hip: frees pfScratch / pfPeers (called by sipnet_batch_destroy, device current)
+void pfRelease(sipnet_batch* b);   // pf.hip: pfScratch / pfPeers go (device current)
 
 inline int useDevice(const sipnet_batch* b) {
   HIP_TRY(hipSetDevice(b->device));

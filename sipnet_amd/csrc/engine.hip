@@ -73,17 +73,9 @@ static void forEachSite(int nS, int nThreads, std::atomic<bool>* failed, F f) {
 // device buffer for `count` records; a launch that still reads the previous plan (on any stream)
 // must have finished before the first site's records land in it
 template <class Rec>
-static int reserveRecords(sipnet_batch* b, Rec** d_ptr, size_t* cap, size_t count) {
-  if (count > *cap) {
-    int rcIdle = waitIdle(b);
-    if (rcIdle) return rcIdle;
-    if (*d_ptr) HIP_TRY(hipFree(*d_ptr));
-    *d_ptr = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(d_ptr, count * sizeof(Rec)));
-    *cap = count;
-  }
-  return SIPNET_OK;
+static int reserveRecords(sipnet_batch* b, DevBuf<Rec>& buf, size_t count) {
+  if (count > buf.capacity()) RC_TRY(waitIdle(b));
+  return buf.reserve(count);
 }
 
 // Which record type the next launch will read, as far as it is known at setup time: the
@@ -95,18 +87,8 @@ static bool wantsFastRecs(const sipnet_batch* b) {
 // One pass per site (buildSitePlan) writes the record type the batch is set up for straight
 // into the flat upload buffer; the other type is produced by a second pass only if a launch ever
 // asks for it (ensureRecords).
-// pinned host block of at least `count` records (kept between hand-overs of a forcing: a fresh buffer costs its
+// (the pinned host blocks are kept between hand-overs of a forcing: a fresh buffer costs its
 // first touch -- 143 MB at c4: 24 ms of page faults, more than building the records -- and its pinning)
-template <class Rec>
-static int reservePinned(Rec** ptr, size_t* cap, size_t count) {
-  if (count <= *cap) return SIPNET_OK;
-  if (*ptr) HIP_TRY(hipHostFree(*ptr));
-  *ptr = nullptr;
-  *cap = 0;
-  HIP_TRY(hipHostMalloc((void**)ptr, count * sizeof(Rec), hipHostMallocDefault));
-  *cap = count;
-  return SIPNET_OK;
-}
 
 // uploads travel on the batch's own copy stream (nothing but copies is ever queued on it, so they are not held up
 // behind another batch's step kernel in a shared hardware queue); the caller's stream waits for them
@@ -133,14 +115,9 @@ static bool mayBuildOnDevice(const sipnet_batch* b) {
 static int sendClimate(sipnet_batch* b, int32_t site) {
   SiteClim& c = b->sc[site];
   const size_t bytes = SiteClim::bytesFor(c.n);
-  if (bytes > c.devCap) {
+  if (bytes > c.dev.capacity()) {
     if (b->planKernelsQueued) HIP_TRY(hipEventSynchronize(b->evPlanDone));
-    if (c.dev) HIP_TRY(hipFree(c.dev));
-    c.dev = nullptr;
-    c.devCap = 0;
-    const size_t cap = bytes + bytes / 8;
-    HIP_TRY(hipMalloc((void**)&c.dev, cap));
-    c.devCap = cap;
+    RC_TRY(c.dev.reserve(bytes + bytes / 8));
   }
   if (b->planKernelsQueued) HIP_TRY(hipStreamWaitEvent(b->upStream, b->evPlanDone, 0));
   HIP_TRY(hipMemcpyAsync(c.dev, c.host, bytes, hipMemcpyHostToDevice, b->upStream));
@@ -159,7 +136,7 @@ static int sendClimate(sipnet_batch* b, int32_t site) {
 static bool devicePrepass(sipnet_batch* b, int32_t s, PlanLight* out) {
   const SiteClim& c = b->sc[s];
   const size_t nT = (size_t)b->n_steps;
-  const bool ev = b->hostEv != nullptr;
+  const bool ev = b->hostEv.get() != nullptr;
   unsigned char* e = ev ? b->hostEv + (size_t)s * nT * 24 : nullptr;
   const PlanCarry* init = b->resume[s].set ? &b->resume[s] : nullptr;
   *out = buildSitePlanLight(b->flags, c.n, c.clim(), c.year(), c.day(), (int32_t)b->events[s].size(), b->events[s].data(), init,
@@ -195,13 +172,13 @@ static int buildAndUpload(sipnet_batch* b, bool fastType, bool first, hipStream_
   // once that launch has finished, instead of as they are built
   int rc = waitStaged(b);
   if (rc) return rc;
-  rc = fastType ? reserveRecords(b, &b->d_fast, &b->fastCap, nFast) : reserveRecords(b, &b->d_plan, &b->planCap, nSteps);
+  rc = fastType ? reserveRecords(b, b->d_fast, nFast) : reserveRecords(b, b->d_plan, nSteps);
   if (rc) return rc;
   const bool deferCopies = stillRunning(b);
   // (sites whose records the device builds itself need no staging: plan_device.h)
   const bool devPass = fastType && first && b->nDevSites > 0;
   const bool anyHostSite = !devPass || b->nDevSites < nS;
-  if (anyHostSite) rc = fastType ? reservePinned(&b->hostFast, &b->hostFastCap, nFast) : reservePinned(&b->hostSteps, &b->hostStepsCap, nSteps);
+  if (anyHostSite) rc = fastType ? b->hostFast.reserve(nFast) : b->hostSteps.reserve(nSteps);
   if (rc) return rc;
   TRACE_T("plan: reserved");
   FastRec* const fast = b->hostFast;
@@ -297,7 +274,7 @@ static int fillDeviceLog2(sipnet_batch* b, hipStream_t stream) {
   const int nS = b->n_sites, nT = b->n_steps, nDev = b->nDevSites;
   int rc = waitStaged(b);
   if (rc) return rc;
-  rc = reservePinned(&b->hostLog2, &b->hostLog2Cap, (size_t)nDev * nT);
+  rc = b->hostLog2.reserve((size_t)nDev * nT);
   if (rc) return rc;
   std::vector<int> siteOf;
   for (int s = 0; s < nS; s++)
@@ -347,13 +324,9 @@ static int buildOnDevice(sipnet_batch* b, const std::vector<int32_t>& bases, hip
                total = offEv + (b->hostEv ? align(perStep * 24) : 0);
   // (the events block: evFirst[nDev][nT], evCount[nDev][nT], dTill[nDev][nT], tillAfter[nDev][nT])
   const size_t offEvCount = offEv + perStep * 4, offDTill = offEv + perStep * 8, offTillAfter = offEv + perStep * 16;
-  if (total > b->planScratchCap) {
+  if (total > b->d_planScratch.capacity()) {
     if (b->planKernelsQueued) HIP_TRY(hipEventSynchronize(b->evPlanDone));
-    if (b->d_planScratch) HIP_TRY(hipFree(b->d_planScratch));
-    b->d_planScratch = nullptr;
-    b->planScratchCap = 0;
-    HIP_TRY(hipMalloc((void**)&b->d_planScratch, total));
-    b->planScratchCap = total;
+    RC_TRY(b->d_planScratch.reserve(total));
   }
   // the site table (pinned staging: the small-array block is free again only after its copies, so a block of its own)
   std::vector<DevPlanSite> tab(nDev);
@@ -482,18 +455,16 @@ static int uploadPlan(sipnet_batch* b, hipStream_t stream) {
   if (mayBuildOnDevice(b)) {
     int rcW = waitStaged(b);   // (the previous hand-over's copies out of the staging blocks)
     if (rcW) return rcW;
-    rcW = reservePinned(&b->hostGdd, &b->hostGddCap, (size_t)nS * b->n_steps);
+    rcW = b->hostGdd.reserve((size_t)nS * b->n_steps);
     if (rcW) return rcW;
     bool anyEvents = false;
     for (int s = 0; s < nS; s++)
       anyEvents |= (b->flags[SIPNET_F_EVENTS] && !b->events[s].empty()) || (b->resume[s].set && b->resume[s].dTill != 0.0);
     if (anyEvents) {
-      rcW = reservePinned(&b->hostEv, &b->hostEvCap, (size_t)nS * b->n_steps * 24);
+      rcW = b->hostEv.reserve((size_t)nS * b->n_steps * 24);
       if (rcW) return rcW;
     } else if (b->hostEv) {   // (no site has events this time: the block is not looked at)
-      HIP_TRY(hipHostFree(b->hostEv));
-      b->hostEv = nullptr;
-      b->hostEvCap = 0;
+      HIP_TRY(b->hostEv.release());
     }
     b->planLight.assign(nS, PlanLight{});
     std::atomic<bool> none{false};
@@ -527,20 +498,8 @@ static int uploadPlan(sipnet_batch* b, hipStream_t stream) {
     starts[s] = SiteStart{p.startCumGdd, p.startTsoil, p.startDayTime};
   }
   const double t1 = nowMs();
-  if (nOps + 1 > b->ringOpCap) {
-    if (b->d_ringOps) HIP_TRY(hipFree(b->d_ringOps));
-    b->d_ringOps = nullptr;
-    b->ringOpCap = 0;
-    HIP_TRY(hipMalloc(&b->d_ringOps, (nOps + 1) * sizeof(RingOp)));
-    b->ringOpCap = nOps + 1;
-  }
-  if (nEv + 1 > b->evCap) {
-    if (b->d_events) HIP_TRY(hipFree(b->d_events));
-    b->d_events = nullptr;
-    b->evCap = 0;
-    HIP_TRY(hipMalloc(&b->d_events, (nEv + 1) * sizeof(EvRec)));
-    b->evCap = nEv + 1;
-  }
+  RC_TRY(b->d_ringOps.reserve(nOps + 1));
+  RC_TRY(b->d_events.reserve(nEv + 1));
   // the small arrays: flattened into one pinned block and sent on the same stream (buildAndUpload has waited for
   // every launch that might still read the previous plan; an empty list keeps one inert entry)
   // (ring evictions: the HOST-built sites' only -- a device-built site's list is written by its walk, and its room in the flat
@@ -552,9 +511,9 @@ static int uploadPlan(sipnet_batch* b, hipStream_t stream) {
   auto align16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t offEv = align16(opsBytes), offStatus = offEv + align16(evBytes), offStart = offStatus + align16(nS * sizeof(int32_t)),
                offBase = offStart + align16(nS * sizeof(SiteStart)), total = offBase + align16(bases.size() * sizeof(int32_t));
-  rc = reservePinned(&b->hostMisc, &b->hostMiscCap, total);
+  rc = b->hostMisc.reserve(total);
   if (rc) return rc;
-  RingOp* hOps = (RingOp*)b->hostMisc;
+  RingOp* hOps = (RingOp*)b->hostMisc.get();
   EvRec* hEv = (EvRec*)(b->hostMisc + offEv);
   std::vector<size_t> hostOff(nS, 0);
   {
@@ -638,7 +597,7 @@ static int ringToHost(sipnet_batch* b, int64_t col0, int64_t ncols, double* out)
     return SIPNET_OK;
   }
   std::vector<float> tmp((size_t)ncols * SIPNET_RING_SLOTS);
-  HIP_TRY(hipMemcpy2D(tmp.data(), (size_t)ncols * eb, (const float*)b->d_ring + col0, (size_t)b->ncol * eb,
+  HIP_TRY(hipMemcpy2D(tmp.data(), (size_t)ncols * eb, (const float*)b->d_ring.get() + col0, (size_t)b->ncol * eb,
                       (size_t)ncols * eb, SIPNET_RING_SLOTS, hipMemcpyDeviceToHost));
   for (size_t i = 0; i < tmp.size(); i++) out[i] = (double)tmp[i];
   return SIPNET_OK;
@@ -652,7 +611,7 @@ static int ringFromHost(sipnet_batch* b, int64_t col0, int64_t ncols, const doub
   }
   std::vector<float> tmp((size_t)ncols * SIPNET_RING_SLOTS);
   for (size_t i = 0; i < tmp.size(); i++) tmp[i] = (float)in[i];
-  HIP_TRY(hipMemcpy2D((float*)b->d_ring + col0, (size_t)b->ncol * eb, tmp.data(), (size_t)ncols * eb,
+  HIP_TRY(hipMemcpy2D((float*)b->d_ring.get() + col0, (size_t)b->ncol * eb, tmp.data(), (size_t)ncols * eb,
                       (size_t)ncols * eb, SIPNET_RING_SLOTS, hipMemcpyHostToDevice));
   return SIPNET_OK;
 }
@@ -751,13 +710,13 @@ int sipnet_batch_create(const int32_t* flags, int32_t n_sites, int32_t n_members
   if (rc) { delete b; return rc; }
   const size_t nc = (size_t)b->ncol;
   hipError_t e = hipSuccess;
-  if (e == hipSuccess) e = hipMalloc(&b->d_prm, nc * SIPNET_NPARAMS * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&b->d_state, nc * SIPNET_NSTATE * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&b->d_ring, nc * SIPNET_RING_SLOTS * ringElemBytes(b));
-  if (e == hipSuccess) e = hipMalloc(&b->d_siteStatus, n_sites * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&b->d_siteStart, n_sites * sizeof(SiteStart));
-  if (e == hipSuccess) e = hipMalloc(&b->d_siteBase, (size_t)3 * n_sites * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&b->d_scratchRow, nc * sizeof(double));
+  if (e == hipSuccess) e = b->d_prm.tryReserve(nc * SIPNET_NPARAMS);
+  if (e == hipSuccess) e = b->d_state.tryReserve(nc * SIPNET_NSTATE);
+  if (e == hipSuccess) e = b->d_ring.tryReserve(ringDoubles(b));
+  if (e == hipSuccess) e = b->d_siteStatus.tryReserve(n_sites);
+  if (e == hipSuccess) e = b->d_siteStart.tryReserve(n_sites);
+  if (e == hipSuccess) e = b->d_siteBase.tryReserve((size_t)3 * n_sites);
+  if (e == hipSuccess) e = b->d_scratchRow.tryReserve(nc);
   if (e == hipSuccess) e = hipMemset(b->d_prm, 0, nc * SIPNET_NPARAMS * sizeof(double));
   if (e == hipSuccess) e = hipMemset(b->d_state, 0, nc * SIPNET_NSTATE * sizeof(double));
   if (e == hipSuccess) e = hipEventCreate(&b->ev0);
@@ -780,43 +739,9 @@ void sipnet_batch_destroy(sipnet_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   pfRelease(b);
-  enkfRelease(b);
-  if (b->d_rawStage) (void)hipFree(b->d_rawStage);
-  if (b->hostRaw) (void)hipHostFree(b->hostRaw);
-  if (b->hostFast) (void)hipHostFree(b->hostFast);
-  if (b->hostSteps) (void)hipHostFree(b->hostSteps);
-  if (b->hostMisc) (void)hipHostFree(b->hostMisc);
-  if (b->hostLog2) (void)hipHostFree(b->hostLog2);
-  if (b->hostGdd) (void)hipHostFree(b->hostGdd);
-  if (b->hostEv) (void)hipHostFree(b->hostEv);
-  for (SiteClim& c : b->sc) {
-    if (c.host) (void)hipHostFree(c.host);
-    if (c.dev) (void)hipFree(c.dev);
+  for (SiteClim& c : b->sc)
     if (c.evCopied) (void)hipEventDestroy(c.evCopied);
-  }
-  if (b->d_planScratch) (void)hipFree(b->d_planScratch);
   if (b->evPlanDone) (void)hipEventDestroy(b->evPlanDone);
-  if (b->d_prm) (void)hipFree(b->d_prm);
-  if (b->d_state) (void)hipFree(b->d_state);
-  if (b->d_ring) (void)hipFree(b->d_ring);
-  if (b->d_prm2) (void)hipFree(b->d_prm2);
-  if (b->d_prmId) (void)hipFree(b->d_prmId);
-  if (b->d_prmId2) (void)hipFree(b->d_prmId2);
-  if (b->d_prmBank) (void)hipFree(b->d_prmBank);
-  if (b->d_pfCrossing) (void)hipFree(b->d_pfCrossing);
-  if (b->d_state2) (void)hipFree(b->d_state2);
-  if (b->d_ring2) (void)hipFree(b->d_ring2);
-  if (b->d_plan) (void)hipFree(b->d_plan);
-  if (b->d_fast) (void)hipFree(b->d_fast);
-  if (b->d_scratchRow) (void)hipFree(b->d_scratchRow);
-  if (b->d_ringOps) (void)hipFree(b->d_ringOps);
-  if (b->d_events) (void)hipFree(b->d_events);
-  if (b->d_siteStatus) (void)hipFree(b->d_siteStatus);
-  if (b->d_siteStart) (void)hipFree(b->d_siteStart);
-  if (b->d_siteBase) (void)hipFree(b->d_siteBase);
-  if (b->d_diag) (void)hipFree(b->d_diag);
-  if (b->d_pfPreMax) (void)hipFree(b->d_pfPreMax);
-  if (b->d_statsPart) (void)hipFree(b->d_statsPart);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   if (b->evBusy) (void)hipEventDestroy(b->evBusy);
@@ -834,14 +759,7 @@ static int climateReserve(sipnet_batch* b, int32_t site, int32_t n_steps) {
   // the previous forcing's copy out of this block must be through before the host writes it again
   if (c.copyQueued) HIP_TRY(hipEventSynchronize(c.evCopied));
   c.copyQueued = false;
-  if (bytes > c.hostCap) {
-    if (c.host) HIP_TRY(hipHostFree(c.host));
-    c.host = nullptr;
-    c.hostCap = 0;
-    const size_t cap = bytes + bytes / 8;
-    HIP_TRY(hipHostMalloc((void**)&c.host, cap, hipHostMallocDefault));
-    c.hostCap = cap;
-  }
+  if (bytes > c.host.capacity()) RC_TRY(c.host.reserve(bytes + bytes / 8));
   c.n = n_steps;
   c.onDevice = false;
   return SIPNET_OK;
@@ -962,14 +880,12 @@ int sipnet_batch_set_params(sipnet_batch* b, int32_t site, int32_t first_member,
   rc = waitStaged(b);
   if (rc) return rc;
   const size_t need = b->hostRawUsed + (size_t)count;
-  if (need > b->hostRawCap) {
-    double* bigger = nullptr;
-    const size_t cap = need > 2 * b->hostRawCap ? need : 2 * b->hostRawCap;
-    HIP_TRY(hipHostMalloc((void**)&bigger, cap * SIPNET_NPARAMS * sizeof(double), hipHostMallocDefault));
+  const size_t rawCap = b->hostRaw.capacity() / SIPNET_NPARAMS;   // rows
+  if (need > rawCap) {   // (the one block that keeps its contents when it grows: into a fresh one, at least twice as large)
+    PinnedBuf<double> bigger;
+    RC_TRY(bigger.reserve((need > 2 * rawCap ? need : 2 * rawCap) * SIPNET_NPARAMS));
     if (b->hostRawUsed) memcpy(bigger, b->hostRaw, b->hostRawUsed * SIPNET_NPARAMS * sizeof(double));
-    if (b->hostRaw) HIP_TRY(hipHostFree(b->hostRaw));
-    b->hostRaw = bigger;
-    b->hostRawCap = cap;
+    b->hostRaw = std::move(bigger);
   }
   memcpy(b->hostRaw + b->hostRawUsed * SIPNET_NPARAMS, raw, (size_t)count * SIPNET_NPARAMS * sizeof(double));
   b->pendingParams.push_back({b->hostRawUsed, col0, count, nRep});
@@ -990,14 +906,9 @@ int flushParams(sipnet_batch* b, hipStream_t stream) {
     // (... and the copy of this rank's parameters that a connected filter's peers hold is out of date: connect again)
     pfDropBank(b);
   }
-  if (b->hostRawUsed > b->rawStageCap) {
-    int rcI = waitIdle(b);
-    if (rcI) return rcI;
-    if (b->d_rawStage) HIP_TRY(hipFree(b->d_rawStage));
-    b->d_rawStage = nullptr;
-    b->rawStageCap = 0;
-    HIP_TRY(hipMalloc(&b->d_rawStage, b->hostRawUsed * SIPNET_NPARAMS * sizeof(double)));
-    b->rawStageCap = b->hostRawUsed;
+  if (b->hostRawUsed * SIPNET_NPARAMS > b->d_rawStage.capacity()) {
+    RC_TRY(waitIdle(b));
+    RC_TRY(b->d_rawStage.reserve(b->hostRawUsed * SIPNET_NPARAMS));
   }
   // The conversion writes d_prm: it must not start while this batch's last launch -- possibly on ANOTHER stream of
   // the caller's (a node shard's, the null stream of pf_publish) -- still reads it.  A device-side wait, no host stall.
@@ -1117,17 +1028,22 @@ int sipnet_debug_pf_barrier(sipnet_batch* b, int32_t spin_budget, int32_t absent
   return SIPNET_OK;
 }
 
+int sipnet_debug_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes) {
+  if (device_bytes) *device_bytes = g_liveDeviceBytes.load();
+  if (pinned_bytes) *pinned_bytes = g_livePinnedBytes.load();
+  return SIPNET_OK;
+}
+
 int sipnet_batch_enable_diagnostics(sipnet_batch* b, int32_t on) {
   if (!b) return SIPNET_ERR_BAD_ARGUMENT;
   int rc = useDevice(b);
   if (rc) return rc;
   if (on && !b->d_diag) {
-    HIP_TRY(hipMalloc(&b->d_diag, (size_t)4 * b->ncol * sizeof(double)));
+    RC_TRY(b->d_diag.reserve((size_t)4 * b->ncol));
     HIP_TRY(hipMemset(b->d_diag, 0, (size_t)4 * b->ncol * sizeof(double)));
   } else if (!on && b->d_diag) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree(b->d_diag));
-    b->d_diag = nullptr;
+    HIP_TRY(b->d_diag.release());
   }
   return SIPNET_OK;
 }
@@ -1315,13 +1231,9 @@ static int runImpl(sipnet_batch* b, int32_t step0, int32_t n_steps, void* d_nee,
   const int chunksPerSite = (b->n_members + 63) / 64;
   if (d_stats && coop) {
     const size_t need = (size_t)3 * b->n_sites * chunksPerSite * n_steps * 2;
-    if (need > b->statsPartCap) {
+    if (need > b->d_statsPart.capacity()) {
       HIP_TRY(hipStreamSynchronize(stream));
-      if (b->d_statsPart) HIP_TRY(hipFree(b->d_statsPart));
-      b->d_statsPart = nullptr;
-      b->statsPartCap = 0;
-      HIP_TRY(hipMalloc(&b->d_statsPart, need * sizeof(double)));
-      b->statsPartCap = need;
+      RC_TRY(b->d_statsPart.reserve(need));
     }
     // sites of different lengths: the rows past a site's last record are never written -- zero sums there
     bool ragged = false;
@@ -1365,13 +1277,7 @@ static int runImpl(sipnet_batch* b, int32_t step0, int32_t n_steps, void* d_nee,
       bool sameLength = true;
       for (int s = 0; s < b->n_sites; s++) sameLength = sameLength && b->siteSteps[s] >= step0 + n_steps;
       if (kernel == SIPNET_KERNEL_ONE_WAVE && !wantFull && d_nee && sameLength) {
-        if ((size_t)blocks1 > b->pfPreMaxCap) {
-          if (b->d_pfPreMax) HIP_TRY(hipFree(b->d_pfPreMax));
-          b->d_pfPreMax = nullptr;
-          b->pfPreMaxCap = 0;
-          HIP_TRY(hipMalloc((void**)&b->d_pfPreMax, (size_t)blocks1 * sizeof(double)));
-          b->pfPreMaxCap = (size_t)blocks1;
-        }
+        RC_TRY(b->d_pfPreMax.reserve((size_t)blocks1));
         f.pfLogw = b->pfArm.d_logw;
         f.pfBlockMax = b->d_pfPreMax;
         f.pfObs = b->pfArm.obs;

@@ -62,21 +62,12 @@ struct sipnet_enkf_local {
   std::vector<int64_t> levelOff;           // [nLevels + 1]: the pairs of level l are [levelOff[l], levelOff[l + 1])
   std::vector<int64_t> slotOff;            // [n_sites][n_obs]: where slot (s, i)'s 1 + deg(s) pairs start
   std::vector<int32_t> slotLen;
-  LocalPair* d_pair = nullptr;
-  int64_t* d_inPtr = nullptr;              // [n_sites + 1]: site t is a neighbour of the sites d_in[d_inPtr[t] ..)
-  int32_t* d_in = nullptr;
-  double* d_inRho = nullptr;               // the tapers rho_ut in d_in's order
+  DevBuf<LocalPair> d_pair;
+  DevBuf<int64_t> d_inPtr;                 // [n_sites + 1]: site t is a neighbour of the sites d_in[d_inPtr[t] ..)
+  DevBuf<int32_t> d_in;
+  DevBuf<double> d_inRho;                  // the tapers rho_ut in d_in's order
   int32_t maxRows = 0;                     // the block-local analysis: the largest n_obs x (1 + in-neighbours) of a site
 };
-
-void enkfRelease(sipnet_batch* b) {
-  if (b->d_enkf) (void)hipFree(b->d_enkf);
-  b->d_enkf = nullptr;
-  b->enkfBytes = 0;
-  if (b->d_smooth) (void)hipFree(b->d_smooth);
-  b->d_smooth = nullptr;
-  b->smoothBytes = 0;
-}
 
 namespace {
 
@@ -201,14 +192,14 @@ int ldsGranted(const void* kernel, size_t dynBytes, int device, bool* ok) {
   return 0;
 }
 
-// A scratch block of the batch (*block of *blockBytes: b->d_enkf, or the series stage's b->d_smooth) sized, grown and carved, in
+// A scratch block of the batch (b->d_enkf, or the series stage's b->d_smooth) sized, grown and carved, in
 // this order: the working copies [nv][ncol] (workInGlobal: else they live in LDS) | part [sites][chunks][cap] | stat [sites]
 // [3 cap] (cap: the kernels' A::kCap) | matPerSite doubles per site (the block-local matrices, the series stage's g and G) | info
 // [sites][4] (a.info is d_site_info where given) | cnt, kept [sites][chunks] | site [sites][2] | src [sites] (withSrc).  part,
 // stat, cnt, kept and site are the per-chunk launches' (perChunk: without them the regions are empty, and cnt, kept and site,
 // which the one-workgroup-per-site kernel never reads, all point at the end of info).  *mat, where asked for, gets the base of
 // the doubles per site.
-int enkfScratch(sipnet_batch* b, void** block, size_t* blockBytes, EnkfArgs& a, int32_t* d_site_info, bool workInGlobal,
+int enkfScratch(sipnet_batch* b, DevBuf<unsigned char>& block, EnkfArgs& a, int32_t* d_site_info, bool workInGlobal,
                 bool perChunk, bool withSrc, size_t matPerSite, double** mat, int cap = kMaxVars) {
   const size_t nSites = (size_t)b->n_sites;
   const size_t nWork = workInGlobal ? (size_t)a.nv * (size_t)b->ncol : 0;
@@ -219,16 +210,11 @@ int enkfScratch(sipnet_batch* b, void** block, size_t* blockBytes, EnkfArgs& a, 
   const size_t nSite = perChunk ? 2 * nSites : 0;
   const size_t nInt = nSites * 4 + 2 * nCnt + nSite + (withSrc ? nSites : 0);
   const size_t bytes = (nWork + nPart + nStat + nMat) * sizeof(double) + nInt * sizeof(int32_t);
-  if (*blockBytes < bytes) {
-    int rc = waitIdle(b);   // (the old block may still be read by a launch in flight)
-    if (rc) return rc;
-    if (*block) (void)hipFree(*block);   // (this block alone: the other may be in use by this very call)
-    *block = nullptr;
-    *blockBytes = 0;
-    HIP_TRY(hipMalloc(block, bytes));
-    *blockBytes = bytes;
+  if (block.capacity() < bytes) {
+    RC_TRY(waitIdle(b));   // (the old block may still be read by a launch in flight)
+    RC_TRY(block.reserve(bytes));   // (this block alone: the other may be in use by this very call)
   }
-  a.work = (double*)*block;
+  a.work = (double*)block.get();
   a.part = a.work + nWork;
   a.stat = a.part + nPart;
   double* matrices = a.stat + nStat;
@@ -301,7 +287,7 @@ int enkfSites(const EnkfCall& c, A& a) {
   int rc = lds ? ldsGranted((const void*)siteKernel, ldsBytes, b->device, &lds) : 0;
   if (rc) return rc;
   a.useLds = lds;
-  rc = enkfScratch(b, &b->d_enkf, &b->enkfBytes, a, c.d_site_info, /*workInGlobal=*/!a.useLds, /*perChunk=*/!group,
+  rc = enkfScratch(b, b->d_enkf, a, c.d_site_info, /*workInGlobal=*/!a.useLds, /*perChunk=*/!group,
                    /*withSrc=*/false, 0, nullptr, A::kCap);
   if (rc) return rc;
   if (group) {
@@ -491,7 +477,7 @@ int smoothFront(const EnkfCall& c, const JointArgs& joint, int32_t nSeries, cons
   // own, not a corner of the batch's: the pool analysis that follows carves b->d_enkf for itself, and so runs on exactly what
   // it runs on without series.
   double* meta = nullptr;
-  int rc = enkfScratch(b, &b->d_smooth, &b->smoothBytes, a, nullptr, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false,
+  int rc = enkfScratch(b, b->d_smooth, a, nullptr, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false,
                        kMeta, &meta, JointArgs::kCap);
   if (rc) return rc;
 
@@ -673,10 +659,6 @@ int sipnet_enkf_local_schedule(int32_t n_sites, int32_t n_obs, const int64_t* nb
 void sipnet_enkf_local_destroy(sipnet_enkf_local* L) {
   if (!L) return;
   (void)hipSetDevice(L->device);
-  if (L->d_pair) (void)hipFree(L->d_pair);
-  if (L->d_inPtr) (void)hipFree(L->d_inPtr);
-  if (L->d_in) (void)hipFree(L->d_in);
-  if (L->d_inRho) (void)hipFree(L->d_inRho);
   delete L;
 }
 
@@ -732,15 +714,14 @@ int sipnet_batch_enkf_local_create(sipnet_batch* b, int32_t n_obs, const int64_t
   L->levelOff = std::move(levelOff);
   L->slotOff = std::move(slotOff);
   L->slotLen = std::move(slotLen);
-  auto upload = [](void** d, const void* h, size_t bytes) -> int {
-    HIP_TRY(hipMalloc(d, bytes > 0 ? bytes : 8));
-    if (bytes) HIP_TRY(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+  auto upload = [](auto& d, const auto& h) -> int {   // (an empty list: 8 bytes, not a null pointer)
+    const size_t elem = sizeof(h[0]);
+    RC_TRY(d.reserve(h.empty() ? (8 + elem - 1) / elem : h.size()));
+    if (!h.empty()) HIP_TRY(hipMemcpy(d, h.data(), h.size() * elem, hipMemcpyHostToDevice));
     return 0;
   };
-  if ((rc = upload((void**)&L->d_pair, pairs.data(), pairs.size() * sizeof(LocalPair))) ||
-      (rc = upload((void**)&L->d_inPtr, inPtr.data(), inPtr.size() * sizeof(int64_t))) ||
-      (rc = upload((void**)&L->d_in, in.data(), in.size() * sizeof(int32_t))) ||
-      (rc = upload((void**)&L->d_inRho, inRho.data(), inRho.size() * sizeof(double)))) {
+  if ((rc = upload(L->d_pair, pairs)) || (rc = upload(L->d_inPtr, inPtr)) || (rc = upload(L->d_in, in)) ||
+      (rc = upload(L->d_inRho, inRho))) {
     sipnet_enkf_local_destroy(L);
     return rc;
   }
@@ -768,7 +749,7 @@ int sipnet_batch_enkf_analysis_local(sipnet_batch* b, const sipnet_enkf_local* L
   EnkfArgs a;
   rc = enkfBegin(name, c, a);
   if (rc) return rc;
-  rc = enkfScratch(b, &b->d_enkf, &b->enkfBytes, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/true, 0,
+  rc = enkfScratch(b, b->d_enkf, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/true, 0,
                    nullptr);
   if (rc) return rc;
   enkfFront(c, a, L);
@@ -817,7 +798,7 @@ int sipnet_batch_enkf_analysis_block(sipnet_batch* b, const sipnet_enkf_local* L
   rc = ldsGranted(ldsKernel, ldsWant, b->device, &useLds);
   if (rc) return rc;
   double* mat = nullptr;   // (a target's matrices in its block of the scratch, unless they are in LDS)
-  rc = enkfScratch(b, &b->d_enkf, &b->enkfBytes, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/true,
+  rc = enkfScratch(b, b->d_enkf, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/true,
                    useLds ? 0 : matDoubles, &mat);
   if (rc) return rc;
   enkfFront(c, a, L);
@@ -850,7 +831,7 @@ int sipnet_batch_enkf_shard_moments(sipnet_batch* b, int32_t n_obs, const sipnet
   int rc = enkfBegin(name, c, a);
   if (rc) return rc;
   const int cap = a.nv * a.nObs, W = shardWords(a.nA, a.nObs);   // (part: a chunk's sums [nv], then its products [nv][n_obs])
-  rc = enkfScratch(b, &b->d_enkf, &b->enkfBytes, a, nullptr, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false, 0,
+  rc = enkfScratch(b, b->d_enkf, a, nullptr, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false, 0,
                    nullptr, cap);
   if (rc) return rc;
   const dim3 chunks = chunkGrid(b, a);
@@ -891,7 +872,7 @@ int sipnet_batch_enkf_analysis_sharded(sipnet_batch* b, int32_t n_obs, const sip
                               "'s moment block is not an integer 0..4194304); nothing was written");
   }
   double* plan = nullptr;
-  rc = enkfScratch(b, &b->d_enkf, &b->enkfBytes, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false,
+  rc = enkfScratch(b, b->d_enkf, a, d_site_info, /*workInGlobal=*/true, /*perChunk=*/true, /*withSrc=*/false,
                    kShardPlan, &plan);
   if (rc) return rc;
   hipLaunchKernelGGL((elem_is_f32 ? enkfLoadKernel<float, EnkfArgs> : enkfLoadKernel<double, EnkfArgs>), chunkGrid(b, a), dim3(256),

@@ -38,11 +38,10 @@
 #include <vector>
 
 #include "../../include/sipnet_amd.h"
+#include "dev_buf.h"
 #include "shard_pool.h"
 
-namespace sipnet {
-void setError(const std::string& s);
-}
+using sipnet::DevBuf;
 using sipnet::setError;
 
 namespace {
@@ -112,18 +111,22 @@ struct sipnet_node {
   int64_t ld = 0;         // maxSites * maxCount: every shard's planes have this leading dimension
   // per shard: planes [3][n_run][ld] (element type by precision), statistics [3][n_run][maxSites][2],
   // gathered statistics [n][3][n_run][maxSites][2], gathered planes [n][3][n_run][ld] (on request)
+  // (nAlloc: the records the planes and statistics were last laid out and zeroed for; every block has its own capacity)
   int32_t nAlloc = 0, nRun = 0, step0 = 0;
-  std::vector<void*> planes, gatheredPlanes;
-  std::vector<double*> stats, gatheredStats, statsCompact;
-  std::vector<size_t> statsCompactCap;
-  size_t gatheredPlanesCap = 0, gatheredStatsCap = 0;
+  // a shard's blocks, together so that they go together, with the shard's device current (sipnet_node_destroy)
+  struct ShardBufs {
+    DevBuf<unsigned char> planes, gatheredPlanes;   // bytes: the element type goes by the precision
+    DevBuf<double> stats, gatheredStats, statsCompact;
+    DevBuf<double> pfGathered;
+    DevBuf<int32_t> pfAnc;
+    DevBuf<int64_t> pfTotals;
+    DevBuf<unsigned char> reduced, gatheredReduced;   // bytes
+  };
+  std::vector<ShardBufs> shard;
   // particle filter: per shard the gathered log-weight blocks, its particles' ancestors, a ring of total weights
   bool pfConnected = false;
   int64_t pfBlock = 0;
   int32_t pfCycles = 0;
-  std::vector<double*> pfGathered;
-  std::vector<int32_t*> pfAnc;
-  std::vector<int64_t*> pfTotals;
   static constexpr int kPfTotals = 64;
   // sipnet_node_run_gathering: the run cut into segments, segment j at rows [3 * segCuts[j], 3 * segCuts[j + 1]) of
   // every shard's planes ([3][len_j][ld] each) and at [n][3][len_j][ld] from element n * 3 * ld * segCuts[j] of the
@@ -136,8 +139,6 @@ struct sipnet_node {
   int32_t reducedForm = 0, reducedSumSteps = 0;
   bool reducedInKernel = false;   // the sums came out of the step kernels' own launches (no planes were written)
   std::vector<int32_t> redCuts;
-  std::vector<void*> reduced, gatheredReduced;
-  size_t reducedCap = 0;   // bytes per shard
   std::vector<hipStream_t> gatherStreams;
   std::vector<hipEvent_t> evSeg, evGathered;
   // event-ordered transport
@@ -156,6 +157,15 @@ struct sipnet_node {
     if (e_ != hipSuccess) {                                                   \
       setError(std::string("sipnet_node: ") + #expr + ": " + hipGetErrorString(e_)); \
       return SIPNET_ERR_NO_DEVICE;                                            \
+    }                                                                         \
+  } while (0)
+// a buffer's reserve: the node's prefix in front of its error text
+#define NODE_BUF(call)                                                        \
+  do {                                                                        \
+    int rc_ = (call);                                                         \
+    if (rc_) {                                                                \
+      setError(std::string("sipnet_node: ") + sipnet_last_error());           \
+      return rc_;                                                             \
     }                                                                         \
   } while (0)
 #define NODE_RCCL(nd, expr)                                                   \
@@ -260,17 +270,7 @@ static int createNode(const int32_t* flags, int32_t n_sites, int32_t n_members, 
   nd->devices.assign(devices, devices + n_devices);
   nd->batches.assign(n_devices, nullptr);
   nd->streams.assign(n_devices, nullptr);
-  nd->planes.assign(n_devices, nullptr);
-  nd->gatheredPlanes.assign(n_devices, nullptr);
-  nd->reduced.assign(n_devices, nullptr);
-  nd->gatheredReduced.assign(n_devices, nullptr);
-  nd->stats.assign(n_devices, nullptr);
-  nd->gatheredStats.assign(n_devices, nullptr);
-  nd->statsCompact.assign(n_devices, nullptr);
-  nd->statsCompactCap.assign(n_devices, 0);
-  nd->pfGathered.assign(n_devices, nullptr);
-  nd->pfAnc.assign(n_devices, nullptr);
-  nd->pfTotals.assign(n_devices, nullptr);
+  nd->shard.resize(n_devices);
   nd->evReady.assign(n_devices, nullptr);
   nd->evCopied.assign(n_devices, nullptr);
   nd->gatherStreams.assign(n_devices, nullptr);
@@ -396,16 +396,7 @@ void sipnet_node_destroy(sipnet_node* nd) {
   for (int k = 0; k < nd->n(); k++) {
     (void)hipSetDevice(nd->devices[k]);
     if (k < (int)nd->comms.size() && nd->comms[k]) nd->rccl->commDestroy(nd->comms[k]);
-    if (nd->planes[k]) (void)hipFree(nd->planes[k]);
-    if (nd->gatheredPlanes[k]) (void)hipFree(nd->gatheredPlanes[k]);
-    if (nd->reduced[k]) (void)hipFree(nd->reduced[k]);
-    if (nd->gatheredReduced[k]) (void)hipFree(nd->gatheredReduced[k]);
-    if (nd->stats[k]) (void)hipFree(nd->stats[k]);
-    if (nd->gatheredStats[k]) (void)hipFree(nd->gatheredStats[k]);
-    if (nd->statsCompact[k]) (void)hipFree(nd->statsCompact[k]);
-    if (nd->pfGathered[k]) (void)hipFree(nd->pfGathered[k]);
-    if (nd->pfAnc[k]) (void)hipFree(nd->pfAnc[k]);
-    if (nd->pfTotals[k]) (void)hipFree(nd->pfTotals[k]);
+    nd->shard[k] = sipnet_node::ShardBufs();
     if (nd->evReady[k]) (void)hipEventDestroy(nd->evReady[k]);
     if (nd->evCopied[k]) (void)hipEventDestroy(nd->evCopied[k]);
     if (nd->evSeg[k]) (void)hipEventDestroy(nd->evSeg[k]);
@@ -607,16 +598,12 @@ static int growRunBuffers(sipnet_node* nd, int k, int32_t n_steps) {
   const size_t planeBytes = (size_t)3 * n_steps * nd->ld * nd->elem();
   const size_t statDoubles = (size_t)3 * n_steps * nd->maxSites * 2;
   NODE_HIP(hipStreamSynchronize(nd->streams[k]));
-  if (nd->planes[k]) NODE_HIP(hipFree(nd->planes[k]));
-  if (nd->stats[k]) NODE_HIP(hipFree(nd->stats[k]));
-  nd->planes[k] = nullptr;
-  nd->stats[k] = nullptr;
-  NODE_HIP(hipMalloc(&nd->planes[k], planeBytes));
-  NODE_HIP(hipMalloc(&nd->stats[k], statDoubles * sizeof(double)));
+  NODE_BUF(nd->shard[k].planes.reserve(planeBytes));
+  NODE_BUF(nd->shard[k].stats.reserve(statDoubles));
   // columns past a shard's own (the padding up to the common leading dimension) and the statistics of
   // sites it does not have stay zero: no kernel ever writes them, whatever the length of a run
-  NODE_HIP(hipMemsetAsync(nd->planes[k], 0, planeBytes, nd->streams[k]));
-  NODE_HIP(hipMemsetAsync(nd->stats[k], 0, statDoubles * sizeof(double), nd->streams[k]));
+  NODE_HIP(hipMemsetAsync(nd->shard[k].planes, 0, planeBytes, nd->streams[k]));
+  NODE_HIP(hipMemsetAsync(nd->shard[k].stats, 0, statDoubles * sizeof(double), nd->streams[k]));
   return SIPNET_OK;
 }
 
@@ -641,7 +628,7 @@ static int runShards(sipnet_node* nd, int32_t step0, int32_t n_steps, bool withS
       int rcg = growRunBuffers(nd, k, n_steps);
       if (rcg) return rcg;
     }
-    char* p = (char*)nd->planes[k];
+    char* p = (char*)nd->shard[k].planes.get();
     const size_t one = (size_t)n_steps * nd->ld * nd->elem();
     if (!grow && shardEndsEarly(nd, k, step0 + n_steps)) NODE_HIP(hipMemsetAsync(p, 0, 3 * one, nd->streams[k]));
     // (site shards may hold forcings of different lengths: a shard runs to the end of ITS longest site; the rows
@@ -652,25 +639,22 @@ static int runShards(sipnet_node* nd, int32_t step0, int32_t n_steps, bool withS
     if (!withStats)
       return sipnet_batch_run(nd->batches[k], step0, nLoc, p, p + one, p + 2 * one, nullptr, nd->ld, nd->streams[k]);
     if (nd->nSites[k] == nd->maxSites && nLoc == n_steps)
-      return sipnet_batch_run_stats(nd->batches[k], step0, n_steps, p, p + one, p + 2 * one, nd->ld, nd->stats[k],
+      return sipnet_batch_run_stats(nd->batches[k], step0, n_steps, p, p + one, p + 2 * one, nd->ld, nd->shard[k].stats,
                                     nd->streams[k]);
     // a shard with fewer sites than the largest, or a shorter run: its block [3][nLoc][nSites][2] is produced
     // compactly and spread out to the common shape [3][n_steps][maxSites][2] (everything else stays zero)
     const size_t compactDoubles = (size_t)3 * nLoc * nd->nSites[k] * 2;
-    if (compactDoubles > nd->statsCompactCap[k]) {
+    if (compactDoubles > nd->shard[k].statsCompact.capacity()) {
       NODE_HIP(hipStreamSynchronize(nd->streams[k]));
-      if (nd->statsCompact[k]) NODE_HIP(hipFree(nd->statsCompact[k]));
-      nd->statsCompact[k] = nullptr;
-      NODE_HIP(hipMalloc(&nd->statsCompact[k], compactDoubles * sizeof(double)));
-      nd->statsCompactCap[k] = compactDoubles;
+      NODE_BUF(nd->shard[k].statsCompact.reserve(compactDoubles));
     }
-    int rc2 = sipnet_batch_run_stats(nd->batches[k], step0, nLoc, p, p + one, p + 2 * one, nd->ld, nd->statsCompact[k],
+    int rc2 = sipnet_batch_run_stats(nd->batches[k], step0, nLoc, p, p + one, p + 2 * one, nd->ld, nd->shard[k].statsCompact,
                                      nd->streams[k]);
     if (rc2) return rc2;
-    if (nLoc != n_steps) NODE_HIP(hipMemsetAsync(nd->stats[k], 0, statDoubles * sizeof(double), nd->streams[k]));
+    if (nLoc != n_steps) NODE_HIP(hipMemsetAsync(nd->shard[k].stats, 0, statDoubles * sizeof(double), nd->streams[k]));
     for (int v = 0; v < 3; v++)
-      NODE_HIP(hipMemcpy2DAsync(nd->stats[k] + (size_t)v * n_steps * nd->maxSites * 2, (size_t)nd->maxSites * 2 * sizeof(double),
-                                nd->statsCompact[k] + (size_t)v * nLoc * nd->nSites[k] * 2,
+      NODE_HIP(hipMemcpy2DAsync(nd->shard[k].stats + (size_t)v * n_steps * nd->maxSites * 2, (size_t)nd->maxSites * 2 * sizeof(double),
+                                nd->shard[k].statsCompact + (size_t)v * nLoc * nd->nSites[k] * 2,
                                 (size_t)nd->nSites[k] * 2 * sizeof(double), (size_t)nd->nSites[k] * 2 * sizeof(double),
                                 (size_t)nLoc, hipMemcpyDeviceToDevice, nd->streams[k]));
     return SIPNET_OK;
@@ -717,7 +701,6 @@ static int runGathering(sipnet_node* nd, int32_t step0, int32_t n_steps, int32_t
   const int n = nd->n();
   const size_t count = (size_t)3 * n_steps * nd->ld;   // elements per shard
   const bool grow = n_steps > nd->nAlloc;
-  const bool growGathered = count * n > nd->gatheredPlanesCap;
   // cuts at whole 16-step tiles of the site plan where the segments are long enough for that
   std::vector<int32_t> cuts(n_segments + 1, 0);
   cuts[n_segments] = n_steps;
@@ -737,52 +720,44 @@ static int runGathering(sipnet_node* nd, int32_t step0, int32_t n_steps, int32_t
   bool sumsInKernel = form == SIPNET_GATHER_SUMS;
   for (int k = 0; k < n && sumsInKernel; k++) sumsInKernel = sipnet_batch_sums_in_kernel(nd->batches[k]) != 0;
   nd->reducedInKernel = sumsInKernel;
-  const bool growReduced = redBytes > nd->reducedCap;
   int rc = onEveryShard(nd, [&](int k) -> int {
-    if (growReduced) {
+    if (redBytes > nd->shard[k].reduced.capacity() || redBytes * n > nd->shard[k].gatheredReduced.capacity()) {
       NODE_HIP(hipStreamSynchronize(nd->streams[k]));
       NODE_HIP(hipStreamSynchronize(nd->gatherStreams[k]));
-      if (nd->reduced[k]) NODE_HIP(hipFree(nd->reduced[k]));
-      if (nd->gatheredReduced[k]) NODE_HIP(hipFree(nd->gatheredReduced[k]));
-      nd->reduced[k] = nd->gatheredReduced[k] = nullptr;
-      NODE_HIP(hipMalloc(&nd->reduced[k], redBytes));
-      NODE_HIP(hipMalloc(&nd->gatheredReduced[k], redBytes * n));
+      NODE_BUF(nd->shard[k].reduced.reserve(redBytes));
+      NODE_BUF(nd->shard[k].gatheredReduced.reserve(redBytes * n));
     }
     if (grow) {
       NODE_HIP(hipStreamSynchronize(nd->gatherStreams[k]));
       int rcg = growRunBuffers(nd, k, n_steps);
       if (rcg) return rcg;
     }
-    if (growGathered && !form) {
+    if (!form && count * n * nd->elem() > nd->shard[k].gatheredPlanes.capacity()) {
       NODE_HIP(hipStreamSynchronize(nd->streams[k]));
       NODE_HIP(hipStreamSynchronize(nd->gatherStreams[k]));
-      if (nd->gatheredPlanes[k]) NODE_HIP(hipFree(nd->gatheredPlanes[k]));
-      nd->gatheredPlanes[k] = nullptr;
-      NODE_HIP(hipMalloc(&nd->gatheredPlanes[k], count * n * nd->elem()));
+      NODE_BUF(nd->shard[k].gatheredPlanes.reserve(count * n * nd->elem()));
     }
     return SIPNET_OK;
   });
   if (rc) return rc;
   if (grow) nd->nAlloc = n_steps;
-  if (growGathered && !form) nd->gatheredPlanesCap = count * n;
-  if (growReduced) nd->reducedCap = redBytes;
   // every shard's host thread walks the segments on its own: launch, hand over to the second stream, all-gather there
   // (RCCL: one communicator per thread, the multi-thread idiom; shards sharing a device: event-ordered copies, the
   // threads meeting at a host barrier per segment)
   rc = onEveryShard(nd, [&](int k) -> int {
     const int32_t have = sipnet_batch_nsteps(nd->batches[k]);
     if (!grow && shardEndsEarly(nd, k, step0 + n_steps))
-      NODE_HIP(hipMemsetAsync(nd->planes[k], 0, count * nd->elem(), nd->streams[k]));
+      NODE_HIP(hipMemsetAsync(nd->shard[k].planes, 0, count * nd->elem(), nd->streams[k]));
     for (int j = 0; j < n_segments; j++) {
       const int32_t a = cuts[j], len = cuts[j + 1] - a;
       const size_t one = (size_t)len * nd->ld * nd->elem();              // one variable of the segment
       const size_t segOff = (size_t)3 * a * nd->ld * nd->elem();         // the segment in a shard's planes
-      char* p = (char*)nd->planes[k] + segOff;
+      char* p = (char*)nd->shard[k].planes.get() + segOff;
       const int32_t nLoc = step0 + a + len <= have ? len : have - (step0 + a);
       if (sumsInKernel) {
         const int32_t rows = redCuts[j + 1] - redCuts[j];
         const size_t redOff = (size_t)3 * redCuts[j] * nd->ld * sizeof(double), oneRed = (size_t)rows * nd->ld;
-        double* r = (double*)((char*)nd->reduced[k] + redOff);
+        double* r = (double*)((char*)nd->shard[k].reduced.get() + redOff);
         if (nLoc < len) NODE_HIP(hipMemsetAsync(r, 0, 3 * oneRed * sizeof(double), nd->streams[k]));   // (groups past a shard's last record: zero)
         if (nLoc > 0) {
           int rcr = sipnet_batch_run_sums(nd->batches[k], step0 + a, nLoc, sumSteps, r, r + oneRed, r + 2 * oneRed, nd->ld, nd->streams[k]);
@@ -790,7 +765,7 @@ static int runGathering(sipnet_node* nd, int32_t step0, int32_t n_steps, int32_t
         }
         NODE_HIP(hipEventRecord(nd->evSeg[k], nd->streams[k]));
         NODE_HIP(hipStreamWaitEvent(nd->gatherStreams[k], nd->evSeg[k], 0));
-        int rcg = allGatherShard(nd, k, r, (char*)nd->gatheredReduced[k] + (size_t)n * redOff, 3 * oneRed * sizeof(double), nd->gatherStreams[k]);
+        int rcg = allGatherShard(nd, k, r, (char*)nd->shard[k].gatheredReduced.get() + (size_t)n * redOff, 3 * oneRed * sizeof(double), nd->gatherStreams[k]);
         if (rcg) return rcg;
         continue;
       }
@@ -802,14 +777,14 @@ static int runGathering(sipnet_node* nd, int32_t step0, int32_t n_steps, int32_t
       NODE_HIP(hipEventRecord(nd->evSeg[k], nd->streams[k]));
       NODE_HIP(hipStreamWaitEvent(nd->gatherStreams[k], nd->evSeg[k], 0));
       if (!form) {
-        int rcg = allGatherShard(nd, k, p, (char*)nd->gatheredPlanes[k] + (size_t)n * segOff, 3 * one, nd->gatherStreams[k]);
+        int rcg = allGatherShard(nd, k, p, (char*)nd->shard[k].gatheredPlanes.get() + (size_t)n * segOff, 3 * one, nd->gatherStreams[k]);
         if (rcg) return rcg;
         continue;
       }
       // the segment's reduced block [3][rows][ld], made on the second stream, then gathered there
       const int32_t rows = redCuts[j + 1] - redCuts[j];
       const size_t redOff = (size_t)3 * redCuts[j] * nd->ld * redElem, redLen = (size_t)3 * rows * nd->ld * redElem;
-      char* r = (char*)nd->reduced[k] + redOff;
+      char* r = (char*)nd->shard[k].reduced.get() + redOff;
       hipStream_t gs = nd->gatherStreams[k];
       if (form == SIPNET_GATHER_F32) {
         const size_t n2 = (size_t)3 * len * nd->ld / 2;   // (ld is even)
@@ -822,7 +797,7 @@ static int runGathering(sipnet_node* nd, int32_t step0, int32_t n_steps, int32_t
           hipLaunchKernelGGL(sumStepsKernel<float>, grid, dim3(256), 0, gs, (const float*)p, (size_t)len * nd->ld, len, sumSteps, rows, nd->ld, (double*)r);
       }
       NODE_HIP(hipGetLastError());
-      int rcg = allGatherShard(nd, k, r, (char*)nd->gatheredReduced[k] + (size_t)n * redOff, redLen, gs);
+      int rcg = allGatherShard(nd, k, r, (char*)nd->shard[k].gatheredReduced.get() + (size_t)n * redOff, redLen, gs);
       if (rcg) return rcg;
     }
     return SIPNET_OK;
@@ -863,14 +838,14 @@ void* sipnet_node_gathered_reduced(sipnet_node* nd, int32_t k, int32_t segment, 
   if (first_row) *first_row = nd->redCuts[segment];
   if (n_rows) *n_rows = nd->redCuts[segment + 1] - nd->redCuts[segment];
   if (elem_bytes) *elem_bytes = (int32_t)redElem;
-  return (char*)nd->gatheredReduced[k] + (size_t)nd->n() * 3 * nd->redCuts[segment] * nd->ld * redElem;
+  return (char*)nd->shard[k].gatheredReduced.get() + (size_t)nd->n() * 3 * nd->redCuts[segment] * nd->ld * redElem;
 }
 int32_t sipnet_node_n_segments(const sipnet_node* nd) { return (nd && nd->segmented) ? (int32_t)nd->segCuts.size() - 1 : 0; }
 void* sipnet_node_gathered_segment(sipnet_node* nd, int32_t k, int32_t segment, int32_t* first_step, int32_t* n_steps) {
   if (!nd || !nd->segmented || k < 0 || k >= nd->n() || segment < 0 || segment + 1 >= (int32_t)nd->segCuts.size()) return nullptr;
   if (first_step) *first_step = nd->step0 + nd->segCuts[segment];
   if (n_steps) *n_steps = nd->segCuts[segment + 1] - nd->segCuts[segment];
-  return (char*)nd->gatheredPlanes[k] + (size_t)nd->n() * 3 * nd->segCuts[segment] * nd->ld * nd->elem();
+  return (char*)nd->shard[k].gatheredPlanes.get() + (size_t)nd->n() * 3 * nd->segCuts[segment] * nd->ld * nd->elem();
 }
 
 int sipnet_node_run(sipnet_node* nd, int32_t step0, int32_t n_steps) { return runShards(nd, step0, n_steps, true); }
@@ -900,13 +875,13 @@ int sipnet_node_get_status(sipnet_node* nd, int32_t* status) {
   return SIPNET_OK;
 }
 
-void* sipnet_node_planes(sipnet_node* nd, int32_t k) { return (nd && k >= 0 && k < nd->n()) ? nd->planes[k] : nullptr; }
-double* sipnet_node_stats(sipnet_node* nd, int32_t k) { return (nd && k >= 0 && k < nd->n()) ? nd->stats[k] : nullptr; }
+void* sipnet_node_planes(sipnet_node* nd, int32_t k) { return (nd && k >= 0 && k < nd->n()) ? nd->shard[k].planes : nullptr; }
+double* sipnet_node_stats(sipnet_node* nd, int32_t k) { return (nd && k >= 0 && k < nd->n()) ? nd->shard[k].stats : nullptr; }
 double* sipnet_node_gathered_stats(sipnet_node* nd, int32_t k) {
-  return (nd && k >= 0 && k < nd->n()) ? nd->gatheredStats[k] : nullptr;
+  return (nd && k >= 0 && k < nd->n()) ? nd->shard[k].gatheredStats : nullptr;
 }
 void* sipnet_node_gathered_planes(sipnet_node* nd, int32_t k) {
-  return (nd && k >= 0 && k < nd->n()) ? nd->gatheredPlanes[k] : nullptr;
+  return (nd && k >= 0 && k < nd->n()) ? nd->shard[k].gatheredPlanes : nullptr;
 }
 
 // ONE all-gather: every shard's statistics block of the last sipnet_node_run to every shard
@@ -917,26 +892,22 @@ int sipnet_node_gather_stats(sipnet_node* nd, double* host_total) {
   }
   const int n = nd->n();
   const size_t block = (size_t)3 * nd->nRun * nd->maxSites * 2;  // doubles per shard
-  if (block * n > nd->gatheredStatsCap) {
-    for (int k = 0; k < n; k++) {
-      NODE_HIP(hipSetDevice(nd->devices[k]));
-      NODE_HIP(hipStreamSynchronize(nd->streams[k]));
-      if (nd->gatheredStats[k]) NODE_HIP(hipFree(nd->gatheredStats[k]));
-      nd->gatheredStats[k] = nullptr;
-      NODE_HIP(hipMalloc(&nd->gatheredStats[k], block * n * sizeof(double)));
-    }
-    nd->gatheredStatsCap = block * n;
+  for (int k = 0; k < n; k++) {
+    if (block * n <= nd->shard[k].gatheredStats.capacity()) continue;
+    NODE_HIP(hipSetDevice(nd->devices[k]));
+    NODE_HIP(hipStreamSynchronize(nd->streams[k]));
+    NODE_BUF(nd->shard[k].gatheredStats.reserve(block * n));
   }
   if (!nd->comms.empty()) {   // one thread, the per-device calls of the collective fused (RCCL's single-process idiom)
     NODE_RCCL(nd, nd->rccl->groupStart());
     for (int k = 0; k < n; k++) {
       NODE_HIP(hipSetDevice(nd->devices[k]));
-      NODE_RCCL(nd, nd->rccl->allGather(nd->stats[k], nd->gatheredStats[k], block, ncclDouble, nd->comms[k], nd->streams[k]));
+      NODE_RCCL(nd, nd->rccl->allGather(nd->shard[k].stats, nd->shard[k].gatheredStats, block, ncclDouble, nd->comms[k], nd->streams[k]));
     }
     NODE_RCCL(nd, nd->rccl->groupEnd());
   } else {
     int rc = onEveryShard(nd, [&](int k) -> int {
-      return allGatherShard(nd, k, nd->stats[k], nd->gatheredStats[k], block * sizeof(double));
+      return allGatherShard(nd, k, nd->shard[k].stats, nd->shard[k].gatheredStats, block * sizeof(double));
     });
     if (rc) return rc;
   }
@@ -946,7 +917,7 @@ int sipnet_node_gather_stats(sipnet_node* nd, double* host_total) {
     std::vector<double> all(block * n);
     NODE_HIP(hipSetDevice(nd->devices[0]));
     NODE_HIP(hipStreamSynchronize(nd->streams[0]));   // shard 0's copy of everybody's block: complete when its all-gather is
-    NODE_HIP(hipMemcpy(all.data(), nd->gatheredStats[0], all.size() * sizeof(double), hipMemcpyDeviceToHost));
+    NODE_HIP(hipMemcpy(all.data(), nd->shard[0].gatheredStats, all.size() * sizeof(double), hipMemcpyDeviceToHost));
     if (nd->mode == SIPNET_SHARD_MEMBERS) {
       for (size_t i = 0; i < block; i++) {
         double s = 0.0;
@@ -974,28 +945,24 @@ int sipnet_node_gather_planes(sipnet_node* nd) {
   }
   const int n = nd->n();
   const size_t count = (size_t)3 * nd->nRun * nd->ld;  // elements per shard
-  if (count * n > nd->gatheredPlanesCap) {
-    for (int k = 0; k < n; k++) {
-      NODE_HIP(hipSetDevice(nd->devices[k]));
-      NODE_HIP(hipStreamSynchronize(nd->streams[k]));
-      if (nd->gatheredPlanes[k]) NODE_HIP(hipFree(nd->gatheredPlanes[k]));
-      nd->gatheredPlanes[k] = nullptr;
-      NODE_HIP(hipMalloc(&nd->gatheredPlanes[k], count * n * nd->elem()));
-    }
-    nd->gatheredPlanesCap = count * n;
+  for (int k = 0; k < n; k++) {
+    if (count * n * nd->elem() <= nd->shard[k].gatheredPlanes.capacity()) continue;
+    NODE_HIP(hipSetDevice(nd->devices[k]));
+    NODE_HIP(hipStreamSynchronize(nd->streams[k]));
+    NODE_BUF(nd->shard[k].gatheredPlanes.reserve(count * n * nd->elem()));
   }
   if (!nd->comms.empty()) {
     NODE_RCCL(nd, nd->rccl->groupStart());
     for (int k = 0; k < n; k++) {
       NODE_HIP(hipSetDevice(nd->devices[k]));
-      NODE_RCCL(nd, nd->rccl->allGather(nd->planes[k], nd->gatheredPlanes[k], count,
+      NODE_RCCL(nd, nd->rccl->allGather(nd->shard[k].planes, nd->shard[k].gatheredPlanes, count,
                                         nd->precision == SIPNET_F64 ? ncclDouble : ncclFloat, nd->comms[k], nd->streams[k]));
     }
     NODE_RCCL(nd, nd->rccl->groupEnd());
     return SIPNET_OK;
   }
   return onEveryShard(nd, [&](int k) -> int {
-    return allGatherShard(nd, k, nd->planes[k], nd->gatheredPlanes[k], count * nd->elem());
+    return allGatherShard(nd, k, nd->shard[k].planes, nd->shard[k].gatheredPlanes, count * nd->elem());
   });
 }
 
@@ -1013,17 +980,11 @@ int sipnet_node_pf_connect(sipnet_node* nd, int32_t with_params) {
     int r2 = sipnet_batch_pf_connect(nd->batches[k], n, k, peers.data());
     if (r2) return r2;
     NODE_HIP(hipStreamSynchronize(nd->streams[k]));
-    if (nd->pfGathered[k]) NODE_HIP(hipFree(nd->pfGathered[k]));
-    if (nd->pfAnc[k]) NODE_HIP(hipFree(nd->pfAnc[k]));
-    if (nd->pfTotals[k]) NODE_HIP(hipFree(nd->pfTotals[k]));
-    nd->pfGathered[k] = nullptr;
-    nd->pfAnc[k] = nullptr;
-    nd->pfTotals[k] = nullptr;
     const int64_t L = sipnet_batch_pf_block_len(nd->batches[k]);
-    NODE_HIP(hipMalloc(&nd->pfGathered[k], (size_t)n * L * sizeof(double)));
-    NODE_HIP(hipMalloc(&nd->pfAnc[k], (size_t)nd->count[k] * sizeof(int32_t)));
-    NODE_HIP(hipMalloc(&nd->pfTotals[k], sipnet_node::kPfTotals * sizeof(int64_t)));
-    NODE_HIP(hipMemset(nd->pfTotals[k], 0xff, sipnet_node::kPfTotals * sizeof(int64_t)));   // -1: "no cycle wrote this slot"
+    NODE_BUF(nd->shard[k].pfGathered.reserve((size_t)n * L));
+    NODE_BUF(nd->shard[k].pfAnc.reserve((size_t)nd->count[k]));
+    NODE_BUF(nd->shard[k].pfTotals.reserve(sipnet_node::kPfTotals));
+    NODE_HIP(hipMemset(nd->shard[k].pfTotals, 0xff, sipnet_node::kPfTotals * sizeof(int64_t)));   // -1: "no cycle wrote this slot"
     return SIPNET_OK;
   });
   if (rc) return rc;
@@ -1041,7 +1002,7 @@ int sipnet_node_pf_arm(sipnet_node* nd, double obs, double sigma) {
   // (host-only: every shard's next forecast launch is told where its log-weight block lies -- its slice of the all-gather's
   // buffer -- and what it will be weighed against)
   for (int k = 0; k < nd->n(); k++) {
-    int rc = sipnet_batch_pf_arm(nd->batches[k], obs, sigma, nd->pfGathered[k] + (size_t)k * nd->pfBlock);
+    int rc = sipnet_batch_pf_arm(nd->batches[k], obs, sigma, nd->shard[k].pfGathered + (size_t)k * nd->pfBlock);
     if (rc) return rc;
   }
   return SIPNET_OK;
@@ -1059,14 +1020,14 @@ int sipnet_node_pf_analysis(sipnet_node* nd, int32_t variable, double obs, doubl
   }
   const int slot = nd->pfCycles % sipnet_node::kPfTotals;
   int rc = onEveryShard(nd, [&](int k) -> int {
-    const char* plane = (const char*)nd->planes[k] + (size_t)variable * nd->nRun * nd->ld * nd->elem();
-    double* mine = nd->pfGathered[k] + (size_t)k * nd->pfBlock;
+    const char* plane = (const char*)nd->shard[k].planes.get() + (size_t)variable * nd->nRun * nd->ld * nd->elem();
+    double* mine = nd->shard[k].pfGathered + (size_t)k * nd->pfBlock;
     int r2 = sipnet_batch_pf_local_weights(nd->batches[k], plane, nd->precision == SIPNET_F32_MIXED, nd->nRun, nd->ld, obs,
                                            sigma, mine, nd->streams[k]);
     if (r2) return r2;
-    r2 = allGatherShard(nd, k, mine, nd->pfGathered[k], (size_t)nd->pfBlock * sizeof(double));   // in place
+    r2 = allGatherShard(nd, k, mine, nd->shard[k].pfGathered, (size_t)nd->pfBlock * sizeof(double));   // in place
     if (r2) return r2;
-    return sipnet_batch_pf_resample_peers(nd->batches[k], nd->pfGathered[k], u0, nd->pfAnc[k], nd->pfTotals[k] + slot,
+    return sipnet_batch_pf_resample_peers(nd->batches[k], nd->shard[k].pfGathered, u0, nd->shard[k].pfAnc, nd->shard[k].pfTotals + slot,
                                           nd->streams[k]);
   });
   if (rc) return rc;
@@ -1081,7 +1042,7 @@ int sipnet_node_pf_check(sipnet_node* nd, int32_t* n_cycles_checked) {
   for (int k = 0; k < nd->n(); k++) {
     NODE_HIP(hipSetDevice(nd->devices[k]));
     NODE_HIP(hipStreamSynchronize(nd->streams[k]));
-    NODE_HIP(hipMemcpy(tk.data(), nd->pfTotals[k], tk.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    NODE_HIP(hipMemcpy(tk.data(), nd->shard[k].pfTotals, tk.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (k == 0) t0 = tk;
     for (int c = 0; c < m; c++) {
       if (tk[c] == SIPNET_PF_VOID_TOTAL) {
@@ -1105,7 +1066,7 @@ int sipnet_node_pf_check(sipnet_node* nd, int32_t* n_cycles_checked) {
   return SIPNET_OK;
 }
 
-int32_t* sipnet_node_pf_ancestors(sipnet_node* nd, int32_t k) { return (nd && k >= 0 && k < nd->n()) ? nd->pfAnc[k] : nullptr; }
+int32_t* sipnet_node_pf_ancestors(sipnet_node* nd, int32_t k) { return (nd && k >= 0 && k < nd->n()) ? nd->shard[k].pfAnc : nullptr; }
 int64_t sipnet_node_pf_block_len(const sipnet_node* nd) { return nd ? nd->pfBlock : 0; }
 
 }  // extern "C"

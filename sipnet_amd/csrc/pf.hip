@@ -1127,17 +1127,31 @@ struct PfPeers {
 void pfDropBank(sipnet_batch* b) {
   if (!b->d_prmBank) return;
   (void)hipDeviceSynchronize();
-  (void)hipFree(b->d_prmBank);
-  b->d_prmBank = nullptr;
+  (void)b->d_prmBank.release();
   b->prmBankPitch = 0;
   b->prmIndexed = false;
   if (b->pfPeers) b->pfPeers->bankLost = true;
 }
 
+// The second copies a resampling gathers into before it swaps (batch_impl.h), made on first use: state and ring, the
+// parameter rows, the particles' parameter index (both copies of it)
+static int ensureSpares(sipnet_batch* b, bool state, bool params, bool index) {
+  const size_t nc = (size_t)b->ncol;
+  if (state) {
+    RC_TRY(b->d_state2.reserve(nc * SIPNET_NSTATE));
+    RC_TRY(b->d_ring2.reserve(ringDoubles(b)));
+  }
+  if (params) RC_TRY(b->d_prm2.reserve(nc * SIPNET_NPARAMS));
+  if (index) {
+    RC_TRY(b->d_prmId.reserve(nc));
+    RC_TRY(b->d_prmId2.reserve(nc));
+  }
+  return SIPNET_OK;
+}
+
 // The parameter bank back in column order (batch_impl.h): gather through the index into the spare, swap.
 int materializeParams(sipnet_batch* b, hipStream_t stream) {
   if (!b->prmIndexed) return SIPNET_OK;
-  const size_t nc = (size_t)b->ncol;
   {   // (the last launch may have run on another stream)
     int rcO = orderBehindBusy(b, stream);
     if (rcO) return rcO;
@@ -1150,7 +1164,7 @@ int materializeParams(sipnet_batch* b, hipStream_t stream) {
     b->prmIndexed = false;
     return markBusy(b, stream);
   }
-  if (!b->d_prm2) HIP_TRY(hipMalloc(&b->d_prm2, nc * SIPNET_NPARAMS * sizeof(double)));
+  RC_TRY(ensureSpares(b, /*state=*/false, /*params=*/true, /*index=*/false));
   launchGatherMember(nullptr, nullptr, false, b->d_prm, b->ncol, nullptr, none, b->d_prmId, b->ncol, nullptr, nullptr, b->d_prm2,
                      b->ncol, stream);   // dst column j <- bank column d_prmId[j]
   HIP_TRY(hipGetLastError());
@@ -1207,67 +1221,52 @@ extern "C" int sipnet_batch_pf_log_weights(sipnet_batch* b, const void* d_plane,
   return logWeights(b, d_plane, elem_is_f32, n_steps, ld, obs, sigma, d_logw, nullptr, hip_stream);
 }
 
-// scratch of the resampling, kept between calls: one per batch for the sipnet_batch_pf_* entry points (freed by
-// sipnet_batch_destroy), one per host thread for the batch-less sipnet_pf_* ones (sipnet_pf_release_scratch)
+// scratch of the resampling, kept between calls: one per batch for the sipnet_batch_pf_* entry points (it goes with the
+// batch), one per host thread for the batch-less sipnet_pf_* ones (sipnet_pf_release_scratch)
 struct PfScratch {
   int device = -1;
-  int64_t cap = 0;
-  double* d_max = nullptr;  // partial maxima of the log-weights (one per 256 weights at most)
-  int64_t* d_w = nullptr;
-  int64_t* d_cdf = nullptr;
-  void* d_tmp = nullptr;
+  DevBuf<double> d_max;    // partial maxima of the log-weights (one per 256 weights at most)
+  DevBuf<int64_t> d_w;     // [n]: its capacity is the number of weights the scratch was made for
+  DevBuf<int64_t> d_cdf;
+  DevBuf<unsigned char> d_tmp;
   size_t tmpBytes = 0;
   // the one-launch analysis (pfFusedKernel): chunk totals + the total weight, the ring of per-launch barrier sets (all
   // zero at allocation; launch L uses set L % kBarSets and clears set (L + kBarAhead) % kBarSets), the stuck report
-  int64_t* d_blockSum = nullptr;      // [kFusedBlocks] + 1: the total
-  int64_t* d_threadIncl = nullptr;    // [kFusedBlocks][256]
-  unsigned long long* d_barrier = nullptr;   // [kBarSets][kBarSetWords] + 1: the stuck word
+  DevBuf<int64_t> d_blockSum;      // [kFusedBlocks] + 1: the total
+  DevBuf<int64_t> d_threadIncl;    // [kFusedBlocks][256]
+  DevBuf<unsigned long long> d_barrier;   // [kBarSets][kBarSetWords] + 1: the stuck word
   unsigned long long launches = 0;      // fused launches that were accepted by the runtime
   int occ[3] = {-1, -1, -1};            // resident workgroups per CU of pfFusedKernel<float,false> / <double,false> / <double,true>
-  void* d_sites = nullptr;              // sipnet_batch_pf_analysis_sites (sitesScratchFor)
-  size_t sitesBytes = 0;
-  void release() {
-    if (d_sites) (void)hipFree(d_sites);
-    d_sites = nullptr;
-    sitesBytes = 0;
-    if (d_max) (void)hipFree(d_max);
-    if (d_w) (void)hipFree(d_w);
-    if (d_cdf) (void)hipFree(d_cdf);
-    if (d_tmp) (void)hipFree(d_tmp);
-    if (d_blockSum) (void)hipFree(d_blockSum);
-    if (d_threadIncl) (void)hipFree(d_threadIncl);
-    if (d_barrier) (void)hipFree(d_barrier);
-    d_threadIncl = nullptr;
-    d_max = nullptr; d_w = d_cdf = nullptr; d_tmp = nullptr; cap = 0; tmpBytes = 0;
-    d_blockSum = nullptr; d_barrier = nullptr; launches = 0;
-    occ[0] = occ[1] = occ[2] = -1;
-  }
-  // no destructor: a thread_local's would run at thread exit, possibly after the HIP runtime is gone
+  DevBuf<unsigned char> d_sites;        // sipnet_batch_pf_analysis_sites (sitesScratchFor), bytes
 };
 namespace {
 constexpr int kMaxParts = 256;
 constexpr size_t kBarrierWords = (size_t)kBarSets * kBarSetWords + 1;   // + the stuck word
-thread_local PfScratch g_pf;
+// the host thread's scratch: a heap object behind a raw pointer that only sipnet_pf_release_scratch deletes -- a thread_local
+// OBJECT's destructor would free at thread exit, possibly after the HIP runtime is gone
+thread_local PfScratch* g_pf = nullptr;
+PfScratch* threadScratch() {
+  if (!g_pf) g_pf = new PfScratch();
+  return g_pf;
+}
 }  // namespace
 
 // scratch for n weights (the partial maxima: one per 256 of them at most)
 static int pfScratchFor(PfScratch& sc, int64_t n, hipStream_t stream) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
-  if (sc.device != dev || sc.cap < n) {
-    sc.release();
+  if (sc.device != dev || (int64_t)sc.d_w.capacity() < n) {
+    sc = PfScratch();   // (everything goes, the many-site block too; d_w, whose capacity says "made", comes last)
     sc.device = dev;
-    HIP_TRY(hipMalloc(&sc.d_max, (size_t)((n + 255) / 256 + kMaxParts) * sizeof(double)));
-    HIP_TRY(hipMalloc(&sc.d_w, (size_t)n * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&sc.d_cdf, (size_t)n * sizeof(int64_t)));
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, sc.tmpBytes, sc.d_w, sc.d_cdf, (int)n, stream));
-    HIP_TRY(hipMalloc(&sc.d_tmp, sc.tmpBytes));
-    HIP_TRY(hipMalloc(&sc.d_blockSum, (size_t)(kFusedBlocks + 1) * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&sc.d_threadIncl, (size_t)kFusedBlocks * 256 * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&sc.d_barrier, kBarrierWords * sizeof(unsigned long long)));
+    RC_TRY(sc.d_max.reserve((size_t)((n + 255) / 256 + kMaxParts)));
+    RC_TRY(sc.d_cdf.reserve((size_t)n));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, sc.tmpBytes, (int64_t*)nullptr, sc.d_cdf.get(), (int)n, stream));
+    RC_TRY(sc.d_tmp.reserve(sc.tmpBytes));
+    RC_TRY(sc.d_blockSum.reserve((size_t)(kFusedBlocks + 1)));
+    RC_TRY(sc.d_threadIncl.reserve((size_t)kFusedBlocks * 256));
+    RC_TRY(sc.d_barrier.reserve(kBarrierWords));
     HIP_TRY(hipMemsetAsync(sc.d_barrier, 0, kBarrierWords * sizeof(unsigned long long), stream));
-    sc.launches = 0;
-    sc.cap = n;
+    RC_TRY(sc.d_w.reserve((size_t)n));
   }
   return SIPNET_OK;
 }
@@ -1358,7 +1357,7 @@ static int ancestorsImpl(PfScratch& sc, const double* d_logw, int64_t n, double 
   }
   hipLaunchKernelGGL(fixedWeightKernel, dim3(grid), dim3(256), 0, stream, d_logw, n, partPtr ? partPtr : sc.d_max, parts, sc.d_w);
   size_t tmpBytes = sc.tmpBytes;
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(sc.d_tmp, tmpBytes, sc.d_w, sc.d_cdf, (int)n, stream));
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(sc.d_tmp, tmpBytes, sc.d_w.get(), sc.d_cdf.get(), (int)n, stream));
   hipLaunchKernelGGL(ancestorKernel, dim3(grid), dim3(256), 0, stream, sc.d_cdf, n, (int64_t)0, n, n, u0, d_ancestors,
                      d_total);
   HIP_TRY(hipGetLastError());
@@ -1371,7 +1370,7 @@ static int ancestorsImpl(PfScratch& sc, const double* d_logw, int64_t n, double 
 extern "C" int sipnet_pf_systematic_ancestors_async(const double* d_logw, int64_t n, double u0,
                                                     int32_t* d_ancestors, int64_t* d_fixed_weights,
                                                     int64_t* d_total, void* hip_stream) {
-  return ancestorsImpl(g_pf, d_logw, n, u0, d_ancestors, d_fixed_weights, d_total, 0, hip_stream);
+  return ancestorsImpl(*threadScratch(), d_logw, n, u0, d_ancestors, d_fixed_weights, d_total, 0, hip_stream);
 }
 
 int sipnet_pf_systematic_ancestors(const double* d_logw, int64_t n, double u0,
@@ -1383,7 +1382,7 @@ int sipnet_pf_systematic_ancestors(const double* d_logw, int64_t n, double u0,
   // the one host round trip: a filter with no surviving particle must be reported
   hipStream_t stream = (hipStream_t)hip_stream;
   int64_t total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, g_pf.d_cdf + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(&total, threadScratch()->d_cdf + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   if (total <= 0) {
     setError("sipnet_pf_systematic_ancestors: every particle has zero weight");
@@ -1395,22 +1394,12 @@ int sipnet_pf_systematic_ancestors(const double* d_logw, int64_t n, double u0,
 namespace {
 struct PlanScratch {
   int device = -1;
-  int64_t cap = 0;
-  int32_t *d_head = nullptr, *d_P = nullptr;
-  int64_t *d_first = nullptr, *d_counts = nullptr;  // [(kMaxWorld+1)*kMaxWorld], [4*kMaxWorld]
-  void* d_tmp = nullptr;
+  DevBuf<int32_t> d_head, d_P;           // [total]; d_P's capacity is the total the scratch was made for
+  DevBuf<int64_t> d_first, d_counts;     // [(kMaxWorld+1)*kMaxWorld], [4*kMaxWorld]
+  DevBuf<unsigned char> d_tmp;
   size_t tmpBytes = 0;
-  void release() {
-    if (d_head) (void)hipFree(d_head);
-    if (d_P) (void)hipFree(d_P);
-    if (d_first) (void)hipFree(d_first);
-    if (d_counts) (void)hipFree(d_counts);
-    if (d_tmp) (void)hipFree(d_tmp);
-    d_head = d_P = nullptr; d_first = d_counts = nullptr; d_tmp = nullptr; cap = 0; tmpBytes = 0;
-  }
-  // (no destructor, see PfScratch)
 };
-thread_local PlanScratch g_plan;
+thread_local PlanScratch* g_plan = nullptr;   // (a heap object, see g_pf)
 }  // namespace
 
 int sipnet_pf_exchange_plan(const int32_t* d_ancestors, int64_t n_local, int32_t world, int32_t rank,
@@ -1426,17 +1415,17 @@ int sipnet_pf_exchange_plan(const int32_t* d_ancestors, int64_t n_local, int32_t
   const int64_t total = n_local * world;
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
-  PlanScratch& sc = g_plan;
-  if (sc.device != dev || sc.cap < total) {
-    sc.release();
+  if (!g_plan) g_plan = new PlanScratch();
+  PlanScratch& sc = *g_plan;
+  if (sc.device != dev || (int64_t)sc.d_P.capacity() < total) {
+    sc = PlanScratch();   // (d_P, whose capacity says "made", comes last)
     sc.device = dev;
-    HIP_TRY(hipMalloc(&sc.d_head, (size_t)total * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&sc.d_P, (size_t)total * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&sc.d_first, (size_t)(kMaxWorld + 1) * kMaxWorld * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&sc.d_counts, (size_t)(4 * kMaxWorld + 1) * sizeof(int64_t)));   // counts, bases, validity flag
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sc.tmpBytes, sc.d_head, sc.d_P, (int)total, stream));
-    HIP_TRY(hipMalloc(&sc.d_tmp, sc.tmpBytes));
-    sc.cap = total;
+    RC_TRY(sc.d_head.reserve((size_t)total));
+    RC_TRY(sc.d_first.reserve((size_t)(kMaxWorld + 1) * kMaxWorld));
+    RC_TRY(sc.d_counts.reserve((size_t)(4 * kMaxWorld + 1)));   // counts, bases, validity flag
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sc.tmpBytes, sc.d_head.get(), (int32_t*)nullptr, (int)total, stream));
+    RC_TRY(sc.d_tmp.reserve(sc.tmpBytes));
+    RC_TRY(sc.d_P.reserve((size_t)total));
   }
   const int grid = (int)((total + 255) / 256);
   hipLaunchKernelGGL(planFirstKernel, dim3(world), dim3(kMaxWorld + 1), 0, stream, d_ancestors, n_local,
@@ -1445,7 +1434,7 @@ int sipnet_pf_exchange_plan(const int32_t* d_ancestors, int64_t n_local, int32_t
   HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int64_t), stream));
   hipLaunchKernelGGL(planHeadKernel, dim3(grid), dim3(256), 0, stream, d_ancestors, n_local, total, sc.d_head, d_bad);
   size_t tmpBytes = sc.tmpBytes;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc.d_tmp, tmpBytes, sc.d_head, sc.d_P, (int)total, stream));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc.d_tmp, tmpBytes, sc.d_head.get(), sc.d_P.get(), (int)total, stream));
   int64_t* d_bases = sc.d_counts + 2 * kMaxWorld;
   hipLaunchKernelGGL(planCountKernel, dim3(1), dim3(64), 0, stream, sc.d_first, sc.d_P, sc.d_head, total,
                      world, rank, sc.d_counts, d_bases);
@@ -1468,8 +1457,10 @@ int sipnet_pf_exchange_plan(const int32_t* d_ancestors, int64_t n_local, int32_t
 }
 
 void sipnet_pf_release_scratch(void) {
-  g_pf.release();
-  g_plan.release();
+  delete g_pf;
+  g_pf = nullptr;
+  delete g_plan;
+  g_plan = nullptr;
 }
 
 int sipnet_batch_pack_members(sipnet_batch* b, const int32_t* d_cols, int64_t n,
@@ -1505,8 +1496,7 @@ static int resampleColumns(sipnet_batch* b, const int32_t* d_src, const double* 
   rc = flushParams(b, stream);
   if (rc) return rc;
   const size_t nc = (size_t)b->ncol;
-  if (!b->d_state2) HIP_TRY(hipMalloc(&b->d_state2, nc * SIPNET_NSTATE * sizeof(double)));
-  if (!b->d_ring2) HIP_TRY(hipMalloc(&b->d_ring2, nc * SIPNET_RING_SLOTS * ringElemBytes(b)));
+  RC_TRY(ensureSpares(b, /*state=*/true, /*params=*/false, /*index=*/false));
   // every particle is here and carries its parameters: they stay where set_params put them, an index is resampled
   // (4 bytes per particle instead of 640; the one-wave forecast kernel reads through it).  With blocks received from
   // other ranks the rows themselves travel, as before.
@@ -1520,11 +1510,10 @@ static int resampleColumns(sipnet_batch* b, const int32_t* d_src, const double* 
     rc = materializeParams(b, stream);
     if (rc) return rc;
     pfDropBank(b);   // (parameter ROWS are about to move: the connection's index means nothing afterwards)
-    if (!b->d_prm2) HIP_TRY(hipMalloc(&b->d_prm2, nc * SIPNET_NPARAMS * sizeof(double)));
+    RC_TRY(ensureSpares(b, /*state=*/false, /*params=*/true, /*index=*/false));
   }
   if (byIndex) {
-    if (!b->d_prmId) HIP_TRY(hipMalloc(&b->d_prmId, nc * sizeof(int32_t)));
-    if (!b->d_prmId2) HIP_TRY(hipMalloc(&b->d_prmId2, nc * sizeof(int32_t)));
+    RC_TRY(ensureSpares(b, /*state=*/false, /*params=*/false, /*index=*/true));
     if (b->d_prmBank) {
       b->prmIndexed = true;   // (a connected filter's index is always current: slots of the bank)
     } else if (!b->prmIndexed) {
@@ -1689,14 +1678,7 @@ int sipnet_batch_pf_analysis(sipnet_batch* b, const void* d_plane, int32_t elem_
 // scratch of the many-site analysis: the sites' totals, and for the split path the chunks' maxima, sums and threads' sums
 static int sitesScratchFor(PfScratch& sc, int64_t nSites, int64_t nChunks) {
   const size_t bytes = (size_t)(nSites + nChunks * (2 + 256)) * sizeof(int64_t);
-  if (sc.sitesBytes < bytes) {
-    if (sc.d_sites) HIP_TRY(hipFree(sc.d_sites));
-    sc.d_sites = nullptr;
-    sc.sitesBytes = 0;
-    HIP_TRY(hipMalloc(&sc.d_sites, bytes));
-    sc.sitesBytes = bytes;
-  }
-  return SIPNET_OK;
+  return sc.d_sites.reserve(bytes);
 }
 
 int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps, int64_t ld,
@@ -1743,7 +1725,7 @@ int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t
   sa.logw = d_logw;
   sa.w = d_fixed_weights;
   sa.anc = d_ancestors;
-  sa.total = (int64_t*)sc.d_sites;
+  sa.total = (int64_t*)sc.d_sites.get();
   sa.totalOut = d_site_total;
   if (!split) {   // one workgroup per site, one launch
     if (elem_is_f32) hipLaunchKernelGGL(pfSitesKernel<float>, dim3((unsigned)nSites), dim3(256), 0, stream, sa);
@@ -1788,11 +1770,8 @@ int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t
 
 // ---- the filter across ranks by peer reads --------------------------------------------------------------------
 void pfRelease(sipnet_batch* b) {
-  if (b->pfScratch) {
-    b->pfScratch->release();
-    delete b->pfScratch;
-    b->pfScratch = nullptr;
-  }
+  delete b->pfScratch;
+  b->pfScratch = nullptr;
   if (b->pfPeers) {
     for (void* p : b->pfPeers->opened) (void)hipIpcCloseMemHandle(p);
     delete b->pfPeers;
@@ -1801,14 +1780,6 @@ void pfRelease(sipnet_batch* b) {
 }
 
 static_assert(sizeof(hipIpcMemHandle_t) <= sizeof(((sipnet_pf_peer*)nullptr)->ipc[0]), "sipnet_pf_peer::ipc holds a hipIpcMemHandle_t");
-
-static int ensureSpares(sipnet_batch* b, bool withParams) {
-  const size_t nc = (size_t)b->ncol;
-  if (!b->d_state2) HIP_TRY(hipMalloc(&b->d_state2, nc * SIPNET_NSTATE * sizeof(double)));
-  if (!b->d_ring2) HIP_TRY(hipMalloc(&b->d_ring2, nc * SIPNET_RING_SLOTS * ringElemBytes(b)));
-  if (withParams && !b->d_prm2) HIP_TRY(hipMalloc(&b->d_prm2, nc * SIPNET_NPARAMS * sizeof(double)));
-  return SIPNET_OK;
-}
 
 extern "C" {
 
@@ -1823,7 +1794,7 @@ int sipnet_batch_pf_publish(sipnet_batch* b, int32_t with_params, sipnet_pf_peer
   }
   int rc = useDevice(b);
   if (rc) return rc;
-  rc = ensureSpares(b, with_params != 0);
+  rc = ensureSpares(b, /*state=*/true, /*params=*/with_params != 0, /*index=*/false);
   if (rc) return rc;
   rc = waitIdle(b);                      // (whatever stream the batch last ran on: the spares and the parameters settle)
   if (rc) return rc;
@@ -1843,11 +1814,8 @@ int sipnet_batch_pf_publish(sipnet_batch* b, int32_t with_params, sipnet_pf_peer
   out->generic_exponents = b->genericExponents ? 1 : 0;
   const bool byIndex = with_params && !(b->kernelOptions & SIPNET_KOPT_PF_MOVE_PARAMS);
   out->params_by_index = byIndex ? 1 : 0;
-  if (byIndex) {   // the particles' index into the bank of all ranks' parameters (filled by connect), double-buffered like the state
-    const size_t nc = (size_t)b->ncol;
-    if (!b->d_prmId) HIP_TRY(hipMalloc(&b->d_prmId, nc * sizeof(int32_t)));
-    if (!b->d_prmId2) HIP_TRY(hipMalloc(&b->d_prmId2, nc * sizeof(int32_t)));
-  }
+  // the particles' index into the bank of all ranks' parameters (filled by connect), double-buffered like the state
+  if (byIndex) RC_TRY(ensureSpares(b, /*state=*/false, /*params=*/false, /*index=*/true));
   void* ptr[8] = {b->d_state, b->d_state2, b->d_ring, b->d_ring2, with_params ? b->d_prm : nullptr,
                   with_params ? b->d_prm2 : nullptr, byIndex ? b->d_prmId : nullptr, byIndex ? b->d_prmId2 : nullptr};
   out->ipc_valid = 1;
@@ -1873,8 +1841,8 @@ int sipnet_batch_pf_connect(sipnet_batch* b, int32_t world, int32_t rank, const 
   int rc = useDevice(b);
   if (rc) return rc;
   const sipnet_pf_peer& me = peers[rank];
-  if (me.process_id != (int64_t)getpid() || me.address[0] != (uint64_t)(uintptr_t)b->d_state ||
-      me.address[1] != (uint64_t)(uintptr_t)b->d_state2 || me.n_particles != b->ncol) {
+  if (me.process_id != (int64_t)getpid() || me.address[0] != (uint64_t)(uintptr_t)b->d_state.get() ||
+      me.address[1] != (uint64_t)(uintptr_t)b->d_state2.get() || me.n_particles != b->ncol) {
     setError("sipnet_batch_pf_connect: peers[rank] is not what this batch published (publish, then connect, with no "
              "resampling in between)");
     return SIPNET_ERR_BAD_ARGUMENT;
@@ -1944,9 +1912,8 @@ int sipnet_batch_pf_connect(sipnet_batch* b, int32_t world, int32_t rank, const 
     // where they are: peer-mapped HBM, as every later gather reads state and ring.)
     const int64_t pitch = (int64_t)world * pp->nmax;
     pfDropBank(b);
-    if (hipMalloc(&b->d_prmBank, (size_t)pitch * SIPNET_NPARAMS * sizeof(double)) != hipSuccess) {
+    if (b->d_prmBank.tryReserve((size_t)pitch * SIPNET_NPARAMS) != hipSuccess) {
       (void)hipGetLastError();
-      b->d_prmBank = nullptr;
       return fail("no memory for the bank of all ranks' parameters (SIPNET_KOPT_PF_MOVE_PARAMS does without)", SIPNET_ERR_INTERNAL);
     }
     b->prmBankPitch = pitch;
@@ -1964,7 +1931,7 @@ int sipnet_batch_pf_connect(sipnet_batch* b, int32_t world, int32_t rank, const 
     }
     b->prmIndexed = false;   // (d_prm is current too: nothing has been resampled yet)
   }
-  if ((!b->d_pfCrossing && hipMalloc(&b->d_pfCrossing, sizeof(unsigned long long)) != hipSuccess) ||
+  if (b->d_pfCrossing.tryReserve(1) != hipSuccess ||
       hipMemset(b->d_pfCrossing, 0, sizeof(unsigned long long)) != hipSuccess) {
     (void)hipGetLastError();
     pfDropBank(b);
@@ -2066,7 +2033,7 @@ int sipnet_batch_pf_resample_peers(sipnet_batch* b, const double* d_gathered, do
     tab.pitch[0] = (int32_t)b->ncol;
     withParams = true;
   }
-  rc = ensureSpares(b, withParams && !byIndex);
+  rc = ensureSpares(b, /*state=*/true, /*params=*/withParams && !byIndex, /*index=*/false);
   if (rc) return rc;
   const int64_t nSlots = (int64_t)tab.world * tab.nmax, stride = tab.nmax + (tab.nmax + 255) / 256;
   PfScratch& sc = scratchOf(b);
@@ -2108,7 +2075,7 @@ int sipnet_batch_pf_resample_peers(sipnet_batch* b, const double* d_gathered, do
     const int gridW = (int)((nSlots + 255) / 256);
     hipLaunchKernelGGL(fixedWeightGatheredKernel, dim3(gridW), dim3(256), 0, stream, d_gathered, tab.world, tab.nmax, stride, sc.d_w);
     size_t tmpBytes = sc.tmpBytes;
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(sc.d_tmp, tmpBytes, sc.d_w, sc.d_cdf, (int)nSlots, stream));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(sc.d_tmp, tmpBytes, sc.d_w.get(), sc.d_cdf.get(), (int)nSlots, stream));
     hipLaunchKernelGGL(ancestorKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sc.d_cdf, nSlots, first, n, nTotal, u0,
                        d_ancestors, sc.d_blockSum + kFusedBlocks);
     HIP_TRY(hipGetLastError());

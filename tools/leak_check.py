@@ -56,6 +56,6 @@ for i in range(300):
     if i in (20, 299):
         torch.cuda.synchronize(); torch.cuda.empty_cache()
         free, total = torch.cuda.mem_get_info()
-        print(i, "free GB", free / 1e9)
+        print(i, "free GB", free / 1e9, "live bytes of the library's own buffers (device, pinned)", sa.debug_live_bytes())
         if free0 is None: free0 = free
 print("leak MB over 279 iterations:", (free0 - free) / 1e6)
