@@ -1,4 +1,4 @@
-// batch_impl.h -- the batch object behind include/sipnet_amd.h (shared by engine.hip and pf.hip).
+// batch_impl.h -- the batch object behind include/sipnet_amd.h (shared by engine.hip, its engine_*.hip parts, pf.hip and enkf.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,7 +14,7 @@
 #include "plan_device.h"
 #include "step_kernel.h"
 
-using namespace sipnet;  // internal header: only engine.hip, pf.hip and enkf.hip include it
+using namespace sipnet;  // internal header: only engine.hip, engine_*.hip, pf.hip and enkf.hip include it
 
 #define HIP_TRY(expr)                                                         \
   do {                                                                        \
@@ -77,9 +77,9 @@ struct sipnet_batch {
   DevBuf<unsigned char> d_planScratch;
   double* d_devLog2 = nullptr;   // [nDevSites][n_steps] inside d_planScratch
   PinnedBuf<double> hostLog2;    // pinned staging of the host-computed log2(vpd)
-  PinnedBuf<double> hostGdd;     // pinned [n_sites][n_steps]: trackers.gdd after every record, the plan threads' chain (engine.hip deviceEligible)
+  PinnedBuf<double> hostGdd;     // pinned [n_sites][n_steps]: trackers.gdd after every record, the plan threads' chain (engine_plan.hip devicePrepass)
   PinnedBuf<unsigned char> hostEv;   // pinned, only while a site has events: per site evFirst[n_steps] evCount[n_steps] (int32), dTill[n_steps] tillAfter[n_steps]
-  std::vector<PlanLight> planLight;  // per site: the plan threads' pass before the records are built (engine.hip devicePrepass)
+  std::vector<PlanLight> planLight;  // per site: the plan threads' pass before the records are built (engine_plan.hip devicePrepass)
   bool devLog2Done = false;
   int32_t devPlanMaxSteps = 0;
   hipEvent_t evPlanDone = nullptr;   // behind the plan kernels: what the next forcing's climate copy waits for
@@ -185,6 +185,12 @@ struct sipnet_batch {
 int flushParams(sipnet_batch* b, hipStream_t stream);   // engine.hip: upload + convert what set_params left pending
 int materializeParams(sipnet_batch* b, hipStream_t stream);   // pf.hip: d_prm back into column order (no-op unless prmIndexed)
 void pfDropBank(sipnet_batch* b);   // pf.hip: a connected filter's bank of all ranks' parameters is void (new parameters, moved rows)
+// (the engine's own parts call these across files; nothing of them is exported from the library)
+#define SIPNET_LOCAL __attribute__((visibility("hidden")))
+SIPNET_LOCAL int uploadPlan(sipnet_batch* b, hipStream_t stream);       // engine_plan.hip: build every site's plan and send it
+SIPNET_LOCAL int ensureStepRecs(sipnet_batch* b, hipStream_t stream);   // engine_plan.hip: the strict-order kernel's records, on first use
+SIPNET_LOCAL int ensureFastRecs(sipnet_batch* b, hipStream_t stream);   // engine_plan.hip: the throughput kernels' records, on first use
+SIPNET_LOCAL int fillDeviceLog2(sipnet_batch* b, hipStream_t stream);   // engine_plan.hip: log2vpd of the device-built records
 
 // "This batch has work in flight on `stream`."  The event itself is recorded only when somebody needs it (a wait from
 // another stream, a host-side wait or query): work queued later on the SAME stream is ordered behind it anyway, and an
@@ -263,6 +269,14 @@ inline int markStaged(sipnet_batch* b, hipStream_t stream) {
 inline int waitStaged(sipnet_batch* b) {
   if (b->staged) HIP_TRY(hipEventSynchronize(b->evStaged));
   b->staged = false;
+  return SIPNET_OK;
+}
+// uploads travel on the batch's own copy stream (nothing but copies is ever queued on it, so they are not held up
+// behind another batch's step kernel in a shared hardware queue); the caller's stream waits for them
+SIPNET_LOCAL inline int joinUploads(sipnet_batch* b, hipStream_t stream) {
+  HIP_TRY(hipEventRecord(b->evStaged, b->upStream));
+  b->staged = true;
+  HIP_TRY(hipStreamWaitEvent(stream, b->evStaged, 0));
   return SIPNET_OK;
 }
 

@@ -27,7 +27,7 @@
 // (~25 us a site; measured on the device: 200 us, the add's dependent-issue latency) and send 8 bytes a step.
 // The records are bit-identical to buildSitePlan()'s -- except FastRec::log2vpd, which only members with dVpdExp != 2
 // read: OCML's log2 is not glibc's to the last bit, so that field is filled from a HOST-computed array when (and only
-// when) such a member exists (engine.hip, fillDeviceLog2).  tests/test_gpu_plan_device.py compares downloaded records
+// when) such a member exists (engine_plan.hip, fillDeviceLog2).  tests/test_gpu_plan_device.py compares downloaded records
 // and eviction lists byte by byte.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,7 +43,7 @@ namespace sipnet {
 // path, which reports it.
 constexpr double kDevPlanMinLen = 0.0202;
 // ... and whose step lengths come in long runs: at most this many steps outside the part of a run that one descriptor covers
-// (engine.hip deviceEligible; a year of half-hourly records: ~245)
+// (engine_plan.hip devicePrepass; a year of half-hourly records: ~245)
 constexpr int64_t kDevPlanMaxWalked = 1024;
 
 struct DevPlanSite {
@@ -53,7 +53,7 @@ struct DevPlanSite {
   const double* preW;     // device [SIPNET_RING_SLOTS]: weights of the ring's live entries before the first record, front first
   int32_t n;              // records of the site
   int32_t site;           // its position in the batch (records at fast + site * nT)
-  int32_t opBase;         // its first RingOp in the flat array (room for opCap = 2 n + preK + 8: engine.hip devRingOpRoom)
+  int32_t opBase;         // its first RingOp in the flat array (room for opCap = 2 n + preK + 8: engine_plan.hip devRingOpRoom)
   int32_t preK;           // number of those entries (a fresh ring: one, carrying the whole window -- runmean.c:44-52)
   int32_t preStart;       // the front one's slot
   int32_t preIns;         // their insert step in the eviction records: -1 fresh, 0 resumed (buildSitePlan's init)

@@ -1,4 +1,4 @@
-// plan_pool.h -- the plan threads: a pool that lives as long as the process, with no HIP in it (engine.hip uses it for
+// plan_pool.h -- the plan threads: a pool that lives as long as the process, with no HIP in it (engine_plan.hip uses it for
 // the site plans, the light passes before a device-built plan and the copies of a several-sites hand-over), so that it
 // builds -- and is raced -- under ThreadSanitizer on a box without a GPU (tests/c/plan_pool_tsan.cpp, `make san`).
 #pragma once

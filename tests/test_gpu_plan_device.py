@@ -286,7 +286,7 @@ def test_a_resumed_segment_is_built_on_the_device_too(base, prec):
 def test_a_resumed_ring_of_many_entries_fits_its_eviction_list(base):
     """a checkpoint's ring of ~241 half-hourly entries followed by a segment with a step long enough to evict them all at
     once: 2 n + preK evictions in the worst case, more than a fresh ring's 2 n -- the list's room follows the checkpoint
-    (engine.hip devRingOpRoom), the walk never writes past it, and the NEXT site's list is the host builder's bytes too"""
+    (engine_plan.hip devRingOpRoom), the walk never writes past it, and the NEXT site's list is the host builder's bytes too"""
     yc = FORCINGS["half-hourly year"]
     members = synth.perturbed_params(base, 64, seed=11)
     b1 = sa.Batch(sa.flags_from(), 1, 64, sa.F64, fast_math=True)

@@ -145,9 +145,9 @@ static void planFrom(const sipnet_clim_table* t) {
           fprintf(stderr, "buildSitePlanLight disagrees with buildSitePlan (status %d vs %d, resumed %d)\n", l.status, pf.status, resumed);
           abort();
         }
-        // the room a DEVICE-built site gets for its eviction list (engine.hip devRingOpRoom: 2 n + the live entries the ring starts
+        // the room a DEVICE-built site gets for its eviction list (engine_plan.hip devRingOpRoom: 2 n + the live entries the ring starts
         // with + 8) bounds the list the host builder produces -- for every ring the device is handed: one that carries the 5-day
-        // window (engine.hip devicePrepass)
+        // window (engine_plan.hip devicePrepass)
         if (pf.status == SIPNET_OK) {
           size_t preK = 1;
           double sum = 5.0;
@@ -198,7 +198,7 @@ static void parse(const std::string& kind, const std::string& path) {
       (void)sipnet_restart_check(&r, g_flags, 1, r.boundary_year, r.boundary_day + 1, 0.0, 0.5, &warn);
       (void)sipnet_restart_check_boundary_for_write(&r, &warn);
       (void)sipnet_io_write_restart((path + ".rewritten").c_str(), &r);
-      // what sipnet_batch_set_resume keeps of it for the site plan (engine.hip): the plans of the forcings that follow are
+      // what sipnet_batch_set_resume keeps of it for the site plan (engine_state.hip): the plans of the forcings that follow are
       // also built as resumed segments
       if (r.mean_length == SIPNET_RING_SLOTS && r.mean_start >= 0 && r.mean_start < SIPNET_RING_SLOTS && r.mean_last >= 0 &&
           r.mean_last < SIPNET_RING_SLOTS) {
