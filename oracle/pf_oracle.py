@@ -4,7 +4,7 @@ PARITY UNPINNED against the reference: PecanProject/sipnet has no particle filte
 runs one process per particle and moves SIPNET_RESTART files between cycles
 (docs/developer-guide/restart-checkpoint.md).  What is restated here is the textbook
 algorithm the engine implements (systematic resampling, e.g. Douc & Cappe 2005, with the
-integer-weight variant of sipnet_amd/csrc/pf.hip so that results are exact) and the
+integer-weight variant of sipnet_amd/csrc/pf_weights.inc so that results are exact) and the
 semantics of the exchange: new particle g of the global set = old particle ancestors[g].
 
 What pins it instead (tests/test_pf.py): hand-computed cases, the defining properties (every count the floor or ceiling of

@@ -20,16 +20,19 @@ def test_every_source_is_built_and_every_step_kernel_file_is_hashed():
             assert "$(HERE)" + f.rsplit(".", 1)[0] + ".o" in objs, f + " has no object in the Makefile's OBJS"
     hdrs = re.search(r"^HDRS := (.*?)\n\n", mk, re.M | re.S).group(1)
     for f in sorted(os.listdir(CSRC)):
-        if f.endswith(".inc") and not f.startswith(("coop_", "enkf_")):      # (coop_*.inc, enkf_*.inc: wildcards)
+        if f.endswith(".inc") and not f.startswith(("coop_", "enkf_", "pf_")):      # (coop_*.inc, enkf_*.inc, pf_*.inc: wildcards)
             assert f in hdrs, f + " is not a prerequisite of the objects"
     assert "$(wildcard $(HERE)coop_*.inc)" in hdrs and "$(wildcard $(HERE)enkf_*.inc)" in hdrs
+    assert "$(wildcard $(HERE)pf_*.inc)" in hdrs
     lib = open(os.path.join(helpers.REPO, "sipnet_amd", "_lib.py")).read()
     hashed = re.search(r"def kernel_source_sha16\(\):.*?for name in \((.*?)\):", lib, re.S).group(1)
-    # (enkf_*.inc are the parts of enkf.hip, a filter source around the step kernels: included there, and like it not hashed)
-    enkf = open(os.path.join(CSRC, "enkf.hip")).read()
+    # (enkf_*.inc and pf_*.inc are the parts of enkf.hip and pf.hip, filter sources around the step kernels: included there,
+    # and like them not hashed)
+    whole = {stem: open(os.path.join(CSRC, stem + ".hip")).read() for stem in ("enkf", "pf")}
     for f in sorted(os.listdir(CSRC)):
-        if f.endswith(".inc") and f.startswith("enkf_"):
-            assert '#include "%s"' % f in enkf, f + " is not included by enkf.hip"
+        if f.endswith(".inc") and f.startswith(("enkf_", "pf_")):
+            stem = f.split("_")[0]
+            assert '#include "%s"' % f in whole[stem], f + " is not included by %s.hip" % stem
             assert '"%s"' % f not in hashed, f + " is no step kernel source"
         elif f.endswith(".inc") or f in ("step_kernel.hip", "step_fast.hip", "step_coop.hip", "step_kernel.h", "fast_math.h"):
             assert '"%s"' % f in hashed, f + " is not in kernel_source_sha16's list"

@@ -1,4 +1,4 @@
-"""Particle-filter analysis step on the GPU (pf.hip; BASELINE config C5):
+"""Particle-filter analysis step on the GPU (pf.hip and its pf_*.inc parts; BASELINE config C5):
 likelihood weights, systematic resampling, packing and the resampling gather against the
 numpy oracle (oracle/pf_oracle.py), and a forecast -> analysis -> forecast cycle whose
 resampled particles continue exactly like their ancestors."""

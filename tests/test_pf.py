@@ -21,7 +21,7 @@ WORDS = 32 + 250
 
 
 class FakeBatch:
-    """CPU stand-in with pf.hip's packing layout: cols[words][ncol]"""
+    """CPU stand-in with the packing layout of pf_gather.inc: cols[words][ncol]"""
 
     def __init__(self, cols):
         self.cols = cols.clone()
