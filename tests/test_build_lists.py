@@ -36,6 +36,23 @@ def test_every_source_is_built_and_every_step_kernel_file_is_hashed():
             assert '"%s"' % f not in hashed, f + " is no step kernel source"
         elif f.endswith(".inc") or f in ("step_kernel.hip", "step_fast.hip", "step_coop.hip", "step_kernel.h", "fast_math.h"):
             assert '"%s"' % f in hashed, f + " is not in kernel_source_sha16's list"
+    # (cli_*.h are the parts of sipnet_cli.cpp: included from there, prerequisites of the CLI alone -- editing the CLI
+    # rebuilds no kernel -- and no step kernel sources)
+    parts = sorted(f for f in os.listdir(CSRC) if f.startswith("cli_") and f.endswith(".h"))
+    reached, queue = set(), ["sipnet_cli.cpp"]
+    while queue:
+        for inc in re.findall(r'^#include "(cli_[^"]*)"', open(os.path.join(CSRC, queue.pop())).read(), re.M):
+            if inc not in reached:
+                reached.add(inc)
+                queue.append(inc)
+    assert parts and reached == set(parts), (parts, sorted(reached))
+    assert re.search(r"^CLI_HDRS := \$\(wildcard \$\(HERE\)cli_\*\.h\)$", mk, re.M)
+    cli_rule = re.search(r"^\$\(PKG\)/bin/sipnet:(.*)$", mk, re.M).group(1)
+    assert "$(CLI_HDRS)" in cli_rule.split() and mk.count("$(CLI_HDRS)") == 1, "the CLI's parts belong to the CLI's rule alone"
+    assert "cli_" not in hdrs and "CLI_HDRS" not in hdrs
+    for f in parts:
+        assert '"%s"' % f not in hashed, f + " is no step kernel source"
+    assert "cli_" not in hashed
     # (step_coop_bounded.hip / step_coop_sums.hip / step_fast_sums.hip are two-line wrappers around hashed sources)
     for f in ("step_coop_bounded.hip", "step_coop_sums.hip", "step_fast_sums.hip"):
         body = [l for l in open(os.path.join(CSRC, f)).read().splitlines() if l.strip() and not l.startswith("//")]

@@ -126,6 +126,33 @@ def test_cli_ensemble_extension(tmp_path):
         assert differing <= 5, differing
 
 
+def test_cli_ensemble_params_table_errors_need_no_gpu(tmp_path):
+    """--ensemble-params: an unknown parameter name, a short row and a table without rows are input errors (exit 5),
+    raised once the climate is read and before any device call"""
+    stage("niwot", tmp_path)
+    for table, words in (("aMax frobnication\n8 1\n", ("frobnication", "m.txt")), ("aMax psnTOpt\n8 24\n9\n", ("short row",)),
+                         ("aMax psnTOpt\n", ("no members",))):
+        open(tmp_path / "m.txt", "w").write(table)
+        r = run_cli(tmp_path, "-i", "sipnet.in", "--ensemble-params", "m.txt")
+        assert r.returncode == 5, (table, r.returncode, r.stdout)
+        assert all(w in r.stdout for w in words), (table, r.stdout)
+
+
+def test_cli_sites_resolves_each_directory_like_a_run_started_inside_it(tmp_path):
+    """--sites: the first directory's sipnet.config is written, as its own run would write it, before the second
+    directory's missing climate ends the process (exit 6)"""
+    for case in ("niwot", "russell_2"):
+        (tmp_path / case).mkdir()
+        stage(case, tmp_path / case)
+    os.remove(tmp_path / "russell_2" / "sipnet.clim")
+    open(tmp_path / "runs.txt", "w").write("niwot\nrussell_2\n")
+    r = run_cli(tmp_path, "--sites", "runs.txt", "-i", "sipnet.in")
+    assert r.returncode == 6, r.stdout
+    got = open(tmp_path / "niwot" / "sipnet.config").read()
+    gold = open(os.path.join(helpers.smoke_dir("niwot"), "sipnet.config")).read()
+    assert config_body(got) == config_body(gold)
+
+
 def test_cli_devices_list_is_validated(tmp_path):
     """--devices: malformed lists are a CLI error (exit 8) before anything else happens"""
     stage("niwot", tmp_path)
