@@ -53,6 +53,22 @@ def test_every_source_is_built_and_every_step_kernel_file_is_hashed():
     for f in parts:
         assert '"%s"' % f not in hashed, f + " is no step kernel source"
     assert "cli_" not in hashed
+    # (node_*.h are the parts of node.cpp in the same way: included from there, prerequisites of node.o alone, not hashed)
+    parts = sorted(f for f in os.listdir(CSRC) if f.startswith("node_") and f.endswith(".h"))
+    reached, queue = set(), ["node.cpp"]
+    while queue:
+        for inc in re.findall(r'^#include "(node_[^"]*)"', open(os.path.join(CSRC, queue.pop())).read(), re.M):
+            if inc not in reached:
+                reached.add(inc)
+                queue.append(inc)
+    assert parts and reached == set(parts), (parts, sorted(reached))
+    assert re.search(r"^NODE_HDRS := \$\(wildcard \$\(HERE\)node_\*\.h\)$", mk, re.M)
+    assert re.search(r"^\$\(HERE\)node\.o:(.*)$", mk, re.M).group(1).split() == ["$(NODE_HDRS)"]
+    assert mk.count("$(NODE_HDRS)") == 1, "the node's parts belong to node.o's rule alone"
+    assert "node_" not in hdrs and "NODE_HDRS" not in hdrs
+    for f in parts:
+        assert '"%s"' % f not in hashed, f + " is no step kernel source"
+    assert "node_" not in hashed
     # (step_coop_bounded.hip / step_coop_sums.hip / step_fast_sums.hip are two-line wrappers around hashed sources)
     for f in ("step_coop_bounded.hip", "step_coop_sums.hip", "step_fast_sums.hip"):
         body = [l for l in open(os.path.join(CSRC, f)).read().splitlines() if l.strip() and not l.startswith("//")]

@@ -256,6 +256,86 @@ def test_site_shards_with_sites_of_different_lengths(base):
     nd.close()
 
 
+def _gathered_reduced_blocks(nd, k):
+    """what device k holds after run_gathering_reduced, as it lies there: [n][3][rows][ld], the segments put together"""
+    import ctypes as C
+    nd.sync()
+    parts = []
+    for j in range(nd.L.sipnet_node_n_segments(nd.h)):
+        first, rows, eb = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        ptr = nd.L.sipnet_node_gathered_reduced(nd.h, k, j, C.byref(first), C.byref(rows), C.byref(eb))
+        assert ptr and first.value == sum(p.shape[2] for p in parts)
+        parts.append(nd._to_host(ptr, (nd.n, 3, rows.value, nd.ld), np.float32 if eb.value == 4 else np.float64))
+    return np.concatenate(parts, axis=2)
+
+
+@pytest.mark.parametrize("fast", [False, True], ids=["strict-planes-summed", "throughput"])
+def test_reduced_gathers_with_sites_of_different_lengths(base, fast):
+    """the reduced gathers where the sites of three site shards (1 + 2 + 2) end at different records, inside, at and past
+    the segments' cuts.  Strict-order kernel: the planes summed on the second stream -- the whole ld-wide block of daily
+    sums on every device against ONE batch's planes summed on the host in step order; rows past a site's end and the
+    padding columns are zero.  Throughput kernel: the planes as floats, the whole block in the same way; and the sums
+    from the step kernel's own launch -- there only what is defined: for each site the groups that begin before its
+    end, in the shard's own n_sites_k * count_k columns"""
+    M, T, K = 16, 48 * 6, 48
+    lengths = [T // 2, T, 100, 37, T - 16]
+    flags = sa.flags_from()
+    clims = []
+    for s_, tl in enumerate(lengths):
+        raw = synth.half_hourly_year_raw(T, site=s_)
+        clims.append(synth.convert_raw(synth.round_like_file({k: v[:tl] for k, v in raw.items()})))
+    members = synth.perturbed_params(base, M)
+    b = one_batch(flags, clims, members)
+    b.set_math(fast)
+    planes = torch.zeros((3, T, 5 * M), dtype=torch.float64, device=DEV)
+    b.run(0, T, planes=planes)
+    want = planes.cpu().numpy().reshape(3, T, 5, M)
+    b.close()
+    groups = T // K
+    want_sums = np.zeros((3, groups, 5, M))
+    for t in range(T):                                  # in step order, like the kernel
+        want_sums[:, t // K] += want[:, t]
+    for s_, tl in enumerate(lengths):
+        assert (want[:, tl:, s_] == 0).all() and np.abs(want[0, :tl, s_]).max() > 0
+
+    nd = Node(flags, 5, M, devices=[0, 0, 0], shard=SHARD_SITES, fast_math=fast)
+    for s_ in range(5):
+        nd.set_climate(s_, clims[s_])
+    nd.set_params(None, members)
+    nd.setup()
+    assert nd.ld == 2 * M and [nd.site_range(q)[1] for q in range(3)] == [1, 2, 2]
+
+    def whole_block(rows_of_sites):                     # [3][R][5][M] -> [n][3][R][ld], zero where a shard has no column
+        out = np.zeros((nd.n, 3, rows_of_sites.shape[1], nd.ld), dtype=rows_of_sites.dtype)
+        for q in range(nd.n):
+            s0, sc = nd.site_range(q)
+            out[q][:, :, :sc * M] = rows_of_sites[:, :, s0:s0 + sc].reshape(3, -1, sc * M)
+        return out
+
+    nd.run_gathering_reduced(0, T, 3, "sums", K)        # cuts at records 96 and 192
+    assert nd.L.sipnet_node_reduced_in_kernel(nd.h) == int(fast)
+    for k in range(nd.n):
+        got = _gathered_reduced_blocks(nd, k)
+        assert got.dtype == np.float64 and got.shape == (3, 3, groups, nd.ld)
+        if not fast:
+            np.testing.assert_array_equal(got, whole_block(want_sums))
+            continue
+        for q in range(nd.n):
+            s0, sc = nd.site_range(q)
+            for s_ in range(s0, s0 + sc):
+                g_end = (lengths[s_] + K - 1) // K      # the groups that begin before the site's end
+                np.testing.assert_array_equal(got[q][:, :g_end, (s_ - s0) * M:(s_ - s0 + 1) * M], want_sums[:, :g_end, s_])
+    if fast:
+        nd.setup()
+        nd.run_gathering_reduced(0, T, 4, "f32")        # cuts at 64, 144, 208
+        for k in range(nd.n):
+            got = _gathered_reduced_blocks(nd, k)
+            assert got.dtype == np.float32
+            np.testing.assert_array_equal(got, whole_block(want.astype(np.float32)))
+    assert (nd.status() == 0).all()
+    nd.close()
+
+
 @pytest.mark.timeout(180)
 def test_a_failing_shard_does_not_leave_the_others_at_the_barrier(base):
     """two site shards on one device (event-ordered all-gathers: the shards' threads meet at a host barrier per
