@@ -110,7 +110,16 @@ class Restart(C.Structure):
             i = (i + 1) % 250
 
 
-class LaunchInfo(C.Structure):
+class _Record(C.Structure):
+    """a struct the library fills in for the caller to read"""
+
+    def as_dict(self):
+        """field name -> value (a char array as str)"""
+        values = ((n, getattr(self, n)) for n, _ in self._fields_)
+        return {n: v.decode() if isinstance(v, bytes) else v for n, v in values}
+
+
+class LaunchInfo(_Record):
     """struct sipnet_launch_info"""
     _fields_ = [("kernel", C.c_char * 96), ("grid", C.c_int32), ("block_threads", C.c_int32),
                 ("waves_per_simd", C.c_int32), ("lds_bytes", C.c_int32), ("num_cus", C.c_int32),
@@ -127,7 +136,7 @@ class PfPeer(C.Structure):
                 ("address", C.c_uint64 * 8), ("ipc", (C.c_ubyte * 64) * 8)]
 
 
-class PfInfo(C.Structure):
+class PfInfo(_Record):
     """struct sipnet_pf_info: what the last particle-filter analysis did, what the exchange has moved"""
     _fields_ = [("fused", C.c_int32), ("grid", C.c_int32), ("budget", C.c_int32), ("world", C.c_int32),
                 ("n_slots", C.c_int64), ("cycles", C.c_int64), ("crossing", C.c_int64),
@@ -416,3 +425,16 @@ class SipnetError(RuntimeError):
 def check(code, where=""):
     if code != OK:
         raise SipnetError(code, where)
+
+
+def ptr(x):
+    """the void* argument for a torch tensor or a numpy array (its first element); None stays None, the NULL pointer"""
+    if x is None:
+        return None
+    return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
+
+
+def c_array(T, xs):
+    """the ctypes array of the T's in xs, never of length zero (an empty list still gives the library a valid pointer)"""
+    xs = list(xs)
+    return (T * max(len(xs), 1))(*xs)

@@ -7,14 +7,26 @@ members and sites at once.  Outputs live in torch CUDA tensors that the caller
 """
 import collections
 import ctypes as C
+import weakref
 
 import numpy as np
 
-from ._lib import (F32_MIXED, F64, KERNEL_AUTO, NPARAMS, NREC, NSTATE, RING_SLOTS, Event, LaunchInfo,
-                   check, lib)
+from ._lib import (F64, KERNEL_AUTO, NDBG, NPARAMS, NREC, NSTATE, RING_SLOTS, EnkfObs, EnkfParam, EnkfSeries, Event,
+                   LaunchInfo, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
+from .config import pool_mask
+from .enkf_local import EnkfLocalization
 
 
 PlaneQuantiles = collections.namedtuple("PlaneQuantiles", "quant count crps rank path")
+
+# the EnKF analyses' arguments in the groups their C signatures have: ops (n_obs, operators, analysed mask), planes (pointers,
+# elements are floats, n_steps, ld), obs (obs, sd, inflation), info (d_site_info); held: what the pointers point into
+EnkfArgs = collections.namedtuple("EnkfArgs", "ops planes obs info held")
+
+
+def _dense(x, dtype, n=None):
+    """x is a contiguous device tensor of dtype (and of n elements)"""
+    return x.is_cuda and x.dtype == dtype and x.is_contiguous() and (n is None or x.numel() == n)
 
 
 def quantile_lds_members(f32=False):
@@ -28,8 +40,7 @@ def quantile_positions(n, q):
     qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
     lo = np.zeros(qs.size, dtype=np.int32)
     g = np.zeros(qs.size)
-    check(lib().sipnet_quantile_positions(int(n), int(qs.size), C.c_void_p(qs.ctypes.data), C.c_void_p(lo.ctypes.data),
-                                          C.c_void_p(g.ctypes.data)), "quantile_positions")
+    check(lib().sipnet_quantile_positions(int(n), int(qs.size), ptr(qs), ptr(lo), ptr(g)), "quantile_positions")
     return lo, g
 
 
@@ -88,8 +99,7 @@ class Batch:
         lds_bytes, num_cus, plan_threads, plan_build_ms, plan_upload_ms)."""
         li = LaunchInfo()
         check(self.L.sipnet_batch_last_launch(self.h, C.byref(li)), "last_launch")
-        return {n: (getattr(li, n).decode() if n == "kernel" else getattr(li, n))
-                for n, _ in LaunchInfo._fields_}
+        return li.as_dict()
 
     # -- lifetime ---------------------------------------------------------------
     def close(self):
@@ -133,9 +143,7 @@ class Batch:
         return int(self.L.sipnet_batch_site_nsteps(self.h, site))
 
     def set_events(self, site, events):
-        n = len(events)
-        arr = (Event * max(n, 1))(*events)
-        check(self.L.sipnet_batch_set_events(self.h, site, n, arr), "set_events")
+        check(self.L.sipnet_batch_set_events(self.h, site, len(events), c_array(Event, events)), "set_events")
 
     def set_params(self, site, raw, first_member=0):
         """site: a site index, or None / ALL_SITES = the same members at every site (one upload)"""
@@ -156,43 +164,43 @@ class Batch:
     def alloc_outputs(self, n_steps, full=False):
         t = self._torch
         planes = t.empty((3, n_steps, self.ncol), dtype=self.out_dtype, device=self.device)
-        rec = (t.empty((n_steps, NREC, self.ncol), dtype=t.float64, device=self.device)
-               if full else None)
-        return planes, rec
+        return planes, self._rec(n_steps) if full else None
+
+    def _rec(self, n_steps):
+        return self._torch.empty((n_steps, NREC, self.ncol), dtype=self._torch.float64, device=self.device)
+
+    def _steps(self, step0, n_steps):
+        """n_steps None: from step0 to the end of the (longest) forcing"""
+        return self.n_steps - step0 if n_steps is None else n_steps
+
+    def _plane(self, plane):
+        """the four plane arguments of a [rows][ld] tensor: pointer, elements are floats, rows, ld"""
+        return ptr(plane), int(plane.dtype == self._torch.float32), plane.shape[0], plane.shape[1]
 
     def run(self, step0=0, n_steps=None, planes=None, rec=None, want_planes=True, full=False):
         """== the time loop of runModelOutput() (sipnet.c:1969-1982).
 
         Returns (planes, rec): planes[3][n_steps][ncol] = NEE, GPP, ET per step;
         rec[n_steps][36][ncol] full records when `full`."""
-        if n_steps is None:
-            n_steps = self.n_steps - step0
+        n_steps = self._steps(step0, n_steps)
         if planes is None and want_planes:
             planes, _ = self.alloc_outputs(n_steps, False)
         if rec is None and full:
-            rec = self._torch.empty((n_steps, NREC, self.ncol), dtype=self._torch.float64,
-                                    device=self.device)
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-        nee = planes[0] if planes is not None else None
-        gpp = planes[1] if planes is not None else None
-        et = planes[2] if planes is not None else None
-        check(self.L.sipnet_batch_run(self.h, step0, n_steps, ptr(nee), ptr(gpp), ptr(et),
-                                      ptr(rec), self.ncol, self._stream()), "run")
+            rec = self._rec(n_steps)
+        nee, gpp, et = (planes[0], planes[1], planes[2]) if planes is not None else (None, None, None)
+        check(self.L.sipnet_batch_run(self.h, step0, n_steps, ptr(nee), ptr(gpp), ptr(et), ptr(rec), self.ncol,
+                                      self._stream()), "run")
         return planes, rec
 
     def run_debug(self, step0=0, n_steps=None):
         """The same advance with the reference's `--debug-log` content (debug_log.c:285-312).
 
         Returns (rec[n_steps][NREC][ncol], dbg[n_steps][NDBG][ncol]) device tensors."""
-        from ._lib import NDBG
         t = self._torch
-        if n_steps is None:
-            n_steps = self.n_steps - step0
-        rec = t.empty((n_steps, NREC, self.ncol), dtype=t.float64, device=self.device)
+        n_steps = self._steps(step0, n_steps)
+        rec = self._rec(n_steps)
         dbg = t.empty((n_steps, NDBG, self.ncol), dtype=t.float64, device=self.device)
-        check(self.L.sipnet_batch_run_debug(self.h, step0, n_steps, C.c_void_p(rec.data_ptr()),
-                                            C.c_void_p(dbg.data_ptr()), self.ncol,
-                                            self._stream()), "run_debug")
+        check(self.L.sipnet_batch_run_debug(self.h, step0, n_steps, ptr(rec), ptr(dbg), self.ncol, self._stream()), "run_debug")
         return rec, dbg
 
     def run_stats(self, step0=0, n_steps=None, planes=None, stats=None):
@@ -200,16 +208,14 @@ class Batch:
         (sipnet_batch_run_stats): stats[3][n_steps][n_sites][2] = sum, sum of squares over each
         site's members.  Returns (planes, stats)."""
         t = self._torch
-        if n_steps is None:
-            n_steps = self.n_steps - step0
+        n_steps = self._steps(step0, n_steps)
         if planes is None:
             planes, _ = self.alloc_outputs(n_steps, False)
         if stats is None:
             stats = t.empty((3, n_steps, self.n_sites, 2), dtype=t.float64, device=self.device)
-        assert stats.is_contiguous() and stats.dtype == t.float64
-        check(self.L.sipnet_batch_run_stats(self.h, step0, n_steps, C.c_void_p(planes[0].data_ptr()),
-                                            C.c_void_p(planes[1].data_ptr()), C.c_void_p(planes[2].data_ptr()),
-                                            self.ncol, C.c_void_p(stats.data_ptr()), self._stream()), "run_stats")
+        assert _dense(stats, t.float64)
+        check(self.L.sipnet_batch_run_stats(self.h, step0, n_steps, ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), self.ncol,
+                                            ptr(stats), self._stream()), "run_stats")
         return planes, stats
 
     def reduce_plane(self, plane, stats=None):
@@ -219,10 +225,8 @@ class Batch:
         n_steps = plane.shape[0]
         if stats is None:
             stats = t.empty((n_steps, self.n_sites, 2), dtype=t.float64, device=self.device)
-        check(self.L.sipnet_batch_reduce_plane(self.h, C.c_void_p(plane.data_ptr()),
-                                               int(plane.dtype == t.float32), n_steps, self.ncol,
-                                               C.c_void_p(stats.data_ptr()), self._stream()),
-              "reduce_plane")
+        check(self.L.sipnet_batch_reduce_plane(self.h, ptr(plane), int(plane.dtype == t.float32), n_steps, self.ncol,
+                                               ptr(stats), self._stream()), "reduce_plane")
         return stats
 
     def plane_quantiles(self, series, q, live_only=True, obs=None, want_crps=None, want_rank=None, path=0, out=None):
@@ -241,10 +245,9 @@ class Batch:
         if (not t.is_tensor(series) or not series.is_cuda or series.dim() != 2 or series.dtype not in (t.float32, t.float64)
                 or not series.is_contiguous() or series.shape[1] < self.ncol):
             raise ValueError(f"{what}: series must be a contiguous 2-D float32 / float64 device tensor [rows][ld >= {self.ncol}]")
-        rows, ld = int(series.shape[0]), int(series.shape[1])
+        plane = _, f32, rows, _ = self._plane(series)
         qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
         n_q = int(qs.size)
-        f32 = int(series.dtype == t.float32)
         ran = int(self.L.sipnet_quantile_path(self.n_members, f32, int(path)))      # (host only: the library's own rule; -1: the call refuses)
         if want_crps is None:
             want_crps = obs is not None and ran == 1
@@ -263,7 +266,7 @@ class Batch:
                 return None
             if x is None:
                 return t.empty(shape, dtype=dtype, device=self.device)
-            if x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or tuple(x.shape) != tuple(shape):
+            if not _dense(x, dtype) or tuple(x.shape) != tuple(shape):
                 raise ValueError(f"{what}: out's {name} must be a contiguous device tensor {tuple(shape)} of {dtype}")
             return x
 
@@ -271,10 +274,8 @@ class Batch:
         count = part(1, True, cells, t.int32, "count")
         crps = part(2, want_crps, cells, t.float64, "crps")
         rank = part(3, want_rank, cells + (2,), t.int32, "rank")
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-        check(self.L.sipnet_batch_plane_quantiles(self.h, ptr(series), f32, rows, ld, n_q, C.c_void_p(qs.ctypes.data),
-                                                  int(bool(live_only)), int(path), ptr(quant), ptr(count), ptr(obs),
-                                                  ptr(crps), ptr(rank), self._stream()), what)
+        check(self.L.sipnet_batch_plane_quantiles(self.h, *plane, n_q, ptr(qs), int(bool(live_only)), int(path), ptr(quant),
+                                                  ptr(count), ptr(obs), ptr(crps), ptr(rank), self._stream()), what)
         return PlaneQuantiles(quant, count, crps, rank, ran)
 
     def time_next_launch(self):
@@ -333,7 +334,6 @@ class Batch:
 
     def import_restart(self, site, restarts, first_member=0):
         """After setup(): overwrite the carried state of len(restarts) members of `site`."""
-        from ._lib import Restart
         arr = (Restart * len(restarts))(*restarts)
         check(self.L.sipnet_batch_import_restart(self.h, site, first_member, len(restarts), arr,
                                                  self._stream()), "import_restart")
@@ -345,10 +345,9 @@ class Batch:
         groups = (n_steps + sum_steps - 1) // sum_steps
         if out is None:
             out = t.empty((3, groups, self.ncol), dtype=t.float64, device=self.device)
-        assert out.dtype == t.float64 and out.is_contiguous() and out.shape == (3, groups, self.ncol)
-        check(self.L.sipnet_batch_run_sums(self.h, int(step0), int(n_steps), int(sum_steps), C.c_void_p(out[0].data_ptr()),
-                                           C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()), self.ncol,
-                                           self._stream()), "run_sums")
+        assert _dense(out, t.float64) and out.shape == (3, groups, self.ncol)
+        check(self.L.sipnet_batch_run_sums(self.h, int(step0), int(n_steps), int(sum_steps), ptr(out[0]), ptr(out[1]),
+                                           ptr(out[2]), self.ncol, self._stream()), "run_sums")
         return out
 
     def sums_in_kernel(self):
@@ -356,7 +355,6 @@ class Batch:
 
     def export_restart(self, site, member, n_steps_done, last_rec=None, prev_pools=None):
         """Checkpoint of one member after n_steps_done records (restartWriteCheckpoint)."""
-        from ._lib import Restart
         r = Restart()
         lr = pp = None
         if last_rec is not None:
@@ -377,39 +375,34 @@ class Batch:
         t = self._torch
         if out is None:
             out = t.empty(self.ncol, dtype=t.float64, device=self.device)
-        check(self.L.sipnet_batch_pf_log_weights(
-            self.h, C.c_void_p(plane.data_ptr()), int(plane.dtype == t.float32), plane.shape[0],
-            plane.shape[1], float(obs), float(sigma), C.c_void_p(out.data_ptr()), self._stream()),
-            "pf_log_weights")
+        check(self.L.sipnet_batch_pf_log_weights(self.h, *self._plane(plane), float(obs), float(sigma), ptr(out),
+                                                 self._stream()), "pf_log_weights")
         return out
 
     def pf_arm(self, obs, sigma):
         """sipnet_batch_pf_arm: the next run() (one-wave kernel, planes only) also leaves the log-weights that
         pf_analysis_local(planes[0], obs, sigma, ...) would otherwise compute in a pass of its own"""
-        t = self._torch
+        check(self.L.sipnet_batch_pf_arm(self.h, float(obs), float(sigma), ptr(self._pf_buffers()[0])), "pf_arm")
+
+    def _pf_buffers(self):
+        """(log-weights f64 [ncol], ancestors int32 [ncol]) of pf_arm and pf_analysis_local, made once"""
         if getattr(self, "_pf_buf", None) is None:
+            t = self._torch
             self._pf_buf = (t.empty(self.ncol, dtype=t.float64, device=self.device),
                             t.empty(self.ncol, dtype=t.int32, device=self.device))
-        check(self.L.sipnet_batch_pf_arm(self.h, float(obs), float(sigma), C.c_void_p(self._pf_buf[0].data_ptr())), "pf_arm")
+        return self._pf_buf
 
     def pf_arm_block(self, obs, sigma, block):
         """the same for a connected filter: the next run() leaves the log-weights in `block` (this rank's slice of the
         all-gather's buffer, pf_local_weights' target), which then only adds the block maxima"""
-        check(self.L.sipnet_batch_pf_arm(self.h, float(obs), float(sigma), C.c_void_p(block.data_ptr())), "pf_arm")
+        check(self.L.sipnet_batch_pf_arm(self.h, float(obs), float(sigma), ptr(block)), "pf_arm")
 
     def pf_analysis_local(self, plane, obs, sigma, u0, with_params=False, total_out=None):
         """log-weights -> systematic resampling -> resample, all particles in this batch, ONE library call
         (sipnet_batch_pf_analysis).  Returns (ancestors int32 [ncol], logw f64 [ncol]) on the device."""
-        t = self._torch
-        if getattr(self, "_pf_buf", None) is None:
-            self._pf_buf = (t.empty(self.ncol, dtype=t.float64, device=self.device),
-                            t.empty(self.ncol, dtype=t.int32, device=self.device))
-        logw, anc = self._pf_buf
-        check(self.L.sipnet_batch_pf_analysis(
-            self.h, C.c_void_p(plane.data_ptr()), int(plane.dtype == t.float32), plane.shape[0], plane.shape[1],
-            float(obs), float(sigma), float(u0), int(with_params), C.c_void_p(logw.data_ptr()),
-            C.c_void_p(anc.data_ptr()), C.c_void_p(total_out.data_ptr()) if total_out is not None else None,
-            self._stream()), "pf_analysis")
+        logw, anc = self._pf_buffers()
+        check(self.L.sipnet_batch_pf_analysis(self.h, *self._plane(plane), float(obs), float(sigma), float(u0), int(with_params),
+                                              ptr(logw), ptr(anc), ptr(total_out), self._stream()), "pf_analysis")
         return anc, logw
 
     def pf_analysis_sites(self, plane, obs, sigma, u0, with_params=False, total_out=None, return_fixed=False):
@@ -420,7 +413,7 @@ class Batch:
         t = self._torch
 
         def per_site(x):
-            x = t.as_tensor(x, dtype=t.float64).reshape(-1).to(self.device).contiguous()
+            x = self._flat64(x)
             assert x.numel() == self.n_sites
             return x
 
@@ -429,13 +422,10 @@ class Batch:
         anc = t.empty(self.ncol, dtype=t.int32, device=self.device)
         fixed = t.empty(self.ncol, dtype=t.int64, device=self.device) if return_fixed else None
         if total_out is not None:
-            assert total_out.dtype == t.int64 and total_out.is_contiguous() and total_out.numel() == self.n_sites
-        check(self.L.sipnet_batch_pf_analysis_sites(
-            self.h, C.c_void_p(plane.data_ptr()), int(plane.dtype == t.float32), plane.shape[0], plane.shape[1],
-            C.c_void_p(obs.data_ptr()), C.c_void_p(sigma.data_ptr()), C.c_void_p(u0.data_ptr()), int(with_params),
-            C.c_void_p(logw.data_ptr()), C.c_void_p(anc.data_ptr()),
-            C.c_void_p(fixed.data_ptr()) if fixed is not None else None,
-            C.c_void_p(total_out.data_ptr()) if total_out is not None else None, self._stream()), "pf_analysis_sites")
+            assert _dense(total_out, t.int64, self.n_sites)
+        check(self.L.sipnet_batch_pf_analysis_sites(self.h, *self._plane(plane), ptr(obs), ptr(sigma), ptr(u0), int(with_params),
+                                                    ptr(logw), ptr(anc), ptr(fixed), ptr(total_out), self._stream()),
+              "pf_analysis_sites")
         return (anc, logw, fixed) if return_fixed else (anc, logw)
 
     def enkf_analysis_sites(self, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
@@ -446,9 +436,9 @@ class Batch:
         operator reads); inflation: one value per site (None: 1).  info_out: int32 device tensor [n_sites][4] for
         {code, observations used, live members, members kept on their forecast} (no host synchronisation); without it the
         call checks the inputs first and raises before anything is written."""
-        args, keep = self._enkf_args("enkf_analysis_sites", obs, sd, operators, analysed, planes, inflation, info_out)
-        check(self.L.sipnet_batch_enkf_analysis_sites(self.h, *args, self._stream()), "enkf_analysis_sites")
-        del keep
+        a = self._enkf_args("enkf_analysis_sites", obs, sd, operators, analysed, planes, inflation, info_out)
+        check(self.L.sipnet_batch_enkf_analysis_sites(self.h, *a.ops, *a.planes, *a.obs, a.info, self._stream()),
+              "enkf_analysis_sites")
 
     def enkf_analysis_joint(self, obs, sd, operators, analysed, params, planes=None, inflation=None, param_inflation=None,
                             info_out=None):
@@ -457,20 +447,11 @@ class Batch:
         next to the pools.  params: sa.enkf_param(name, lo, hi), at most sa.ENKF_MAX_PARAMS (bounds in file units; the
         members' converted rows are clipped into them and rewritten); param_inflation: one value per site for the
         parameter variables (None: 1); the other arguments as enkf_analysis_sites."""
-        from ._lib import EnkfParam
-        t = self._torch
-        args, keep = self._enkf_args("enkf_analysis_joint", obs, sd, operators, analysed, planes, inflation, info_out)
-        prm = list(params)
-        arr = (EnkfParam * max(len(prm), 1))(*prm)
-        pinfl = None
-        if param_inflation is not None:
-            pinfl = t.as_tensor(param_inflation, dtype=t.float64).reshape(-1).to(self.device).contiguous()
-            if pinfl.numel() != self.n_sites:
-                raise ValueError(f"enkf_analysis_joint: param_inflation needs {self.n_sites} values, got {pinfl.numel()}")
-        check(self.L.sipnet_batch_enkf_analysis_joint(
-            self.h, *args[:3], len(prm), arr, *args[3:10], C.c_void_p(pinfl.data_ptr()) if pinfl is not None else None,
-            args[10], self._stream()), "enkf_analysis_joint")
-        del keep
+        what = "enkf_analysis_joint"
+        a = self._enkf_args(what, obs, sd, operators, analysed, planes, inflation, info_out)
+        prm, pinfl = self._enkf_params(what, params, param_inflation)
+        check(self.L.sipnet_batch_enkf_analysis_joint(self.h, *a.ops, *prm, *a.planes, *a.obs, ptr(pinfl), a.info,
+                                                      self._stream()), what)
 
     def enkf_analysis_smooth(self, obs, sd, operators, analysed, series, params=(), planes=None, inflation=None,
                              param_inflation=None, info_out=None):
@@ -481,17 +462,10 @@ class Batch:
         [3][groups][ncol]) counts as one series per leading index.  At most sa.ENKF_MAX_SERIES.  Live members of analysed
         sites get the filter's value, everything else dst = src.  Returns the list of dst tensors; the other arguments as
         enkf_analysis_joint."""
-        from ._lib import EnkfParam, EnkfSeries
         t = self._torch
         what = "enkf_analysis_smooth"
-        args, keep = self._enkf_args(what, obs, sd, operators, analysed, planes, inflation, info_out)
-        prm = list(params)
-        arr = (EnkfParam * max(len(prm), 1))(*prm)
-        pinfl = None
-        if param_inflation is not None:
-            pinfl = t.as_tensor(param_inflation, dtype=t.float64).reshape(-1).to(self.device).contiguous()
-            if pinfl.numel() != self.n_sites:
-                raise ValueError(f"{what}: param_inflation needs {self.n_sites} values, got {pinfl.numel()}")
+        a = self._enkf_args(what, obs, sd, operators, analysed, planes, inflation, info_out)
+        prm, pinfl = self._enkf_params(what, params, param_inflation)
         pairs = []
         for item in series:
             src, dst = item if isinstance(item, (tuple, list)) else (item, item)
@@ -499,7 +473,7 @@ class Batch:
                 pairs += [(src[k], dst[k]) for k in range(src.shape[0])]
             else:
                 pairs.append((src, dst))
-        desc = (EnkfSeries * max(len(pairs), 1))()
+        desc = []
         for k, (src, dst) in enumerate(pairs):
             for x in (src, dst):
                 if not x.is_cuda or x.dim() != 2 or x.dtype not in (t.float32, t.float64) or x.stride(1) != 1:
@@ -510,11 +484,9 @@ class Batch:
             if src.shape[1] < self.ncol:
                 raise ValueError(f"{what}: series {k} has {src.shape[1]} columns, the batch {self.ncol}")
             ld = src.stride(0) if src.shape[0] > 1 else src.shape[1]
-            desc[k] = EnkfSeries(src.data_ptr(), dst.data_ptr(), src.shape[0], int(src.dtype == t.float32), ld)
-        check(self.L.sipnet_batch_enkf_analysis_smooth(
-            self.h, *args[:3], len(prm), arr, *args[3:10], C.c_void_p(pinfl.data_ptr()) if pinfl is not None else None,
-            len(pairs), desc, args[10], self._stream()), what)
-        del keep
+            desc.append(EnkfSeries(src.data_ptr(), dst.data_ptr(), src.shape[0], int(src.dtype == t.float32), ld))
+        check(self.L.sipnet_batch_enkf_analysis_smooth(self.h, *a.ops, *prm, *a.planes, *a.obs, ptr(pinfl), len(pairs),
+                                                       c_array(EnkfSeries, desc), a.info, self._stream()), what)
         return [dst for _, dst in pairs]
 
     def get_params(self, file_units=False):
@@ -528,10 +500,8 @@ class Batch:
         """a localization of this batch's sites for enkf_analysis_local (sipnet_batch_enkf_local_create): site s's neighbours
         nbr[nbr_ptr[s]:nbr_ptr[s + 1]] (strictly ascending, not s) with tapers rho in (0, 1] -- e.g. sa.gaspari_cohn's CSR
         arrays -- for n_obs observation columns.  -> an EnkfLocalization (.n_levels, .close()); closing the batch closes it."""
-        from .enkf_local import EnkfLocalization
         loc = EnkfLocalization(self, nbr_ptr, nbr, rho, n_obs)
         if not hasattr(self, "_localizations"):
-            import weakref
             self._localizations = weakref.WeakSet()
         self._localizations.add(loc)
         return loc
@@ -542,9 +512,9 @@ class Batch:
         localization's tapers.  local: enkf_localization(...) of this batch with n_obs = len(operators); the other
         arguments as enkf_analysis_sites."""
         loc = self._open_localization("enkf_analysis_local", local)
-        args, keep = self._enkf_args("enkf_analysis_local", obs, sd, operators, analysed, planes, inflation, info_out)
-        check(self.L.sipnet_batch_enkf_analysis_local(self.h, loc, *args, self._stream()), "enkf_analysis_local")
-        del keep
+        a = self._enkf_args("enkf_analysis_local", obs, sd, operators, analysed, planes, inflation, info_out)
+        check(self.L.sipnet_batch_enkf_analysis_local(self.h, loc, *a.ops, *a.planes, *a.obs, a.info, self._stream()),
+              "enkf_analysis_local")
 
     def enkf_analysis_block(self, local, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None,
                             rows_out=None):
@@ -555,19 +525,14 @@ class Batch:
         n_obs = len(operators) and max_rows <= sa.ENKF_BLOCK_MAX_ROWS; rows_out: int32 device tensor [n_sites][2] for
         {rows used, rows dropped}; the other arguments as enkf_analysis_sites."""
         loc = self._open_localization("enkf_analysis_block", local)
-        t = self._torch
-        if rows_out is not None and (rows_out.dtype != t.int32 or not rows_out.is_contiguous() or not rows_out.is_cuda
-                                     or rows_out.numel() != 2 * self.n_sites):
+        if rows_out is not None and not _dense(rows_out, self._torch.int32, 2 * self.n_sites):
             raise ValueError("enkf_analysis_block: rows_out must be a contiguous int32 device tensor of n_sites x 2")
-        args, keep = self._enkf_args("enkf_analysis_block", obs, sd, operators, analysed, planes, inflation, info_out)
-        check(self.L.sipnet_batch_enkf_analysis_block(self.h, loc, *args,
-                                                      C.c_void_p(rows_out.data_ptr()) if rows_out is not None else None,
+        a = self._enkf_args("enkf_analysis_block", obs, sd, operators, analysed, planes, inflation, info_out)
+        check(self.L.sipnet_batch_enkf_analysis_block(self.h, loc, *a.ops, *a.planes, *a.obs, a.info, ptr(rows_out),
                                                       self._stream()), "enkf_analysis_block")
-        del keep
 
     def enkf_moment_words(self, operators, analysed):
         """doubles in one site's moment block of enkf_shard_moments (sipnet_enkf_moment_words)"""
-        from .config import pool_mask
         return int(self.L.sipnet_enkf_moment_words(bin(pool_mask(analysed)).count("1"), len(list(operators))))
 
     def enkf_shard_moments(self, operators, analysed, planes=None, out=None):
@@ -579,16 +544,15 @@ class Batch:
         t = self._torch
         what = "enkf_shard_moments"
         ops = list(operators)
-        args, keep = self._enkf_args(what, None, None, ops, analysed, planes, None, None)
+        a = self._enkf_args(what, None, None, ops, analysed, planes, None, None)
         W = self.enkf_moment_words(ops, analysed)
         if W < 0:
             raise ValueError(f"{what}: needs 1..16 operators and 1..13 analysed pools")
         if out is None:
             out = t.empty((self.n_sites, W), dtype=t.float64, device=self.device)
-        elif out.dtype != t.float64 or not out.is_contiguous() or not out.is_cuda or out.numel() != self.n_sites * W:
+        elif not _dense(out, t.float64, self.n_sites * W):
             raise ValueError(f"{what}: out must be a contiguous float64 device tensor of n_sites x {W}")
-        check(self.L.sipnet_batch_enkf_shard_moments(self.h, *args[:7], C.c_void_p(out.data_ptr()), self._stream()), what)
-        del keep
+        check(self.L.sipnet_batch_enkf_shard_moments(self.h, *a.ops, *a.planes, ptr(out), self._stream()), what)
         return out.view(self.n_sites, W)
 
     def enkf_analysis_sharded(self, gathered, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
@@ -601,13 +565,11 @@ class Batch:
         what = "enkf_analysis_sharded"
         ops = list(operators)
         W = self.enkf_moment_words(ops, analysed)
-        if (gathered.dtype != t.float64 or not gathered.is_contiguous() or not gathered.is_cuda or gathered.dim() != 3
-                or tuple(gathered.shape[1:]) != (self.n_sites, W)):
+        if not _dense(gathered, t.float64) or gathered.dim() != 3 or tuple(gathered.shape[1:]) != (self.n_sites, W):
             raise ValueError(f"{what}: gathered must be a contiguous float64 device tensor [world][{self.n_sites}][{W}]")
-        args, keep = self._enkf_args(what, obs, sd, ops, analysed, planes, inflation, info_out)
-        check(self.L.sipnet_batch_enkf_analysis_sharded(self.h, *args[:10], int(gathered.shape[0]),
-                                                        C.c_void_p(gathered.data_ptr()), args[10], self._stream()), what)
-        del keep
+        a = self._enkf_args(what, obs, sd, ops, analysed, planes, inflation, info_out)
+        check(self.L.sipnet_batch_enkf_analysis_sharded(self.h, *a.ops, *a.planes, *a.obs, int(gathered.shape[0]), ptr(gathered),
+                                                        a.info, self._stream()), what)
 
     @staticmethod
     def _open_localization(what, local):
@@ -616,25 +578,37 @@ class Batch:
             raise ValueError(f"{what}: the localization is closed")
         return local.h
 
+    def _flat64(self, x):
+        """x (an array-like or a tensor) as a contiguous flat float64 tensor on the batch's device"""
+        t = self._torch
+        return t.as_tensor(x, dtype=t.float64).reshape(-1).to(self.device).contiguous()
+
+    def _upload(self, what, x, n, name):
+        """_flat64(x), which must hold n values; None stays None"""
+        if x is None:
+            return None
+        x = self._flat64(x)
+        if x.numel() != n:
+            raise ValueError(f"{what}: {name} needs {n} values, got {x.numel()}")
+        return x
+
+    def _enkf_params(self, what, params, param_inflation):
+        """the joint analyses' (n_params, EnkfParam array), and the checked param_inflation on the device (None: 1), which
+        the caller holds until the call"""
+        prm = list(params)
+        return (len(prm), c_array(EnkfParam, prm)), self._upload(what, param_inflation, self.n_sites, "param_inflation")
+
     def _enkf_args(self, what, obs, sd, operators, analysed, planes, inflation, info_out):
-        """the EnKF analyses' arguments from n_obs to d_site_info, and the uploaded tensors they point into (keep them
-        alive until the call)"""
-        from ._lib import EnkfObs
-        from .config import pool_mask
+        """the EnKF analyses' arguments from n_obs to d_site_info as an EnkfArgs; it holds the uploaded tensors the
+        pointers point into, so it must live until the call"""
         t = self._torch
         ops = list(operators)
         n_obs = len(ops)
-
-        def dev(x, n, name):
-            x = t.as_tensor(x, dtype=t.float64).reshape(-1).to(self.device).contiguous()
-            if x.numel() != n:
-                raise ValueError(f"{what}: {name} needs {n} values, got {x.numel()}")
-            return x
-
         if obs is not None:                              # (None: a call without observations, enkf_shard_moments)
-            obs, sd = dev(obs, self.n_sites * n_obs, "obs"), dev(sd, self.n_sites * n_obs, "sd")
-        infl = dev(inflation, self.n_sites, "inflation") if inflation is not None else None
-        arr = (EnkfObs * max(n_obs, 1))(*ops)
+            obs = self._upload(what, obs, self.n_sites * n_obs, "obs")
+            sd = self._upload(what, sd, self.n_sites * n_obs, "sd")
+        infl = self._upload(what, inflation, self.n_sites, "inflation")
+        arr = c_array(EnkfObs, ops)
         ptrs = (C.c_void_p * 3)()
         f32, n_steps, ld = 0, 0, 0
         if planes is not None:
@@ -652,27 +626,21 @@ class Batch:
                 raise ValueError(f"{what}: the planes differ in dtype, step count or row pitch: " + str(layouts))
             if layouts:
                 f32, n_steps, ld = layouts.pop()
-        if info_out is not None and (info_out.dtype != t.int32 or not info_out.is_contiguous() or not info_out.is_cuda
-                                     or info_out.numel() != 4 * self.n_sites):
+        if info_out is not None and not _dense(info_out, t.int32, 4 * self.n_sites):
             raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x 4")
-        args = (n_obs, arr, pool_mask(analysed), ptrs if planes is not None else None, f32, n_steps, ld,
-                C.c_void_p(obs.data_ptr()) if obs is not None else None, C.c_void_p(sd.data_ptr()) if sd is not None else None,
-                C.c_void_p(infl.data_ptr()) if infl is not None else None,
-                C.c_void_p(info_out.data_ptr()) if info_out is not None else None)
-        return args, (obs, sd, infl, arr, ptrs)
+        return EnkfArgs((n_obs, arr, pool_mask(analysed)), (ptrs if planes is not None else None, f32, n_steps, ld),
+                        (ptr(obs), ptr(sd), ptr(infl)), ptr(info_out), (obs, sd, infl))
 
     # -- the filter across ranks by peer reads (sipnet_batch_pf_publish / _connect / _resample_peers) ----------
     def pf_publish(self, with_params=True):
         """-> bytes of this batch's sipnet_pf_peer descriptor (exchange them, then pf_connect)"""
-        from ._lib import PfPeer
         d = PfPeer()
         check(self.L.sipnet_batch_pf_publish(self.h, int(with_params), C.byref(d)), "pf_publish")
         return bytes(d)
 
     def pf_connect(self, descriptors, rank):
         """descriptors: every rank's pf_publish() bytes in rank order"""
-        from ._lib import PfPeer
-        arr = (PfPeer * len(descriptors))(*[PfPeer.from_buffer_copy(x) for x in descriptors])
+        arr = c_array(PfPeer, [PfPeer.from_buffer_copy(x) for x in descriptors])
         check(self.L.sipnet_batch_pf_connect(self.h, len(descriptors), int(rank), arr), "pf_connect")
         self._pf_gathered = None
 
@@ -682,10 +650,9 @@ class Batch:
     def pf_info(self):
         """sipnet_batch_pf_info: what the last analysis did (one launch or several, its grid, the resident-workgroup
         budget) and how many of this rank's particles have crossed ranks since pf_connect (synchronises the stream)"""
-        from ._lib import PfInfo
         d = PfInfo()
         check(self.L.sipnet_batch_pf_info(self.h, C.byref(d), self._stream()), "pf_info")
-        return {k: getattr(d, k) for k, _ in PfInfo._fields_}
+        return d.as_dict()
 
     def debug_set_num_cus(self, n):
         """test hook: pretend the device has n compute units (32 = one partition of a CPX-mode MI355X)"""
@@ -703,23 +670,20 @@ class Batch:
     def pf_local_weights(self, plane, obs, sigma, block):
         """this rank's block [nmax log-weights | block maxima] of the all-gather, into `block` (f64 device
         tensor of pf_block_len() entries, e.g. this rank's slice of the gathered buffer)"""
-        t = self._torch
-        assert block.dtype == t.float64 and block.is_contiguous() and block.numel() == self.pf_block_len()
-        check(self.L.sipnet_batch_pf_local_weights(
-            self.h, C.c_void_p(plane.data_ptr()), int(plane.dtype == t.float32), plane.shape[0], plane.shape[1],
-            float(obs), float(sigma), C.c_void_p(block.data_ptr()), self._stream()), "pf_local_weights")
+        assert _dense(block, self._torch.float64, self.pf_block_len())
+        check(self.L.sipnet_batch_pf_local_weights(self.h, *self._plane(plane), float(obs), float(sigma), ptr(block),
+                                                   self._stream()), "pf_local_weights")
         return block
 
     def pf_resample_peers(self, gathered, u0, ancestors=None, total_out=None):
         """gathered[world][pf_block_len()]: every rank's block.  Resamples this rank's particles from wherever
         their ancestors live (peer reads); returns the ancestors' slots (int32 [ncol])."""
         t = self._torch
-        assert gathered.dtype == t.float64 and gathered.is_contiguous()
+        assert _dense(gathered, t.float64)
         if ancestors is None:
             ancestors = t.empty(self.ncol, dtype=t.int32, device=self.device)
-        check(self.L.sipnet_batch_pf_resample_peers(
-            self.h, C.c_void_p(gathered.data_ptr()), float(u0), C.c_void_p(ancestors.data_ptr()),
-            C.c_void_p(total_out.data_ptr()) if total_out is not None else None, self._stream()), "pf_resample_peers")
+        check(self.L.sipnet_batch_pf_resample_peers(self.h, ptr(gathered), float(u0), ptr(ancestors), ptr(total_out),
+                                                    self._stream()), "pf_resample_peers")
         return ancestors
 
     def pack_members(self, cols, with_params=False):
@@ -730,8 +694,7 @@ class Batch:
         cols = cols.to(device=self.device, dtype=t.int32).contiguous()
         buf = t.empty((words, cols.numel()), dtype=t.float64, device=self.device)
         if cols.numel():
-            check(self.L.sipnet_batch_pack_members(self.h, C.c_void_p(cols.data_ptr()), cols.numel(),
-                                                   int(with_params), C.c_void_p(buf.data_ptr()),
+            check(self.L.sipnet_batch_pack_members(self.h, ptr(cols), cols.numel(), int(with_params), ptr(buf),
                                                    self._stream()), "pack_members")
         return buf
 
@@ -741,11 +704,10 @@ class Batch:
         t = self._torch
         src = src.to(device=self.device, dtype=t.int32).contiguous()
         assert src.numel() == self.ncol
-        nb = len(block_cols)
-        bc = (C.c_int64 * max(nb, 1))(*[int(x) for x in block_cols])
-        rp = C.c_void_p(recv.data_ptr()) if recv is not None and recv.numel() else None
-        check(self.L.sipnet_batch_resample(self.h, C.c_void_p(src.data_ptr()), rp, nb, bc,
-                                           int(with_params), self._stream()), "resample")
+        bc = c_array(C.c_int64, [int(x) for x in block_cols])
+        rp = ptr(recv) if recv is not None and recv.numel() else None
+        check(self.L.sipnet_batch_resample(self.h, ptr(src), rp, len(block_cols), bc, int(with_params), self._stream()),
+              "resample")
 
     def site_series(self, site):
         g = np.zeros(self.n_steps)

@@ -7,7 +7,11 @@ members, produced by the wavefront-shuffle reduction kernel -- from which every 
 forms the ensemble mean / variance.  On ROCm the "nccl" backend is RCCL over xGMI; the
 same code runs on "gloo" CPU tensors in the tests.
 """
+import ctypes as C
+
 import numpy as np
+
+from ._lib import check, lib, ptr
 
 
 def shard_members(n_total, world, rank):
@@ -47,15 +51,18 @@ def _gather0(x, world, group):
     return out.view((world,) + tuple(x.shape))
 
 
+def _gather0_or_alone(x, group):
+    """_gather0 over the group; a single process returns x[None]"""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return x.unsqueeze(0)
+    return _gather0(x, dist.get_world_size(group), group)
+
+
 def all_gather_stats(stats, group=None):
     """stats: tensor [..., 2] (sum, sum of squares) of this rank -> [world, ..., 2].
     One all_gather_into_tensor; a single process returns stats[None]."""
-    import torch
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return stats.unsqueeze(0)
-    world = dist.get_world_size(group)
-    return _gather0(stats, world, group)
+    return _gather0_or_alone(stats, group)
 
 
 def combine_stats(gathered, counts):
@@ -72,12 +79,7 @@ def all_gather_planes(planes, group=None):
     """Optional full-block gather: planes[3][T][ncol_local] -> [world][3][T][ncol_local].
     Message size per rank is 3*T*ncol*elem bytes -- see DESIGN.md for why the statistics
     block, not this, is the default exchange."""
-    import torch
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return planes.unsqueeze(0)
-    world = dist.get_world_size(group)
-    return _gather0(planes, world, group)
+    return _gather0_or_alone(planes, group)
 
 
 # ---- particle-filter analysis step (BASELINE config C5, SURVEY 8(e)) ---------------------------
@@ -86,9 +88,7 @@ def pf_systematic_ancestors(logw, u0, return_fixed=False, total_out=None):
     logw f64 CUDA tensor [n] -> int32 ancestors [n], non-decreasing, identical on every rank.
     With `total_out` (int64 CUDA tensor [1]) nothing is synchronised: the total integer weight
     is left there and the caller checks `total_out > 0` (a particle survived) later."""
-    import ctypes as C
     import torch
-    from ._lib import check, lib
     logw = logw.contiguous()
     assert logw.dtype == torch.float64 and logw.is_cuda
     anc = torch.empty(logw.numel(), dtype=torch.int32, device=logw.device)
@@ -96,14 +96,11 @@ def pf_systematic_ancestors(logw, u0, return_fixed=False, total_out=None):
     stream = C.c_void_p(torch.cuda.current_stream(logw.device).cuda_stream)
     if total_out is not None:
         assert total_out.dtype == torch.int64 and total_out.is_cuda
-        check(lib().sipnet_pf_systematic_ancestors_async(
-            C.c_void_p(logw.data_ptr()), logw.numel(), float(u0), C.c_void_p(anc.data_ptr()),
-            C.c_void_p(fixed.data_ptr()) if return_fixed else None,
-            C.c_void_p(total_out.data_ptr()), stream), "pf_systematic_ancestors")
+        check(lib().sipnet_pf_systematic_ancestors_async(ptr(logw), logw.numel(), float(u0), ptr(anc), ptr(fixed),
+                                                         ptr(total_out), stream), "pf_systematic_ancestors")
     else:
-        check(lib().sipnet_pf_systematic_ancestors(
-            C.c_void_p(logw.data_ptr()), logw.numel(), float(u0), C.c_void_p(anc.data_ptr()),
-            C.c_void_p(fixed.data_ptr()) if return_fixed else None, stream), "pf_systematic_ancestors")
+        check(lib().sipnet_pf_systematic_ancestors(ptr(logw), logw.numel(), float(u0), ptr(anc), ptr(fixed), stream),
+              "pf_systematic_ancestors")
     return (anc, fixed) if return_fixed else anc
 
 
@@ -117,16 +114,13 @@ def pf_exchange_plan(ancestors, n_local, world, rank):
     formulation below is the same plan for CPU tensors (the gloo tests) and its reference."""
     import torch
     if ancestors.is_cuda:
-        import ctypes as C
-        from ._lib import check, lib
         anc = ancestors.to(torch.int32).contiguous()
         send = torch.empty(world * n_local, dtype=torch.int32, device=anc.device)
         src = torch.empty(n_local, dtype=torch.int32, device=anc.device)
         sc, rc = (C.c_int64 * world)(), (C.c_int64 * world)()
         stream = C.c_void_p(torch.cuda.current_stream(anc.device).cuda_stream)
-        check(lib().sipnet_pf_exchange_plan(C.c_void_p(anc.data_ptr()), n_local, world, rank,
-                                            C.c_void_p(send.data_ptr()), C.c_void_p(src.data_ptr()),
-                                            sc, rc, stream), "pf_exchange_plan")
+        check(lib().sipnet_pf_exchange_plan(ptr(anc), n_local, world, rank, ptr(send), ptr(src), sc, rc, stream),
+              "pf_exchange_plan")
         cols, off = [], 0
         for d in range(world):
             cols.append(send[off:off + sc[d]])
@@ -165,6 +159,18 @@ def pf_exchange_plan_reference(ancestors, n_local, world, rank):
     return send_cols, src, recv_counts
 
 
+def _collectives(collectives, world):
+    """the `collectives` argument's default: only with more than one rank"""
+    return world > 1 if collectives is None else collectives
+
+
+def _ess_and_unique(logw, anc):
+    """the diagnostics of an analysis: the effective sample size of the weights, the number of distinct ancestors"""
+    import torch
+    w = torch.exp(logw - logw.max())
+    return {"ess": float(w.sum() ** 2 / (w * w).sum()), "unique_ancestors": int(torch.unique_consecutive(anc).numel())}
+
+
 def pf_resample(batch, ancestors, rank=0, world=1, group=None, with_params=False, collectives=None):
     """Move particle state so that global particle g becomes old global particle
     ancestors[g]: local gather for ancestors this rank already holds, ONE all-to-all
@@ -176,9 +182,7 @@ def pf_resample(batch, ancestors, rank=0, world=1, group=None, with_params=False
     import torch
     import torch.distributed as dist
     n = batch.ncol
-    if collectives is None:
-        collectives = world > 1
-    if not collectives:
+    if not _collectives(collectives, world):
         batch.resample(ancestors[:n].to(torch.int32), None, (), with_params)
         return {"sent": 0, "received": 0, "bytes_sent": 0}
     send_cols, src, recv_counts = pf_exchange_plan(ancestors, n, world, rank)
@@ -206,10 +210,7 @@ def pf_analysis(batch, plane, obs, sigma, u0, rank=0, world=1, group=None, with_
     all-gather of log-weights (n_total x 8 B) -> systematic resampling (redundant, identical
     on every rank) -> pf_resample.  Returns (ancestors, info).  `total_out` (int64 CUDA tensor
     [1]): run without a host round trip and leave the total weight there for a later check."""
-    import torch
-    import torch.distributed as dist
-    if collectives is None:
-        collectives = world > 1
+    collectives = _collectives(collectives, world)
     if not collectives and hasattr(batch, "pf_analysis_local"):
         # every particle is here: the three steps in one library call (without `diagnostics` the ancestors
         # returned are the batch's own buffer, overwritten by its next analysis)
@@ -223,11 +224,8 @@ def pf_analysis(batch, plane, obs, sigma, u0, rank=0, world=1, group=None, with_
             logw = _gather0(logw, world, group).reshape(-1)
         anc = pf_systematic_ancestors(logw, u0, total_out=total_out)
         info = pf_resample(batch, anc, rank, world, group, with_params, collectives)
-    if not diagnostics:
-        return anc, info
-    w = torch.exp(logw - logw.max())
-    info["ess"] = float(w.sum() ** 2 / (w * w).sum())
-    info["unique_ancestors"] = int(torch.unique_consecutive(anc).numel())
+    if diagnostics:
+        info.update(_ess_and_unique(logw, anc))
     return anc, info
 
 
@@ -261,10 +259,8 @@ class DirectComm:
     ranks and carries the 128-byte id from rank 0 to the others; the librccl is the one the process already holds (PyTorch's)."""
 
     def __init__(self, rank, world, device, group=None):
-        import ctypes as C
-        import torch.distributed as dist
-        from ._lib import lib, check
         import torch
+        import torch.distributed as dist
         self.L = lib()
         # every rank asks for an id (only rank 0's is used): a rank whose RCCL is unusable finds out HERE, and all ranks agree on
         # that before any of them enters the collective ncclCommInitRank -- which would otherwise wait for the missing one
@@ -287,11 +283,9 @@ class DirectComm:
 
     def all_gather(self, mine, gathered, stream):
         """gathered [world][L] (device, contiguous) <- every rank's `mine` [L]; `mine` may be gathered[rank] (in place)"""
-        import ctypes as C
-        from ._lib import check
         assert gathered.is_contiguous() and mine.is_contiguous() and gathered.shape[0] == self.world
-        check(self.L.sipnet_comm_all_gather(self.h, C.c_void_p(mine.data_ptr()), C.c_void_p(gathered.data_ptr()),
-                                            mine.numel() * mine.element_size(), stream), "comm_all_gather")
+        check(self.L.sipnet_comm_all_gather(self.h, ptr(mine), ptr(gathered), mine.numel() * mine.element_size(), stream),
+              "comm_all_gather")
 
     def close(self):
         if getattr(self, "h", None):
@@ -305,17 +299,38 @@ class DirectComm:
             pass
 
 
+def _gathered_buffer(batch, name, shape):
+    """the float64 device tensor of `shape` = [world, ...] that the batch keeps as attribute `name` for the all-gather of a
+    cycle: made on first use, and again when the shape changes"""
+    import torch
+    buf = getattr(batch, name, None)
+    if buf is None or buf.shape != shape:
+        buf = torch.empty(shape, dtype=torch.float64, device=batch.device)
+        setattr(batch, name, buf)
+    return buf
+
+
+def _all_gather_in_place(mine, gathered, batch, group, comm):
+    """every rank's block into gathered [world][...], of which this rank has written its own slice `mine`: through comm (a
+    DirectComm, on the batch's stream), else the process group -- gloo by host copies, RCCL in place"""
+    import torch
+    import torch.distributed as dist
+    if comm is not None:
+        comm.all_gather(mine, gathered, batch._stream())
+    elif _host_staged(mine, group):
+        out = torch.empty(gathered.shape, dtype=gathered.dtype)
+        dist.all_gather_into_tensor(out.view(-1), mine.cpu().view(-1), group=group)
+        gathered.copy_(out)
+    else:   # in place: rank r's input is its own slice of the output
+        dist.all_gather_into_tensor(gathered.view(-1), mine.view(-1), group=group)
+
+
 def pf_arm_peers(batch, obs, sigma, rank=0, world=1, pretend_world=0):
     """before the forecast's run() of a connected filter: that launch then leaves this rank's log-weights in its slice of
     the all-gather's buffer (sipnet_batch_pf_arm), and pf_analysis_peers only adds the block maxima"""
-    import torch
     if pretend_world > 1:
         rank, world = pretend_world - 1, pretend_world
-    L = batch.pf_block_len()
-    gathered = getattr(batch, "_pf_gathered", None)
-    if gathered is None or gathered.shape != (world, L):
-        gathered = batch._pf_gathered = torch.empty((world, L), dtype=torch.float64, device=batch.device)
-    batch.pf_arm_block(obs, sigma, gathered[rank])
+    batch.pf_arm_block(obs, sigma, _gathered_buffer(batch, "_pf_gathered", (world, batch.pf_block_len()))[rank])
 
 
 def pf_analysis_peers(batch, plane, obs, sigma, u0, rank=0, world=1, group=None, total_out=None,
@@ -325,18 +340,14 @@ def pf_analysis_peers(batch, plane, obs, sigma, u0, rank=0, world=1, group=None,
     ancestor where it lives.  No host synchronisation, no second collective.  Returns (ancestor slots
     int32 [ncol] -- rank * nmax + particle --, gathered blocks).  comm: a DirectComm -- the all-gather then goes
     through the engine's own RCCL communicator on the batch's stream instead of torch.distributed's process group."""
-    import torch
     import torch.distributed as dist
-    if collectives is None:
-        collectives = world > 1
+    collectives = _collectives(collectives, world)
     pretend = pretend_world > 1
     if pretend:
         rank, world = pretend_world - 1, pretend_world
     L = batch.pf_block_len()
     if gathered is None:
-        gathered = getattr(batch, "_pf_gathered", None)
-        if gathered is None or gathered.shape != (world, L):
-            gathered = batch._pf_gathered = torch.empty((world, L), dtype=torch.float64, device=batch.device)
+        gathered = _gathered_buffer(batch, "_pf_gathered", (world, L))
     mine = gathered[rank]
     batch.pf_local_weights(plane, obs, sigma, mine)
     if pretend:
@@ -353,27 +364,18 @@ def pf_analysis_peers(batch, plane, obs, sigma, u0, rank=0, world=1, group=None,
             dist.all_gather_into_tensor(mine, mine, group=group)
         gathered[:rank].copy_(mine.expand(rank, L))
     elif collectives:
-        if comm is not None:
-            comm.all_gather(mine, gathered, batch._stream())
-        elif _host_staged(mine, group):
-            out = torch.empty((world, L), dtype=torch.float64)
-            dist.all_gather_into_tensor(out.view(-1), mine.cpu(), group=group)
-            gathered.copy_(out)
-        else:   # in place: rank r's input is its own slice of the output
-            dist.all_gather_into_tensor(gathered.view(-1), mine, group=group)
+        _all_gather_in_place(mine, gathered, batch, group, comm)
     anc = batch.pf_resample_peers(gathered, u0, ancestors, total_out)
     if not diagnostics:
         return anc, gathered
     nmax = (L * 256) // 257                      # L = nmax + ceil(nmax / 256)
     while nmax + (nmax + 255) // 256 < L:
         nmax += 1
-    logw = gathered[:, :nmax].reshape(-1)
-    w = torch.exp(logw - logw.max())
     crossed = int(((anc // nmax) != rank).sum())
     pinfo = batch.pf_info()
     # a crossing particle: state + ring + its 4-byte column in the replicated parameter bank -- or its parameter rows
     per = batch.L.sipnet_batch_member_words(batch.h, 0) * 8 + 4 if pinfo["params_by_index"] else batch.L.sipnet_batch_member_words(batch.h, 1) * 8
-    info = {"ess": float(w.sum() ** 2 / (w * w).sum()), "unique_ancestors": int(torch.unique_consecutive(anc).numel()),
+    info = {**_ess_and_unique(gathered[:, :nmax].reshape(-1), anc),
             "received": crossed, "sent": 0, "bytes_received": crossed * per, "bytes_per_crossing_particle": per,
             "exchange": "peer reads", "params_by_index": pinfo["params_by_index"], "analysis_one_launch": pinfo["fused"],
             "analysis_grid": pinfo["grid"], "analysis_slots": pinfo["n_slots"]}
@@ -388,23 +390,12 @@ def enkf_analysis_sharded(batch, obs, sd, operators, analysed, planes=None, infl
     inflation must be the same on every rank.  collectives: a DirectComm -- the all-gather then goes through the engine's own
     RCCL communicator on the batch's stream -- else torch.distributed's process group; with world 1 and no group there is no
     collective.  Returns the gathered blocks."""
-    import torch
-    import torch.distributed as dist
     ops = list(operators)
-    W = batch.enkf_moment_words(ops, analysed)
-    gathered = getattr(batch, "_enkf_gathered", None)
-    if gathered is None or gathered.shape != (world, batch.n_sites, W):
-        gathered = batch._enkf_gathered = torch.empty((world, batch.n_sites, W), dtype=torch.float64, device=batch.device)
+    gathered = _gathered_buffer(batch, "_enkf_gathered", (world, batch.n_sites, batch.enkf_moment_words(ops, analysed)))
     mine = gathered[rank]
     batch.enkf_shard_moments(ops, analysed, planes=planes, out=mine)
-    if isinstance(collectives, DirectComm):
-        collectives.all_gather(mine.view(-1), gathered.view(world, -1), batch._stream())
-    elif world > 1 or group is not None:
-        if _host_staged(mine, group):
-            out = torch.empty((world, batch.n_sites, W), dtype=torch.float64)
-            dist.all_gather_into_tensor(out.view(-1), mine.cpu().view(-1), group=group)
-            gathered.copy_(out)
-        else:   # in place: rank r's input is its own slice of the output
-            dist.all_gather_into_tensor(gathered.view(-1), mine.view(-1), group=group)
+    comm = collectives if isinstance(collectives, DirectComm) else None
+    if comm is not None or world > 1 or group is not None:
+        _all_gather_in_place(mine, gathered, batch, group, comm)
     batch.enkf_analysis_sharded(gathered, obs, sd, ops, analysed, planes=planes, inflation=inflation, info_out=info_out)
     return gathered

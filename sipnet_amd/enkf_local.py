@@ -26,6 +26,7 @@ def _csr(nbr_ptr, nbr, rho):
 
 
 def _ptr(a):
+    """the void* argument for a numpy array, NULL for an empty one (_lib.ptr keeps an empty array's address)"""
     return C.c_void_p(a.ctypes.data) if a.size else None
 
 
@@ -36,9 +37,8 @@ def enkf_local_schedule(nbr_ptr, nbr, rho, n_obs):
     n_sites = ptr.size - 1
     level = np.zeros((max(n_sites, 0), max(int(n_obs), 0)), dtype=np.int32)
     n_levels = C.c_int32(0)
-    check(lib().sipnet_enkf_local_schedule(n_sites, int(n_obs), C.c_void_p(ptr.ctypes.data), _ptr(idx), _ptr(w),
-                                           C.c_void_p(level.ctypes.data) if level.size else None, C.byref(n_levels)),
-          "enkf_local_schedule")
+    check(lib().sipnet_enkf_local_schedule(n_sites, int(n_obs), _ptr(ptr), _ptr(idx), _ptr(w), _ptr(level),
+                                           C.byref(n_levels)), "enkf_local_schedule")
     return level, int(n_levels.value)
 
 
@@ -50,8 +50,8 @@ def enkf_local_rows(nbr_ptr, nbr, n_obs):
     n_sites = ptr.size - 1
     rows = np.zeros(max(n_sites, 0), dtype=np.int32)
     most = C.c_int32(0)
-    check(lib().sipnet_enkf_local_rows(n_sites, int(n_obs), C.c_void_p(ptr.ctypes.data), _ptr(idx),
-                                       C.c_void_p(rows.ctypes.data) if rows.size else None, C.byref(most)), "enkf_local_rows")
+    check(lib().sipnet_enkf_local_rows(n_sites, int(n_obs), _ptr(ptr), _ptr(idx), _ptr(rows), C.byref(most)),
+          "enkf_local_rows")
     return rows, int(most.value)
 
 
@@ -111,8 +111,8 @@ class EnkfLocalization:
         self.L = batch.L
         self.n_obs = int(n_obs)
         h = C.c_void_p()
-        check(self.L.sipnet_batch_enkf_local_create(batch.h, self.n_obs, C.c_void_p(ptr.ctypes.data), _ptr(idx), _ptr(w),
-                                                    C.byref(h)), "enkf_localization")
+        check(self.L.sipnet_batch_enkf_local_create(batch.h, self.n_obs, _ptr(ptr), _ptr(idx), _ptr(w), C.byref(h)),
+              "enkf_localization")
         self.h = h
         self.max_rows = enkf_local_rows(ptr, idx, self.n_obs)[1]
 

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ALL_SITES, F64, NPARAMS, SHARD_MEMBERS, SHARD_SITES, Event, check, lib
+from ._lib import ALL_SITES, F64, NPARAMS, NSTATE, RING_SLOTS, SHARD_MEMBERS, Event, PfInfo, c_array, check, lib
 
 
 class Node:
@@ -66,9 +66,7 @@ class Node:
                                              clim.day.ctypes.data), "node_set_climate")
 
     def set_events(self, site, events):
-        n = len(events)
-        arr = (Event * max(n, 1))(*events)
-        check(self.L.sipnet_node_set_events(self.h, site, n, arr), "node_set_events")
+        check(self.L.sipnet_node_set_events(self.h, site, len(events), c_array(Event, events)), "node_set_events")
 
     def set_params(self, site, raw, first_member=0):
         """site=None: the same members at every site (SIPNET_ALL_SITES)"""
@@ -121,10 +119,9 @@ class Node:
         out = np.empty((3, self.n_run, self.ld), dtype=flat.dtype)
         first0 = None
         for j in range(nseg):
-            first, length = C.c_int32(0), C.c_int32(0)
-            self.L.sipnet_node_gathered_segment(self.h, k, j, C.byref(first), C.byref(length))
-            first0 = first.value if first0 is None else first0
-            a, n = first.value - first0, length.value
+            _, first, n = self._segment(k, j)
+            first0 = first if first0 is None else first0
+            a = first - first0
             out[:, a:a + n] = flat[3 * a * self.ld:3 * (a + n) * self.ld].reshape(3, n, self.ld)
         return out
 
@@ -142,11 +139,22 @@ class Node:
 
     def gathered_segment(self, k, j):
         """-> (first record, segment j of every shard as device k holds it: [n][3][len][ld]) on the host (after sync)"""
-        first, length = C.c_int32(0), C.c_int32(0)
-        ptr = self.L.sipnet_node_gathered_segment(self.h, k, j, C.byref(first), C.byref(length))
+        ptr, first, length = self._segment(k, j)
         if not ptr:
             raise ValueError("no such segment")
-        return first.value, self._to_host(ptr, (self.n, 3, length.value, self.ld), self._elem())
+        return first, self._to_host(ptr, (self.n, 3, length, self.ld), self._elem())
+
+    def _segment(self, k, j):
+        """sipnet_node_gathered_segment -> (device pointer or None, first record, records)"""
+        first, length = C.c_int32(0), C.c_int32(0)
+        ptr = self.L.sipnet_node_gathered_segment(self.h, k, j, C.byref(first), C.byref(length))
+        return ptr, first.value, length.value
+
+    def _scatter(self, out, rows, q, block):
+        """shard q's block [3][len(rows)][>= its sites x members, site-major] into out[3][rows][n_sites][n_members]"""
+        m0, mc = self.member_range(q)
+        s0, sc = self.site_range(q)
+        out[:, rows, s0:s0 + sc, m0:m0 + mc] = block[:, :, :sc * mc].reshape(block.shape[:2] + (sc, mc))
 
     def gathered_member_planes(self, k):
         """what device k holds after run_gathering, as [3][n_run][n_sites][n_members] on the host"""
@@ -156,9 +164,7 @@ class Node:
         for j in range(self.L.sipnet_node_n_segments(self.h)):
             _, g = self.gathered_segment(k, j)
             for q in range(self.n):
-                m0, mc = self.member_range(q)
-                s0, sc = self.site_range(q)
-                out[:, t:t + g.shape[2], s0:s0 + sc, m0:m0 + mc] = g[q][:, :, :sc * mc].reshape(3, g.shape[2], sc, mc)
+                self._scatter(out, slice(t, t + g.shape[2]), q, g[q])
             t += g.shape[2]
         return out
 
@@ -183,9 +189,7 @@ class Node:
             g = self._to_host(ptr, (self.n, 3, rows.value, self.ld), np.float32 if eb.value == 4 else np.float64)
             out = np.zeros((3, rows.value, self.n_sites, self.n_members), dtype=g.dtype)
             for q in range(self.n):
-                m0, mc = self.member_range(q)
-                s0, sc = self.site_range(q)
-                out[:, :, s0:s0 + sc, m0:m0 + mc] = g[q][:, :, :sc * mc].reshape(3, rows.value, sc, mc)
+                self._scatter(out, slice(None), q, g[q])
             parts.append(out)
         return np.concatenate(parts, axis=1)
 
@@ -198,30 +202,21 @@ class Node:
         self.sync()
         out = np.zeros((3, self.n_run, self.n_sites, self.n_members), dtype=self._elem())
         for k in range(self.n):
-            p = self.planes(k)
-            m0, mc = self.member_range(k)
-            s0, sc = self.site_range(k)
-            out[:, :, s0:s0 + sc, m0:m0 + mc] = p[:, :, :sc * mc].reshape(3, self.n_run, sc, mc)
+            self._scatter(out, slice(None), k, self.planes(k))
         return out
 
     # -- per-shard state (through the shard's batch) ------------------------------------
     def shard_state(self, k):
-        from ._lib import NSTATE
-        m0, mc = self.member_range(k)
-        s0, sc = self.site_range(k)
-        st = np.zeros((sc * mc, NSTATE))
-        check(self.L.sipnet_batch_get_state(self.L.sipnet_node_batch(self.h, k), st.ctypes.data,
-                                            self.L.sipnet_node_stream(self.h, k)), "get_state")
-        return st
+        return self._shard_rows(k, NSTATE, self.L.sipnet_batch_get_state, "get_state")
 
     def shard_rings(self, k):
-        from ._lib import RING_SLOTS
-        m0, mc = self.member_range(k)
-        s0, sc = self.site_range(k)
-        r = np.zeros((sc * mc, RING_SLOTS))
-        check(self.L.sipnet_batch_get_rings(self.L.sipnet_node_batch(self.h, k), r.ctypes.data,
-                                            self.L.sipnet_node_stream(self.h, k)), "get_rings")
-        return r
+        return self._shard_rows(k, RING_SLOTS, self.L.sipnet_batch_get_rings, "get_rings")
+
+    def _shard_rows(self, k, width, get, where):
+        """[shard k's columns][width] doubles, read from the shard's batch on the shard's stream"""
+        out = np.zeros((self.site_range(k)[1] * self.member_range(k)[1], width))
+        check(get(self.L.sipnet_node_batch(self.h, k), out.ctypes.data, self.L.sipnet_node_stream(self.h, k)), where)
+        return out
 
     # -- particle filter ----------------------------------------------------------------
     def pf_connect(self, with_params=True):
@@ -241,11 +236,10 @@ class Node:
 
     def pf_info(self, k):
         """sipnet_batch_pf_info of shard k's batch"""
-        from ._lib import PfInfo
         d = PfInfo()
         check(self.L.sipnet_batch_pf_info(self.L.sipnet_node_batch(self.h, k), C.byref(d), self.L.sipnet_node_stream(self.h, k)),
               "pf_info")
-        return {f: getattr(d, f) for f, _ in PfInfo._fields_}
+        return d.as_dict()
 
     def pf_ancestors(self, k):
         return self._to_host(self.L.sipnet_node_pf_ancestors(self.h, k), (self.member_range(k)[1],), np.int32)

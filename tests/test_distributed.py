@@ -25,6 +25,11 @@ def test_shard_members_covers_everything():
         assert max(sizes) - min(sizes) <= 1
 
 
+def test_shard_members_of_ten_over_three_ranks():
+    import sipnet_amd.dist
+    assert [sipnet_amd.dist.shard_members(10, 3, r) for r in range(3)] == [(0, 4), (4, 7), (7, 10)]
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
