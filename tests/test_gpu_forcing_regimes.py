@@ -15,37 +15,16 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 import sipnet_amd as sa
 from sipnet_amd.config import param_index as pi
 from tests import forcing_regimes as fr
 from tests import helpers
+from tests.regime_gpu_common import COOP, FLAG_SETS, batch, family_ok, judge, outputs, same
 
 pytestmark = pytest.mark.gpu
 DATA = os.path.join(helpers.REPO, "sipnet_amd", "data")
 REGIMES = list(fr.FILE_REGIMES) + ["tiny"]
-NCYCLE_FLAGS = dict(litterPool=1, anaerobic=1, nitrogenCycle=1)
-RUSSELL_3 = dict(growthResp=1, leafWater=1, litterPool=1, waterHResp=0)
-FLAG_SETS = {"default": {}, "ncycle": NCYCLE_FLAGS, "russell_3": RUSSELL_3}
-COOP = {"coop_lds": sa.KERNEL_COOP_LDS, "coop_hbm": sa.KERNEL_COOP_HBM, "coop_pair": sa.KERNEL_COOP_PAIR, "coop_quad": sa.KERNEL_COOP_QUAD}
-
-
-def family_ok(family, flagset, name):
-    """did the forced kernel run?  (last_launch()'s name: 'stepCoopKernel<double, true, true, false>' ...)"""
-    head, args = name.split("<", 1)
-    args = [a.strip(" >") for a in args.split(",")]
-    x = {"default": "", "russell_3": "X", "ncycle": "N"}[flagset]
-    if family == "strict":
-        return head == "stepKernel"
-    if family == "one_wave":
-        return head == "stepFastKernel" and (flagset != "default" or args[2] == "0")      # (0: the flags compiled in)
-    if family in ("coop_lds", "coop_hbm"):
-        return head == "stepCoop" + x + "Kernel" and args[2] == ("true" if family == "coop_lds" else "false")
-    return head == {"coop_pair": "stepCoop" + x + "PairKernel", "coop_quad": "stepCoop" + x + "QuadKernel",
-                    "coop_ncycle": "stepCoopNKernel", "coop_ncycle_pair": "stepCoopNPairKernel"}[family]
-
-
 class Reference:
     """the oracle's planes, final records, status and counters per (regime, flag set), computed once"""
 
@@ -85,40 +64,6 @@ class Reference:
 @pytest.fixture(scope="module")
 def ref(oracle):
     return Reference(oracle)
-
-
-def batch(flags, clims, members, prec, kernel, options=0, strict=False, diagnostics=False):
-    b = sa.Batch(flags, len(clims), members.shape[0], prec, fast_math=(not strict) if prec == sa.F64 else None,
-                 kernel=kernel, kernel_options=options)
-    for s, c in enumerate(clims):
-        b.set_climate(s, c)
-    b.set_params(None, members)
-    if diagnostics:
-        b.enable_diagnostics()
-    b.setup()
-    return b
-
-
-def judge(tag, prec, got, state, status, want, final, st):
-    """the fuzzer's criteria (tools/fuzz_gpu.py), with the achieved figures printed first"""
-    ok = st == 0
-    assert np.array_equal(np.asarray(status) != 0, ~ok) and (np.asarray(status)[ok] == 0).all(), (tag, status, st)
-    got, want = got[:, :, ok], want[:, :, ok]
-    scale = np.maximum(np.abs(want).max(axis=(1, 2), keepdims=True), 1e-3)
-    rel = np.abs(got - want) / scale
-    pfloor = 1.0 if prec == sa.F32_MIXED else 1e-2
-    perr = (np.abs(state[ok, :13] - final[ok, 14:27]) / np.maximum(np.abs(final[ok, 14:27]), pfloor)).max()
-    if prec == sa.F64:
-        print(f"{tag}: planes {np.nanmax(rel):.2e} of the plane maximum, pools {perr:.2e}")
-        assert np.isfinite(got).all(), tag
-        assert rel.max() < 1e-9 and perr < 1e-8, tag
-    else:
-        share = float((rel > 1e-4).mean())
-        sums = (np.abs(got.sum(1) - want.sum(1)) / (np.abs(want).sum(1) + 1.0)).max()
-        print(f"{tag}: fp32 max {np.nanmax(rel):.2e}, share off by > 1e-4 of the plane maximum {share:.2e}, time sums {sums:.2e}, "
-              f"pools {perr:.2e}")
-        assert np.isfinite(got).all() and np.isfinite(state[ok, :13]).all(), tag
-        assert share < 2e-3 and sums < 2e-3 and perr < 5e-3, tag
 
 
 def run_case(ref, regime, flagset, family, prec):
@@ -178,27 +123,6 @@ def test_optional_physics_and_nitrogen_kernels(regime, flagset, family, prec, re
 def test_optional_physics_four_chunk_layout(regime, ref):
     """stepCoopXQuadKernel: the fp32-mixed build only (the engine refuses the fp64 one)"""
     run_case(ref, regime, "russell_3", "coop_quad", sa.F32_MIXED)
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8)
-
-
-def outputs(b, cuts=None):
-    T = b.n_steps
-    planes, _ = b.alloc_outputs(T)
-    cuts = [0, T] if cuts is None else cuts
-    for a, z in zip(cuts[:-1], cuts[1:]):
-        b.run(a, z - a, planes=planes[:, a:z])
-    out = (planes, b.get_state(), b.get_rings(), b.last_launch())
-    b.close()
-    return out
-
-
-def same(x, y, what):
-    assert torch.equal(bits(x[0]), bits(y[0])), what + ": planes"
-    assert np.array_equal(x[1], y[1], equal_nan=True), what + ": state"
-    assert np.array_equal(x[2], y[2], equal_nan=True), what + ": rings"
 
 
 @pytest.mark.parametrize("prec", [sa.F64, sa.F32_MIXED], ids=["f64", "f32"])
