@@ -558,6 +558,75 @@ int sipnet_batch_pf_analysis_sites(sipnet_batch *b, const void *d_plane, int32_t
                                    int32_t with_params, double *d_logw, int32_t *d_ancestors,
                                    int64_t *d_fixed_weights, int64_t *d_site_total, void *hip_stream);
 
+/* ---- series likelihood weights: every member's log-likelihood of a window ---------------------------------------
+ * A TERM is one observed series: d_series (DEVICE, [rows * sum_steps][ld], ld >= ncol; doubles, or floats with the call's
+ * elem_is_f32: a plane of sipnet_batch_run, an array of sipnet_batch_run_sums, a smoothed series) against d_obs and d_sd
+ * (DEVICE, [n_sites][rows]; obs NaN = gap; sd is the Gaussian sigma or the Laplace scale b and is read only where obs is
+ * not NaN).  Observation row r is compared with h = scale * (the sum of series rows r sum_steps .. (r + 1) sum_steps - 1,
+ * ascending, from 0.0) of the member's column.  Row term of member c of site s at a used row, y = obs[s][r], d = h - y:
+ *   GAUSS    -0.5 (d / sd)^2, with normalise != 0 also - (log sd + 0.5 log 2 pi);
+ *   LAPLACE  -|d| / b,        with normalise != 0 also - log(2 b).
+ * (The device multiplies by 1 / sd and fuses the constant in: a row term is within a few ulp of these expressions.)
+ * Order, part of the contract -- the bits do not depend on the path or on how the work was spread: per term the rows are
+ * cut into tiles of SIPNET_LOGLIK_TILE_ROWS; a tile's used rows are added in ascending order from +0.0; a term's tiles in
+ * ascending order from +0.0; the terms in ascending order from +0.0; last d_add[c] when d_add is given (DEVICE [ncol],
+ * may be d_loglik itself: weights accumulated over windows without a resampling in between).
+ * Outputs (DEVICE): d_loglik [ncol]; d_parts [n_terms][ncol] (may be NULL) each term's own sum; d_used [n_sites][n_terms]
+ * int32 (may be NULL) the rows used; d_site_info [n_sites][2] int32 (may be NULL) = {code, rows used over all terms}.
+ * A member whose status is non-zero (sipnet_batch_pf_log_weights' rule) gets -inf in d_loglik and d_parts, whatever d_add
+ * holds.  Site codes: 1 evaluated; -1 no observation in any term (live members get 0 + add); -2 bad input -- a non-NaN
+ * non-finite obs, or at a row whose obs is not NaN an sd that is not finite and > 0: every column of the site gets NaN in
+ * d_loglik and d_parts (sipnet_batch_pf_resample_sites weighs that as nothing); the rows used count the good rows.
+ * d_site_info given: nothing is synchronised.  NULL: obs and sd are read back and checked first (hip_stream is
+ * synchronised); a -2 site gives SIPNET_ERR_BAD_ARGUMENT naming the site and the term, and nothing is written.
+ * Paths, the same bits on both: 1 -- a workgroup (256 neighbouring columns of one site) walks all tiles and writes the
+ * result; 2 -- a grid over (tile, column chunk) writes the tiles' sums to scratch and a second launch adds them in tile
+ * order.  path = 0 chooses 2 when the columns alone leave the device short of workgroups; 1 / 2 force one.  No atomic, no
+ * grid barrier, no spin.
+ * SIPNET_ERR_BAD_ARGUMENT before any launch (sipnet_last_error says why): a NULL batch, terms or d_loglik, or a NULL
+ * series, obs or sd of a term; n_terms outside 1..SIPNET_LOGLIK_MAX_TERMS; a kind that is not one of the two; rows < 1,
+ * sum_steps < 1, ld < ncol; a scale that is not finite; path outside 0..2, or 2 with more than INT32_MAX workgroups;
+ * ncol > 4 194 304; a batch that was not set up (the members' status is read).  The batch is not changed; pending
+ * set_params rows are NOT flushed (no parameter is read); a connected batch is fine. */
+#define SIPNET_LOGLIK_TILE_ROWS 256
+#define SIPNET_LOGLIK_MAX_TERMS 8
+enum sipnet_loglik_kind { SIPNET_LOGLIK_GAUSS = 0, SIPNET_LOGLIK_LAPLACE = 1 };
+typedef struct sipnet_loglik_term {
+  const void *d_series;   /* DEVICE [rows * sum_steps][ld] */
+  const double *d_obs;    /* DEVICE [n_sites][rows]; NaN = gap */
+  const double *d_sd;     /* DEVICE [n_sites][rows] */
+  int32_t rows, sum_steps;
+  int32_t kind;           /* enum sipnet_loglik_kind */
+  int32_t reserved;
+  double scale;
+} sipnet_loglik_term;
+int sipnet_batch_series_loglik(sipnet_batch *b, int32_t n_terms, const sipnet_loglik_term *terms /* HOST */,
+                               int32_t elem_is_f32, int64_t ld, int32_t normalise, int32_t path,
+                               const double *d_add, double *d_loglik, double *d_parts, int32_t *d_used,
+                               int32_t *d_site_info, void *hip_stream);
+/* Everything of sipnet_batch_pf_analysis_sites after its log-weights, from log-weights the caller GIVES (d_logw, DEVICE
+ * [ncol]: sipnet_batch_series_loglik's, or anything else), by the same rules.  Site s: w = the fixed-point weight of
+ * beta[s] * logw under the site's maximum of beta[s] * logw (d_beta DEVICE [n_sites]; NULL: 1, and the product is not
+ * formed; beta in (0, 1] tempers a likelihood that is too sharp); a NaN or -inf log-weight weighs 0.  Prefix sum,
+ * systematic draw with d_u0 [n_sites], ancestors inside the site's range: as there -- from sipnet_batch_pf_analysis_sites'
+ * d_logw and the same u0 the ancestors, integer weights and totals are that call's, bit for bit.
+ * d_ess [n_sites] (may be NULL) = S^2 / sum w^2 of the integer weights, 0 when S = 0; sum w^2 is formed exactly, so the
+ * value does not depend on the path.  d_ess_min [n_sites] (may be NULL): a site with S > 0 and ESS >= ess_min[s] KEEPS
+ * its particles -- identity ancestors, site total -3, its d_logw stays; a site that resamples gets the log-weights of all
+ * its columns set to 0.  With d_ess_min NULL every site with S > 0 resamples and d_logw is not written.  (With d_add of
+ * sipnet_batch_series_loglik: a complete sequential-importance-sampling cycle on the device, no host decision.)
+ * site_total[s]: S > 0 resampled; 0 no particle of the site weighs anything, identity ancestors; -2 u0 outside [0, 1), a
+ * beta not finite or <= 0, an ess_min that is NaN, or a +inf log-weight in the site: identity ancestors and the total,
+ * nothing else of the site is written; -3 kept.  Then sipnet_batch_resample's gather with the ancestors (with_params: as
+ * there).  d_site_total given: nothing is synchronised.  NULL: the totals are read back before the gather; a site at -2
+ * gives SIPNET_ERR_BAD_ARGUMENT, else a site at 0 SIPNET_ERR_BAD_PARAMETER, naming the first such site, and nothing is
+ * resampled.  SIPNET_ERR_BAD_ARGUMENT before any launch: a NULL batch, d_logw, d_u0 or d_ancestors; ncol > 4 194 304; a
+ * batch connected by sipnet_batch_pf_connect.  Both paths of the many-site analysis (sipnet_batch_pf_info's fused says
+ * which ran; SIPNET_KOPT_PF_MULTI_LAUNCH forces the three launches) give the same bits. */
+int sipnet_batch_pf_resample_sites(sipnet_batch *b, double *d_logw, const double *d_u0, const double *d_beta,
+                                   const double *d_ess_min, int32_t with_params, int32_t *d_ancestors,
+                                   int64_t *d_fixed_weights, int64_t *d_site_total, double *d_ess, void *hip_stream);
+
 /* ---- ensemble Kalman filter analysis of the member pools, a filter per site ------------------------------------
  * Observation operators (h of one member, from its forecast state, planes and converted parameters):
  *   POOLS: h = scale * (sum of the pools in pool_mask) / (param >= 0 ? prm[param] : 1)

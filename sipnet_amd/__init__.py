@@ -10,13 +10,14 @@ from ._lib import (KERNEL_AUTO, KERNEL_COOP_HBM, KERNEL_COOP_LDS, KERNEL_COOP_PA
                    KOPT_FULL_STATE, KOPT_NO_REGULAR_TILES, KOPT_ONE_WAVE_PER_SIMD, KOPT_RUNTIME_FLAGS,
                    KOPT_STATS_IN_KERNEL, KOPT_BOUNDED_WAITS, KOPT_WAIT_SELFTEST, KOPT_HOST_PLAN, KOPT_DEVICE_PLAN,
                    KOPT_PF_MULTI_LAUNCH, KOPT_PF_MOVE_PARAMS, PF_VOID_TOTAL)
+from ._lib import (LOGLIK_GAUSS, LOGLIK_LAPLACE, LOGLIK_MAX_TERMS, LOGLIK_TILE_ROWS)
 from ._lib import (ENKF_MAX_PARAMS, ENKF_MAX_SERIES, F32_MIXED, F64, NCLIM, NFLAGS, NPARAMS, NREC, NSTATE, RING_SLOTS,
                    Event, Restart, SipnetError, lib)
 from .config import (DEFAULT_FLAGS, FLAG_NAMES, PARAM_NAMES, POOLS, enkf_param, enkf_plane, enkf_pools, flags_from, read_config)
 from .io import (ClimTable, format_out_header, format_out_row, read_clim, read_events,
                  read_params, read_restart, check_restart, write_debug_logs, write_events_out, write_out,
                  write_restart)
-from .batch import Batch, PlaneQuantiles, debug_live_bytes, quantile_lds_members, quantile_positions
+from .batch import Batch, PlaneQuantiles, debug_live_bytes, loglik_term, quantile_lds_members, quantile_positions
 from .enkf_local import ENKF_BLOCK_MAX_ROWS, EnkfLocalization, enkf_local_rows, enkf_local_schedule, gaspari_cohn
 
 __all__ = [
@@ -27,4 +28,5 @@ __all__ = [
     "KERNEL_AUTO", "KERNEL_ONE_WAVE", "KERNEL_COOP_LDS", "KERNEL_COOP_HBM", "KERNEL_COOP_PAIR", "KERNEL_COOP_QUAD", "KERNEL_COOP_NCYCLE", "KERNEL_COOP_NCYCLE_PAIR", "KERNEL_STRICT",
     "KOPT_ONE_WAVE_PER_SIMD", "KOPT_RUNTIME_FLAGS", "KOPT_FULL_STATE", "KOPT_NO_REGULAR_TILES", "KOPT_STATS_IN_KERNEL", "KOPT_BOUNDED_WAITS", "KOPT_WAIT_SELFTEST", "KOPT_HOST_PLAN", "KOPT_DEVICE_PLAN", "KOPT_PF_MULTI_LAUNCH", "KOPT_PF_MOVE_PARAMS", "PF_VOID_TOTAL",
     "NPARAMS", "NFLAGS", "NCLIM", "NREC", "NSTATE", "RING_SLOTS",
+    "loglik_term", "LOGLIK_GAUSS", "LOGLIK_LAPLACE", "LOGLIK_MAX_TERMS", "LOGLIK_TILE_ROWS",
 ]

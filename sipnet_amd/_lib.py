@@ -61,6 +61,17 @@ class EnkfParam(C.Structure):
 
 ENKF_MAX_SERIES = 8   # SIPNET_ENKF_MAX_SERIES
 
+LOGLIK_GAUSS, LOGLIK_LAPLACE = 0, 1   # enum sipnet_loglik_kind
+LOGLIK_TILE_ROWS, LOGLIK_MAX_TERMS = 256, 8   # SIPNET_LOGLIK_TILE_ROWS, SIPNET_LOGLIK_MAX_TERMS
+
+
+class LoglikTerm(C.Structure):
+    """struct sipnet_loglik_term: one observed series of sipnet_batch_series_loglik (device arrays); held: the tensors the
+    pointers point into"""
+    _fields_ = [("d_series", C.c_void_p), ("d_obs", C.c_void_p), ("d_sd", C.c_void_p), ("rows", C.c_int32),
+                ("sum_steps", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double)]
+    held = ()
+
 
 class EnkfSeries(C.Structure):
     """struct sipnet_enkf_series: one series of sipnet_batch_enkf_analysis_smooth (device arrays [rows][ld])"""
@@ -194,6 +205,9 @@ SIGNATURES = {
                                            C.c_int32, _P, _P, _P, _P]),
     "sipnet_batch_pf_analysis_sites": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, _P,
                                                  _P, _P, _P]),
+    "sipnet_batch_series_loglik": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                             _P, _P]),
+    "sipnet_batch_pf_resample_sites": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     "sipnet_batch_enkf_analysis_sites": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
                                                    _P, _P, _P, _P]),
     "sipnet_enkf_params_check": (C.c_int, [C.c_int32, _P, _P, _P]),

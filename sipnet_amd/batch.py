@@ -11,8 +11,8 @@ import weakref
 
 import numpy as np
 
-from ._lib import (F64, KERNEL_AUTO, NDBG, NPARAMS, NREC, NSTATE, RING_SLOTS, EnkfObs, EnkfParam, EnkfSeries, Event,
-                   LaunchInfo, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
+from ._lib import (F64, KERNEL_AUTO, LOGLIK_GAUSS, LOGLIK_LAPLACE, LOGLIK_MAX_TERMS, NDBG, NPARAMS, NREC, NSTATE, RING_SLOTS,
+                   EnkfObs, EnkfParam, EnkfSeries, Event, LaunchInfo, LoglikTerm, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
 from .config import pool_mask
 from .enkf_local import EnkfLocalization
 
@@ -42,6 +42,18 @@ def quantile_positions(n, q):
     g = np.zeros(qs.size)
     check(lib().sipnet_quantile_positions(int(n), int(qs.size), ptr(qs), ptr(lo), ptr(g)), "quantile_positions")
     return lo, g
+
+
+def loglik_term(series, obs, sd, kind=LOGLIK_GAUSS, scale=1.0, sum_steps=1):
+    """one observed series of Batch.series_loglik: series [rows * sum_steps][ld] (a contiguous 2-D float32 / float64 device
+    tensor: a plane of run(), an array of run_sums(), a smoothed series) against obs and sd [n_sites][rows] (array-likes,
+    uploaded as float64, or float64 device tensors; obs NaN: a gap; sd: the Gaussian sigma or the Laplace scale b).  Row r
+    is compared with scale * (the sum of series rows r * sum_steps .. (r + 1) * sum_steps - 1).  The batch checks the shapes."""
+    if kind not in (LOGLIK_GAUSS, LOGLIK_LAPLACE):
+        raise ValueError("loglik_term: kind must be LOGLIK_GAUSS or LOGLIK_LAPLACE")
+    t = LoglikTerm(0, 0, 0, 0, int(sum_steps), int(kind), 0, float(scale))
+    t.held = (series, obs, sd)
+    return t
 
 
 class Batch:
@@ -427,6 +439,84 @@ class Batch:
                                                     ptr(logw), ptr(anc), ptr(fixed), ptr(total_out), self._stream()),
               "pf_analysis_sites")
         return (anc, logw, fixed) if return_fixed else (anc, logw)
+
+    def series_loglik(self, terms, normalise=True, add=None, out=None, parts_out=None, used_out=None, info_out=None, path=0):
+        """every member's log-likelihood of a window against observed series with gaps (sipnet_batch_series_loglik).  terms:
+        sa.loglik_term(...) values, at most sa.LOGLIK_MAX_TERMS, all of one dtype and row pitch; normalise: with the
+        densities' constants; add: float64 device tensor [ncol] added last (may be `out`: weights carried over windows).
+        out [ncol] f64, parts_out [n_terms][ncol] f64 (each term's own sum), used_out [n_sites][n_terms] int32 (rows used),
+        info_out [n_sites][2] int32 ({code, rows used}; no host synchronisation -- without it the call checks obs and sd
+        first and raises before anything is written): device tensors to write into.  path: 0 auto, 1 one launch, 2 tiles'
+        sums and their sum (the same bits).  -> out.  The batch is not changed."""
+        t = self._torch
+        what = "series_loglik"
+        terms = list(terms)
+        if not 1 <= len(terms) <= LOGLIK_MAX_TERMS:
+            raise ValueError(f"{what}: needs 1..{LOGLIK_MAX_TERMS} terms")
+        layouts, desc, held = set(), [], []
+        for k, term in enumerate(terms):
+            series, obs, sd = term.held
+            if (not t.is_tensor(series) or not series.is_cuda or series.dim() != 2 or series.dtype not in (t.float32, t.float64)
+                    or not series.is_contiguous() or series.shape[1] < self.ncol):
+                raise ValueError(f"{what}: term {k}: series must be a contiguous 2-D float32 / float64 device tensor "
+                                 f"[rows * sum_steps][ld >= {self.ncol}]")
+            p, f32, n, ld = self._plane(series)
+            if term.sum_steps < 1 or n < term.sum_steps or n % term.sum_steps:
+                raise ValueError(f"{what}: term {k}: {n} series rows are no multiple of sum_steps = {term.sum_steps}")
+            rows = n // term.sum_steps
+            obs = self._upload(what, obs, self.n_sites * rows, f"term {k}'s obs")
+            sd = self._upload(what, sd, self.n_sites * rows, f"term {k}'s sd")
+            layouts.add((f32, ld))
+            held += [obs, sd]
+            desc.append(LoglikTerm(series.data_ptr(), obs.data_ptr(), sd.data_ptr(), rows, term.sum_steps, term.kind, 0, term.scale))
+        if len(layouts) > 1:
+            raise ValueError(f"{what}: the terms' series differ in dtype or row pitch: " + str(sorted(layouts)))
+        f32, ld = layouts.pop()
+
+        def dense(x, dtype, n, name):
+            if x is not None and not _dense(x, dtype, n):
+                raise ValueError(f"{what}: {name} must be a contiguous device tensor of {n} {dtype} values")
+            return x
+
+        add = dense(add, t.float64, self.ncol, "add")
+        if out is None:
+            out = t.empty(self.ncol, dtype=t.float64, device=self.device)
+        dense(out, t.float64, self.ncol, "out")
+        dense(parts_out, t.float64, len(terms) * self.ncol, "parts_out")
+        dense(used_out, t.int32, self.n_sites * len(terms), "used_out")
+        dense(info_out, t.int32, 2 * self.n_sites, "info_out")
+        check(self.L.sipnet_batch_series_loglik(self.h, len(desc), c_array(LoglikTerm, desc), f32, ld, int(bool(normalise)),
+                                                int(path), ptr(add), ptr(out), ptr(parts_out), ptr(used_out), ptr(info_out),
+                                                self._stream()), what)
+        return out
+
+    def pf_resample_sites(self, logw, u0, beta=None, ess_min=None, with_params=False, total_out=None, ess_out=None,
+                          return_fixed=False):
+        """the many-site analysis from log-weights the caller gives (sipnet_batch_pf_resample_sites): everything of
+        pf_analysis_sites after its log-weights.  logw: float64 device tensor [ncol] (series_loglik's out, or anything else;
+        NaN and -inf weigh nothing); u0, beta (None: 1; in (0, 1] it tempers), ess_min (None: every site resamples and logw
+        is not written; else a site whose effective sample size is at least ess_min[s] keeps its particles -- total -3 --
+        and a site that resamples gets its log-weights set to 0): one value per site.  total_out: int64 device tensor
+        [n_sites] (no host synchronisation); ess_out: float64 device tensor [n_sites].  Returns (ancestors int32 [ncol] --
+        global columns --[, fixed-point weights int64 [ncol]]) on the device."""
+        t = self._torch
+        what = "pf_resample_sites"
+        if not t.is_tensor(logw) or not _dense(logw, t.float64, self.ncol):
+            raise ValueError(f"{what}: logw must be a contiguous float64 device tensor of {self.ncol} values")
+        u0 = self._upload(what, u0, self.n_sites, "u0")
+        beta = self._upload(what, beta, self.n_sites, "beta")
+        ess_min = self._upload(what, ess_min, self.n_sites, "ess_min")
+        if u0 is None:
+            raise ValueError(f"{what}: u0 needs {self.n_sites} values")
+        if total_out is not None and not _dense(total_out, t.int64, self.n_sites):
+            raise ValueError(f"{what}: total_out must be a contiguous int64 device tensor of {self.n_sites} values")
+        if ess_out is not None and not _dense(ess_out, t.float64, self.n_sites):
+            raise ValueError(f"{what}: ess_out must be a contiguous float64 device tensor of {self.n_sites} values")
+        anc = t.empty(self.ncol, dtype=t.int32, device=self.device)
+        fixed = t.empty(self.ncol, dtype=t.int64, device=self.device) if return_fixed else None
+        check(self.L.sipnet_batch_pf_resample_sites(self.h, ptr(logw), ptr(u0), ptr(beta), ptr(ess_min), int(with_params),
+                                                    ptr(anc), ptr(fixed), ptr(total_out), ptr(ess_out), self._stream()), what)
+        return (anc, fixed) if return_fixed else anc
 
     def enkf_analysis_sites(self, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
         """an ensemble Kalman filter analysis of the member pools, every site a filter of its own, one library call

@@ -23,12 +23,15 @@
 //                    barrier in device memory, pfFusedKernel (why one launch, residency, the barrier: explained there)
 //   pf_plan.inc      the exchange plan of a resampling whose checkpoints travel in packed blocks: the four plan*Kernels
 //   pf_sites.inc     the analysis of a batch of many sites: SitesArgs, pfSitesKernel (a workgroup per site), the split path's
-//                    three launches
+//                    three launches; both from a plane and an observation per site, or from log-weights the caller gives
+//   pf_series.inc    every member's log-likelihood of a window's series against observed series with gaps: LoglikArgs,
+//                    loglikKernel (one launch), loglikTileKernel + loglikCombineKernel (tiles' sums, then their sum in order)
 //
 // The host side runs three filters.  One batch (sipnet_batch_pf_analysis): the PfPre match (takePfPre), the one launch
 // (fusedSetup + the one-batch fields) or the launches of their own, the synchronous check (checkTotal), the resampling
 // gather (resampleColumns: settleParams, recvMapOf, launchGatherMember, adoptSpares, widenExponents).  Many sites
-// (sipnet_batch_pf_analysis_sites): the arguments, sitesLaunch, sitesCheck, resampleColumns.  Across ranks by peer reads:
+// (sipnet_batch_pf_analysis_sites, and sipnet_batch_pf_resample_sites from given log-weights): the arguments, sitesLaunch,
+// sitesCheck, resampleColumns.  Series weights (sipnet_batch_series_loglik): loglikCheck, the path, the launches.  Across ranks by peer reads:
 // sipnet_batch_pf_publish, _connect (own descriptor, closePeers, mapPeer, fillBank and the crossing counter) and
 // _resample_peers (peerTable, peerAncestors: fusedSetup + the gathered fields or launches, peerGather, adoptSpares).
 #include <hip/hip_runtime.h>
@@ -55,6 +58,7 @@ namespace {
 #include "pf_fused.inc"
 #include "pf_plan.inc"
 #include "pf_sites.inc"
+#include "pf_series.inc"
 
 }  // namespace
 }  // namespace sipnet
@@ -212,6 +216,8 @@ struct PfScratch {
   unsigned long long launches = 0;      // fused launches that were accepted by the runtime
   int occ[3] = {-1, -1, -1};            // resident workgroups per CU of pfFusedKernel<float,false> / <double,false> / <double,true>
   DevBuf<unsigned char> d_sites;        // sipnet_batch_pf_analysis_sites (sitesScratchFor), bytes
+  DevBuf<double> d_loglik;              // sipnet_batch_series_loglik, path 2: [terms' tiles][ncol] the tiles' sums
+  DevBuf<int32_t> d_loglikUsed;         // ... and [n_sites][terms' tiles] the tiles' rows used
 };
 namespace {
 constexpr int kMaxParts = 256;
@@ -692,46 +698,75 @@ int sipnet_batch_pf_analysis(sipnet_batch* b, const void* d_plane, int32_t elem_
 }
 
 // scratch of the many-site analysis: the sites' totals, and for the split path the chunks' maxima, sums and threads' sums
+// (and, behind them, the chunks' sums of squares that given weights' effective sample size needs)
 static int sitesScratchFor(PfScratch& sc, int64_t nSites, int64_t nChunks) {
-  const size_t bytes = (size_t)(nSites + nChunks * (2 + 256)) * sizeof(int64_t);
+  const size_t bytes = (size_t)(nSites + nChunks * (2 + 256 + 2)) * sizeof(int64_t);
   return sc.d_sites.reserve(bytes);
 }
 
 // the many-site analysis on the device: one workgroup per site in one launch, or (split) chunks of sa.chunk columns in three
-static void sitesLaunch(SitesArgs& sa, PfScratch& sc, int64_t nSites, bool split, bool f32, hipStream_t stream) {
+// (given: the weight source is the caller's log-weights, sipnet_batch_pf_resample_sites)
+static void sitesLaunch(SitesArgs& sa, PfScratch& sc, int64_t nSites, bool split, bool f32, hipStream_t stream, bool given = false) {
+  const dim3 sites((unsigned)nSites);
   if (!split) {
-    if (f32) hipLaunchKernelGGL(pfSitesKernel<float>, dim3((unsigned)nSites), dim3(256), 0, stream, sa);
-    else hipLaunchKernelGGL(pfSitesKernel<double>, dim3((unsigned)nSites), dim3(256), 0, stream, sa);
+    if (given) hipLaunchKernelGGL((pfSitesKernel<double, true>), sites, dim3(256), 0, stream, sa);
+    else if (f32) hipLaunchKernelGGL(pfSitesKernel<float>, sites, dim3(256), 0, stream, sa);
+    else hipLaunchKernelGGL(pfSitesKernel<double>, sites, dim3(256), 0, stream, sa);
     return;
   }
   sa.chunkMax = (double*)(sa.total + nSites);
   sa.chunkSum = sa.total + nSites + nSites * sa.nChunks;
   sa.threadIncl = sa.chunkSum + nSites * sa.nChunks;
+  sa.chunkSq = sa.threadIncl + nSites * sa.nChunks * 256;
   if (!sa.w) sa.w = sc.d_w;
   const dim3 chunks((unsigned)nSites, (unsigned)sa.nChunks);
+  const dim3 tiles((unsigned)nSites, (unsigned)((sa.M + 255) / 256));
+  if (given) {
+    hipLaunchKernelGGL((sitesChunkKernel<double, true>), chunks, dim3(256), 0, stream, sa);
+    hipLaunchKernelGGL(sitesWeightKernel<true>, chunks, dim3(256), 0, stream, sa);
+    hipLaunchKernelGGL(sitesAncestorKernel<true>, tiles, dim3(256), 0, stream, sa);
+    return;
+  }
   if (f32) hipLaunchKernelGGL(sitesChunkKernel<float>, chunks, dim3(256), 0, stream, sa);
   else hipLaunchKernelGGL(sitesChunkKernel<double>, chunks, dim3(256), 0, stream, sa);
-  hipLaunchKernelGGL(sitesWeightKernel, chunks, dim3(256), 0, stream, sa);
-  hipLaunchKernelGGL(sitesAncestorKernel, dim3((unsigned)nSites, (unsigned)((sa.M + 255) / 256)), dim3(256), 0, stream, sa);
+  hipLaunchKernelGGL(sitesWeightKernel<false>, chunks, dim3(256), 0, stream, sa);
+  hipLaunchKernelGGL(sitesAncestorKernel<false>, tiles, dim3(256), 0, stream, sa);
 }
 // the synchronous checks of the many-site analysis, before anything is resampled: the sites' totals, read back
-static int sitesCheck(PfScratch& sc, int64_t nSites, hipStream_t stream) {
+// (who: the entry point; invalid: what makes a site's arguments bad there)
+static int sitesCheck(PfScratch& sc, int64_t nSites, hipStream_t stream, const char* who = "sipnet_batch_pf_analysis_sites",
+                      const char* invalid = "a finite obs needs a finite sigma > 0; 0 <= u0 < 1") {
   std::vector<int64_t> tot((size_t)nSites);
   HIP_TRY(hipMemcpyAsync(tot.data(), sc.d_sites, (size_t)nSites * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   for (int64_t s = 0; s < nSites; s++)
     if (tot[(size_t)s] == kSiteInvalid) {
-      setError("sipnet_batch_pf_analysis_sites: site " + std::to_string(s) +
-               ": bad argument (a finite obs needs a finite sigma > 0; 0 <= u0 < 1); nothing was resampled");
+      setError(std::string(who) + ": site " + std::to_string(s) + ": bad argument (" + invalid + "); nothing was resampled");
       return SIPNET_ERR_BAD_ARGUMENT;
     }
   for (int64_t s = 0; s < nSites; s++)
     if (tot[(size_t)s] == 0) {
-      setError("sipnet_batch_pf_analysis_sites: site " + std::to_string(s) +
-               ": every particle has zero weight; nothing was resampled");
+      setError(std::string(who) + ": site " + std::to_string(s) + ": every particle has zero weight; nothing was resampled");
       return SIPNET_ERR_BAD_PARAMETER;
     }
   return SIPNET_OK;
+}
+// the many-site analysis' path and the split path's chunks (256 x a power of two columns, at most kSitesMaxChunks per site).
+// One workgroup per site only when the sites fill the device: fewer sites than CUs leave CUs idle while a few of them
+// read all the planes (64 x 4096 particles: 0.22 ms against 0.14 split, profiles/r07_pf_sites_time.txt)
+static bool sitesGeometry(const sipnet_batch* b, int* chunk, int* nChunks) {
+  const int64_t M = b->n_members;
+  *chunk = 256;   // (at least two workgroups per CU for the log-weights of a few big sites)
+  while ((M + *chunk - 1) / *chunk > kSitesMaxChunks) *chunk *= 2;
+  *nChunks = (int)((M + *chunk - 1) / *chunk);
+  return M > kSitesLds || b->n_sites < b->numCUs || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
+}
+// what sipnet_batch_pf_info reports of a many-site analysis
+static void sitesInfo(sipnet_batch* b, bool split) {
+  b->pfInfo.fused = split ? 0 : 1;
+  b->pfInfo.grid = split ? 0 : (int32_t)b->n_sites;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = b->ncol;
 }
 
 int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps, int64_t ld,
@@ -756,12 +791,8 @@ int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t
   rc = pfScratchFor(sc, b->ncol, stream);
   if (rc) return rc;
   const int64_t M = b->n_members, nSites = b->n_sites;
-  // one workgroup per site only when the sites fill the device: fewer sites than CUs leave CUs idle while a few of them
-  // read all the planes (64 x 4096 particles: 0.22 ms against 0.14 split, profiles/r07_pf_sites_time.txt)
-  const bool split = M > kSitesLds || nSites < b->numCUs || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
-  int chunk = 256;   // (at least two workgroups per CU for the log-weights of a few big sites)
-  while ((M + chunk - 1) / chunk > kSitesMaxChunks) chunk *= 2;
-  const int nChunks = (int)((M + chunk - 1) / chunk);
+  int chunk, nChunks;
+  const bool split = sitesGeometry(b, &chunk, &nChunks);
   rc = sitesScratchFor(sc, nSites, split ? nSites * nChunks : 0);
   if (rc) return rc;
   SitesArgs sa{};
@@ -782,15 +813,163 @@ int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t
   sa.totalOut = d_site_total;
   sitesLaunch(sa, sc, nSites, split, elem_is_f32 != 0, stream);
   HIP_TRY(hipGetLastError());
-  b->pfInfo.fused = split ? 0 : 1;
-  b->pfInfo.grid = split ? 0 : (int32_t)nSites;
-  b->pfInfo.budget = 0;
-  b->pfInfo.nSlots = b->ncol;
+  sitesInfo(b, split);
   if (!d_site_total) {
     rc = sitesCheck(sc, nSites, stream);
     if (rc) return rc;
   }
   return resampleColumns(b, d_ancestors, nullptr, 0, nullptr, with_params, hip_stream);
+}
+
+int sipnet_batch_pf_resample_sites(sipnet_batch* b, double* d_logw, const double* d_u0, const double* d_beta,
+                                   const double* d_ess_min, int32_t with_params, int32_t* d_ancestors,
+                                   int64_t* d_fixed_weights, int64_t* d_site_total, double* d_ess, void* hip_stream) {
+  if (!b || !d_logw || !d_u0 || !d_ancestors || b->ncol > (int64_t)1 << 22) {
+    setError("sipnet_batch_pf_resample_sites: bad argument (device pointers d_logw, d_u0, d_ancestors; at most 4194304 particles)");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  if (b->pfPeers) {
+    setError("sipnet_batch_pf_resample_sites: this batch is connected to a filter across ranks (sipnet_batch_pf_connect): "
+             "resample through sipnet_batch_pf_resample_peers");
+    return SIPNET_ERR_BAD_ARGUMENT;
+  }
+  int rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  b->pfPre.valid = false;
+  PfScratch& sc = scratchOf(b);
+  rc = pfScratchFor(sc, b->ncol, stream);
+  if (rc) return rc;
+  const int64_t nSites = b->n_sites;
+  int chunk, nChunks;
+  const bool split = sitesGeometry(b, &chunk, &nChunks);
+  rc = sitesScratchFor(sc, nSites, split ? nSites * nChunks : 0);
+  if (rc) return rc;
+  SitesArgs sa{};
+  sa.M = b->n_members;
+  sa.nChunks = nChunks;
+  sa.chunk = chunk;
+  sa.u0 = d_u0;
+  sa.logw = d_logw;
+  sa.w = d_fixed_weights;
+  sa.anc = d_ancestors;
+  sa.total = (int64_t*)sc.d_sites.get();
+  sa.totalOut = d_site_total;
+  sa.beta = d_beta;
+  sa.essMin = d_ess_min;
+  sa.ess = d_ess;
+  sitesLaunch(sa, sc, nSites, split, false, stream, /*given=*/true);
+  HIP_TRY(hipGetLastError());
+  sitesInfo(b, split);
+  if (!d_site_total) {
+    rc = sitesCheck(sc, nSites, stream, "sipnet_batch_pf_resample_sites",
+                    "0 <= u0 < 1, a finite beta > 0, an ess_min that is not NaN, no +inf log-weight");
+    if (rc) return rc;
+  }
+  return resampleColumns(b, d_ancestors, nullptr, 0, nullptr, with_params, hip_stream);
+}
+
+// ---- series likelihood weights ---------------------------------------------------------------------------------------
+static int loglikRefuse(const std::string& why) {
+  setError("sipnet_batch_series_loglik: " + why);
+  return SIPNET_ERR_BAD_ARGUMENT;
+}
+// the synchronous form's check: obs and sd read back, the first site and term with bad input named
+static int loglikCheck(const sipnet_batch* b, int32_t n_terms, const sipnet_loglik_term* terms, hipStream_t stream) {
+  std::vector<double> obs, sd;
+  for (int q = 0; q < n_terms; q++) {
+    const size_t n = (size_t)b->n_sites * (size_t)terms[q].rows;
+    obs.resize(n);
+    sd.resize(n);
+    HIP_TRY(hipMemcpyAsync(obs.data(), terms[q].d_obs, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(sd.data(), terms[q].d_sd, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < n; i++) {
+      const double y = obs[i];
+      if (y != y) continue;
+      if (std::isfinite(y) && sd[i] > 0.0 && std::isfinite(sd[i])) continue;
+      return loglikRefuse("site " + std::to_string(i / (size_t)terms[q].rows) + ", term " + std::to_string(q) + ", row " +
+                          std::to_string(i % (size_t)terms[q].rows) +
+                          ": bad input (an obs that is not NaN must be finite and needs a finite sd > 0); nothing was written");
+    }
+  }
+  return SIPNET_OK;
+}
+
+int sipnet_batch_series_loglik(sipnet_batch* b, int32_t n_terms, const sipnet_loglik_term* terms, int32_t elem_is_f32,
+                               int64_t ld, int32_t normalise, int32_t path, const double* d_add, double* d_loglik,
+                               double* d_parts, int32_t* d_used, int32_t* d_site_info, void* hip_stream) {
+  if (!b || !terms || !d_loglik) return loglikRefuse("a NULL batch, terms or d_loglik");
+  if (n_terms < 1 || n_terms > kLoglikMaxTerms) return loglikRefuse("n_terms must be 1.." + std::to_string(kLoglikMaxTerms));
+  if (ld < b->ncol) return loglikRefuse("ld < ncol");
+  if (b->ncol > (int64_t)1 << 22) return loglikRefuse("at most 4194304 columns");
+  if (path < 0 || path > 2) return loglikRefuse("path must be 0 (auto), 1 or 2");
+  LoglikArgs a{};
+  int64_t tilesTotal = 0;
+  for (int q = 0; q < n_terms; q++) {
+    const sipnet_loglik_term& t = terms[q];
+    const std::string who = "term " + std::to_string(q) + ": ";
+    if (!t.d_series || !t.d_obs || !t.d_sd) return loglikRefuse(who + "a NULL series, obs or sd");
+    if (t.kind != SIPNET_LOGLIK_GAUSS && t.kind != SIPNET_LOGLIK_LAPLACE) return loglikRefuse(who + "kind must be SIPNET_LOGLIK_GAUSS or SIPNET_LOGLIK_LAPLACE");
+    if (t.rows < 1 || t.sum_steps < 1) return loglikRefuse(who + "rows and sum_steps must be at least 1");
+    if (!std::isfinite(t.scale)) return loglikRefuse(who + "the scale is not finite");
+    LoglikTerm& k = a.term[q];
+    k.series = t.d_series;
+    k.obs = t.d_obs;
+    k.sd = t.d_sd;
+    k.rows = t.rows;
+    k.sumSteps = t.sum_steps;
+    k.kind = t.kind;
+    k.tiles = (int32_t)(((int64_t)t.rows + kLoglikTile - 1) / kLoglikTile);
+    k.scale = t.scale;
+    tilesTotal += k.tiles;
+  }
+  if (b->planDirty) return loglikRefuse("needs a batch that was set up (sipnet_batch_setup): the members' status is read");
+  int rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int64_t M = b->n_members, nSites = b->n_sites, chunksPerSite = (M + 255) / 256, groups = nSites * chunksPerSite;
+  // path 2 when the columns alone leave the device short of workgroups (10 240 members x 17 520 rows: 40 of them on 256 CUs)
+  // and there is more than one tile to spread
+  bool two = path == 2 || (path == 0 && tilesTotal > 1 && groups < 2 * (int64_t)b->numCUs);
+  if (two && groups * tilesTotal > (int64_t)INT32_MAX) {
+    if (path == 2) return loglikRefuse("path 2 would need more than INT32_MAX workgroups");
+    two = false;
+  }
+  if (!d_site_info) {
+    rc = loglikCheck(b, n_terms, terms, stream);
+    if (rc) return rc;
+  }
+  a.nTerms = n_terms;
+  a.normalise = normalise != 0;
+  a.chunksPerSite = (int32_t)chunksPerSite;
+  a.tilesTotal = (int32_t)tilesTotal;
+  a.ld = ld;
+  a.M = M;
+  a.ncol = b->ncol;
+  a.status = b->d_state + (size_t)ST_status * b->ncol;
+  a.add = d_add;
+  a.out = d_loglik;
+  a.parts = d_parts;
+  a.used = d_used;
+  a.siteInfo = d_site_info;
+  if (!two) {
+    if (elem_is_f32) hipLaunchKernelGGL(loglikKernel<float>, dim3((unsigned)groups), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(loglikKernel<double>, dim3((unsigned)groups), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return SIPNET_OK;
+  }
+  PfScratch& sc = scratchOf(b);
+  RC_TRY(sc.d_loglik.reserve((size_t)tilesTotal * (size_t)b->ncol));
+  RC_TRY(sc.d_loglikUsed.reserve((size_t)tilesTotal * (size_t)nSites));
+  a.partial = sc.d_loglik;
+  a.tileUsed = sc.d_loglikUsed;
+  const dim3 grid((unsigned)(groups * tilesTotal));
+  if (elem_is_f32) hipLaunchKernelGGL(loglikTileKernel<float>, grid, dim3(256), 0, stream, a, groups);
+  else hipLaunchKernelGGL(loglikTileKernel<double>, grid, dim3(256), 0, stream, a, groups);
+  hipLaunchKernelGGL(loglikCombineKernel, dim3((unsigned)groups), dim3(256), 0, stream, a);
+  HIP_TRY(hipGetLastError());
+  return SIPNET_OK;
 }
 
 }  // extern "C"
