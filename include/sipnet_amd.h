@@ -419,7 +419,27 @@ int sipnet_batch_run_stats(sipnet_batch *b, int32_t step0, int32_t n_steps, void
                            void *d_gpp, void *d_et, int64_t ld, double *d_stats,
                            void *hip_stream);
 
-/* Copy per-member state to / from HOST memory: state[ncol][SIPNET_NSTATE]. */
+/* Copy per-member state to / from HOST memory: state[ncol][SIPNET_NSTATE].
+ *
+ * What a caller of set_state may change (tests/test_gpu_state_edits.py holds every step kernel to the reference on it):
+ *   0..12   the pools: any finite value, and >= 0 for all but plantCAccountingDelta.  The next step derives the alive
+ *           flag from them (hasSufficientBiomass, sipnet.c:1530-1544) like every step does; soil water above capacity,
+ *           snow at any time of the year, leaf carbon or mineral N of 0 are forecast as the reference forecasts them.
+ *           Negative or non-finite pools are undefined.
+ *   14..26  the accumulators: reporting only, nothing in a step depends on them.
+ *   29      status: a non-zero value takes the member out of every later launch and analysis.
+ * What must be handed back as read -- or kept consistent by the caller:
+ *   13, 28  the ring sum and ring_valid_from belong to the rings (sipnet_batch_set_rings): the sum is the weighted sum of
+ *           the slots inserted at steps >= ring_valid_from, and no launch recomputes it.
+ *   27      the phenology bits;  30, 31  died_at_step and the clamp count (reporting).
+ * Pools that leave a member DEAD at the head of the next step (an emptied stand, plantWoodC + plantCAccountingDelta
+ * <= 1e-6): write 0 into slot 13 and the index of that next step into slot 28 along with them.  Every death the model
+ * produces itself is a death step, which resets the running mean of NPP (sipnet.c:1757), and the engine takes a dead
+ * step as the start of a new ring epoch: entries before it count as zero, while the sum is left as it was handed in.
+ * The reference, given such pools from outside, has no death step and carries its old ring over the dead steps; a ring
+ * indexed by step cannot stand still, so the engine defines such an edit as a death -- with the two slots written it
+ * forecasts what the reference forecasts after resetMeanTracker(meanNPP, 0) at that record, without them neither.
+ * The filters never need this: their analyses keep the forecast of a member that would fail hasSufficientBiomass. */
 int sipnet_batch_get_state(sipnet_batch *b, double *state, void *hip_stream);
 int sipnet_batch_set_state(sipnet_batch *b, const double *state, void *hip_stream);
 /* Ring contents of one column to HOST: values[SIPNET_RING_SLOTS]. */

@@ -177,6 +177,46 @@ int ref_run_member(const double *raw_params, double *rec, double *nee,
   return t;
 }
 
+/* ref_run_member with overwrites, to pin sipo_run_block_edits: before updateState() of record
+ * edit_step[i] (strictly ascending) every finite entry of edit_pools[i][13] replaces the field of
+ * the global `envi`, in the order of captureRecord()'s columns 14..26; NaN keeps the field.
+ * Nothing else of the reference's state is touched, unless edit_ring_reset (NULL or [n_edits])
+ * is non-zero: then the reference's own resetMeanTracker(meanNPP, 0) is called as well, as its
+ * death step does (sipnet.c:1757). */
+int ref_run_member_edits(const double *raw_params, int n_edits, const int *edit_step,
+                         const double *edit_pools, const int *edit_ring_reset, double *rec) {
+  memcpy(&params, raw_params, sizeof(params));
+  setupModel();
+  if (ctx.events) {
+    setupEvents();
+  }
+  int t = 0, next = 0;
+  while (climate != NULL) {
+    if (next < n_edits && edit_step[next] == t) {
+      double *field[13] = {&envi.plantWoodC, &envi.plantLeafC, &envi.soilC, &envi.soilWater,
+                           &envi.litterC, &envi.snow, &envi.coarseRootC, &envi.fineRootC,
+                           &envi.minN, &envi.soilOrgN, &envi.litterN, &envi.plantStorageN,
+                           &envi.plantCAccountingDelta};
+      for (int k = 0; k < 13; k++) {
+        if (isfinite(edit_pools[13 * next + k])) {
+          *field[k] = edit_pools[13 * next + k];
+        }
+      }
+      if (edit_ring_reset && edit_ring_reset[next]) {
+        resetMeanTracker(meanNPP, 0.0);
+      }
+      next++;
+    }
+    updateState();
+    if (rec) {
+      captureRecord(rec + (size_t)REF_NREC * t);
+    }
+    climate = climate->nextClim;
+    t++;
+  }
+  return t;
+}
+
 /* Time `n_members` back-to-back member runs (params given as
  * [n_members][NUM_PARAMS]); returns seconds; sink defeats dead-code removal. */
 double ref_time_members(const double *raw_params, int n_members,

@@ -1408,11 +1408,44 @@ static void capture(const Member *M, double *r) {
   r[35] = tr->totGpp;
 }
 
+/* Overwrites for one member (sipo_run_block_edits): before step(M, c, step[i]) every finite entry of
+ * pools[i * pool_stride + 0..12] replaces the pool, and of params[i * param_stride + 0..79] the converted
+ * parameter; NaN keeps the member's own.  Nothing else of Member is touched -- unless ring_reset[i * reset_stride]
+ * asks for what a death step does to the running mean (sipnet.c:1757). */
+typedef struct {
+  int n;
+  const int *step;
+  const double *pools, *params; /* params may be NULL */
+  const int *ring_reset;        /* may be NULL */
+  size_t pool_stride, param_stride, reset_stride;
+} Edits;
+
+static void applyEdit(Member *M, const Edits *ed, int i) {
+  const double *src = ed->pools + ed->pool_stride * (size_t)i;
+  double *e = (double *)&M->e; /* Pools is 13 doubles in Envi order */
+  for (int k = 0; k < (int)(sizeof(Pools) / sizeof(double)); k++) {
+    if (isfinite(src[k])) {
+      e[k] = src[k];
+    }
+  }
+  if (ed->params) {
+    src = ed->params + ed->param_stride * (size_t)i;
+    for (int k = 0; k < SIPO_NPARAMS; k++) {
+      if (isfinite(src[k])) {
+        M->p[k] = src[k];
+      }
+    }
+  }
+  if (ed->ring_reset && ed->ring_reset[ed->reset_stride * (size_t)i]) {
+    ringReset(&M->ring, 0.0);
+  }
+}
+
 static int runMember(Member *M, const int *flags, const double *raw_params,
                      int n_steps, const double *clim, const int *year,
                      const int *day, int n_events, const sipo_event *events,
                      double *rec, double *nee, double *gpp, double *et,
-                     size_t out_stride, FILE *evout, double *dbg) {
+                     size_t out_stride, FILE *evout, double *dbg, const Edits *ed) {
   if (n_steps <= 0) {
     return SIPO_OK;
   }
@@ -1425,8 +1458,12 @@ static int runMember(Member *M, const int *flags, const double *raw_params,
   M->events = events;
   M->ev_next = 0;
   M->evout = evout;
+  int next_edit = 0;
   for (int t = 0; t < n_steps; t++) {
     Clim c = climAt(clim, year, day, t);
+    if (ed && next_edit < ed->n && ed->step[next_edit] == t) {
+      applyEdit(M, ed, next_edit++);
+    }
     step(M, &c, t);
     if (M->status) {
       return M->status;
@@ -1478,7 +1515,7 @@ int sipo_run_member(const int *flags, const double *raw_params, int n_steps,
     evout = fopen(events_out, "w");
   }
   int st = runMember(M, flags, raw_params, n_steps, clim, year, day, n_events,
-                     events, rec, nee, gpp, et, 1, evout, NULL);
+                     events, rec, nee, gpp, et, 1, evout, NULL, NULL);
   if (evout) {
     fclose(evout);
   }
@@ -1495,23 +1532,32 @@ int sipo_run_member_debug(const int *flags, const double *raw_params, int n_step
                           double *dbg) {
   Member *M = (Member *)malloc(sizeof(Member));
   int st = runMember(M, flags, raw_params, n_steps, clim, year, day, n_events,
-                     events, rec, NULL, NULL, NULL, 1, NULL, dbg);
+                     events, rec, NULL, NULL, NULL, 1, NULL, dbg, NULL);
   free(M);
   return st;
 }
 
-int sipo_run_block(const int *flags, const double *raw_params, int m0, int m1,
-                   int n_members_total, int n_steps, const double *clim,
-                   const int *year, const int *day, int n_events,
-                   const sipo_event *events, double *nee, double *gpp,
-                   double *et, double *final_rec, int *status) {
+static int runBlock(const int *flags, const double *raw_params, int m0, int m1,
+                    int n_members_total, int n_steps, const double *clim,
+                    const int *year, const int *day, int n_events,
+                    const sipo_event *events, double *nee, double *gpp,
+                    double *et, double *final_rec, int *status, int n_edits,
+                    const int *edit_step, const double *edit_pools,
+                    const double *edit_params, const int *edit_ring_reset, double *rec,
+                    sipo_diag *diag) {
   Member *M = (Member *)malloc(sizeof(Member));
   int worst = 0;
   for (int m = m0; m < m1; m++) {
+    Edits ed = {n_edits, edit_step, edit_pools ? edit_pools + (size_t)13 * m : NULL,
+                edit_params ? edit_params + (size_t)SIPO_NPARAMS * m : NULL,
+                edit_ring_reset ? edit_ring_reset + m : NULL,
+                (size_t)13 * n_members_total, (size_t)SIPO_NPARAMS * n_members_total,
+                (size_t)n_members_total};
     int st = runMember(M, flags, raw_params + (size_t)SIPO_NPARAMS * m, n_steps,
-                       clim, year, day, n_events, events, NULL,
+                       clim, year, day, n_events, events, rec,
                        nee ? nee + m : NULL, gpp ? gpp + m : NULL,
-                       et ? et + m : NULL, (size_t)n_members_total, NULL, NULL);
+                       et ? et + m : NULL, (size_t)n_members_total, NULL, NULL,
+                       edit_pools ? &ed : NULL);
     if (status) {
       status[m] = st;
     }
@@ -1521,9 +1567,45 @@ int sipo_run_block(const int *flags, const double *raw_params, int m0, int m1,
     if (final_rec) {
       capture(M, final_rec + (size_t)SIPO_NREC * m);
     }
+    if (diag) {
+      diag[m] = M->diag;
+    }
   }
   free(M);
   return worst;
+}
+
+int sipo_run_block(const int *flags, const double *raw_params, int m0, int m1,
+                   int n_members_total, int n_steps, const double *clim,
+                   const int *year, const int *day, int n_events,
+                   const sipo_event *events, double *nee, double *gpp,
+                   double *et, double *final_rec, int *status) {
+  return runBlock(flags, raw_params, m0, m1, n_members_total, n_steps, clim, year, day,
+                  n_events, events, nee, gpp, et, final_rec, status, 0, NULL, NULL, NULL, NULL, NULL, NULL);
+}
+
+int sipo_run_block_edits(const int *flags, const double *raw_params, int m0, int m1,
+                         int n_members_total, int n_steps, const double *clim,
+                         const int *year, const int *day, int n_events,
+                         const sipo_event *events, double *nee, double *gpp,
+                         double *et, double *final_rec, int *status, int n_edits,
+                         const int *edit_step, const double *edit_pools,
+                         const double *edit_params, const int *edit_ring_reset, double *rec,
+                         sipo_diag *diag) {
+  for (int i = 0; i < n_edits; i++) {
+    if (edit_step[i] < 0 || edit_step[i] >= n_steps || (i > 0 && edit_step[i] <= edit_step[i - 1])) {
+      return SIPO_ERR_BAD_PARAM;
+    }
+  }
+  if (n_edits > 0 && !edit_pools) {
+    return SIPO_ERR_BAD_PARAM;
+  }
+  if (rec && m1 - m0 != 1) { /* the full record is one member's */
+    return SIPO_ERR_BAD_PARAM;
+  }
+  return runBlock(flags, raw_params, m0, m1, n_members_total, n_steps, clim, year, day, n_events,
+                  events, nee, gpp, et, final_rec, status, n_edits, edit_step, edit_pools,
+                  edit_params, edit_ring_reset, rec, diag);
 }
 
 double sipo_time_members(const int *flags, const double *raw_params,
@@ -1535,7 +1617,7 @@ double sipo_time_members(const int *flags, const double *raw_params,
   clock_gettime(CLOCK_MONOTONIC, &t0);
   for (int m = 0; m < n_members; m++) {
     runMember(M, flags, raw_params + (size_t)SIPO_NPARAMS * m, n_steps, clim,
-              year, day, 0, NULL, NULL, NULL, NULL, NULL, 1, NULL, NULL);
+              year, day, 0, NULL, NULL, NULL, NULL, NULL, 1, NULL, NULL, NULL);
     acc += M->tr.totNee;
   }
   clock_gettime(CLOCK_MONOTONIC, &t1);

@@ -135,6 +135,35 @@ int sipo_run_block(const int *flags, const double *raw_params, int m0, int m1,
                    const sipo_event *events, double *nee, double *gpp,
                    double *et, double *final_rec, int *status);
 
+/* sipo_run_block with overwrites: what a filter's analysis, or a caller's set_state, does to a
+ * member between two steps.
+ *  edit_step    [n_edits], strictly ascending, each in 0 .. n_steps-1
+ *  edit_pools   [n_edits][n_members_total][13], `Envi` order (record columns 14..26)
+ *  edit_params  NULL or [n_edits][n_members_total][80], CONVERTED units (what setupModel leaves)
+ * Immediately before the step loop's pass over record edit_step[i], every finite entry replaces
+ * the member's pool or converted parameter; a NaN entry keeps the member's own.  Nothing else
+ * of the member is touched: ring, trackers, phenology bits, d_till_mod and the event cursor
+ * carry on, and isAlive is derived from the pools at the head of the step as always
+ * (sipnet.c:1538-1544), so an emptied stand is dead from that step on without a transition
+ * (diag.died_at_step records transitions only).  n_edits == 0 gives sipo_run_block's bits.
+ *  edit_ring_reset  NULL or [n_edits][n_members_total]: non-zero also resets the member's running
+ *               mean of NPP to 0 at that edit, by the reference's own resetMeanTracker(meanNPP, 0) --
+ *               what its death step does (sipnet.c:1757) and an emptying from outside by-passes.
+ *               This is how the engine defines pools written from outside that leave a member dead
+ *               (include/sipnet_amd.h, sipnet_batch_set_state).
+ *  rec          NULL, or [n_steps][SIPO_NREC] when m1 == m0 + 1: that member's full record
+ *  diag         NULL or [n_members_total]
+ * SIPO_ERR_BAD_PARAM, nothing run: steps not ascending or out of range, edits without pools,
+ * rec with more than one member. */
+int sipo_run_block_edits(const int *flags, const double *raw_params, int m0, int m1,
+                         int n_members_total, int n_steps, const double *clim,
+                         const int *year, const int *day, int n_events,
+                         const sipo_event *events, double *nee, double *gpp,
+                         double *et, double *final_rec, int *status, int n_edits,
+                         const int *edit_step, const double *edit_pools,
+                         const double *edit_params, const int *edit_ring_reset, double *rec,
+                         sipo_diag *diag);
+
 /* ---- single-function probes for the reference's known-answer unit tests ---- */
 /* depeffects.c:11-96 */
 double sipo_clipped_water_frac(double water, double whc);

@@ -100,6 +100,37 @@ class Oracle:
                                 vp(planes[2]), vp(final), vp(status))
         return planes, final, status
 
+    def run_block_edits(self, flags, raw, clim, edit_steps, edit_pools, edit_params=None, events=None,
+                        rec_member=None, ring_reset=None):
+        """run_block with overwrites: before step edit_steps[i] every finite entry of edit_pools[i][member][13]
+        (and of edit_params[i][member][80], converted units) replaces the member's own; NaN keeps it; where
+        ring_reset[i][member] is non-zero the member's running mean of NPP is reset too, as a death step does.
+        -> planes, final, status, diag (list of Diag per member); with rec_member = m only that member runs and the
+        fifth result is its record [n_steps][36]"""
+        fl = (C.c_int * 12)(*flags)
+        raw = np.ascontiguousarray(raw, dtype=np.float64)
+        M, n = raw.shape[0], clim.n_steps
+        steps = np.ascontiguousarray(edit_steps, dtype=np.int32)
+        pools = np.ascontiguousarray(edit_pools, dtype=np.float64).reshape(len(steps), M, 13)
+        if edit_params is not None:
+            edit_params = np.ascontiguousarray(edit_params, dtype=np.float64).reshape(len(steps), M, 80)
+        if ring_reset is not None:
+            ring_reset = np.ascontiguousarray(ring_reset, dtype=np.int32).reshape(len(steps), M)
+        planes = np.zeros((3, n, M))
+        final = np.zeros((M, NREC))
+        status = np.zeros(M, dtype=np.int32)
+        diag = (Diag * M)()
+        rec = np.zeros((n, NREC)) if rec_member is not None else None
+        m0, m1 = (0, M) if rec_member is None else (rec_member, rec_member + 1)
+        nev, evarr = self._events(events)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self.lib.sipo_run_block_edits.restype = C.c_int
+        rc = self.lib.sipo_run_block_edits(fl, vp(raw), m0, m1, M, n, vp(clim.data), vp(clim.year), vp(clim.day), nev, evarr,
+                                           vp(planes[0]), vp(planes[1]), vp(planes[2]), vp(final), vp(status), len(steps),
+                                           vp(steps), vp(pools), vp(edit_params), vp(ring_reset), vp(rec), diag)
+        assert rc == int(status[m0:m1].max()), (rc, status)
+        return (planes, final, status, list(diag)) + ((rec,) if rec is not None else ())
+
     def time_members(self, flags, raw, clim):
         fl = (C.c_int * 12)(*flags)
         raw = np.ascontiguousarray(raw, dtype=np.float64)

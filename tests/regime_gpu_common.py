@@ -1,4 +1,4 @@
-"""What tests/test_gpu_forcing_regimes.py and tests/test_gpu_parameter_regimes.py share: the flag sets and forced kernels,
+"""What tests/test_gpu_forcing_regimes.py, tests/test_gpu_parameter_regimes.py and tests/test_gpu_state_edits.py share: the flag sets and forced kernels,
 a batch set up in one call, the fuzzer's criteria (tools/fuzz_gpu.py) with the achieved figures printed first, the check
 that the forced kernel ran, and the bit-for-bit comparison of two batches' outputs."""
 import numpy as np
@@ -64,6 +64,15 @@ def judge(tag, prec, got, state, status, want, final, st, unjudged=None):
               f"pools {perr:.2e}")
         assert np.isfinite(got).all() and np.isfinite(state[ok, :13]).all(), tag
         assert share < 2e-3 and sums < 2e-3 and perr < 5e-3, tag
+
+
+def host_sums(planes, k):
+    """planes [3][T][ncol] -> [3][ceil(T / k)][ncol], added in step order like the kernel"""
+    T = planes.shape[1]
+    out = np.zeros((3, (T + k - 1) // k, planes.shape[2]))
+    for t in range(T):
+        out[:, t // k] += planes[:, t]
+    return out
 
 
 def bits(x):

@@ -127,6 +127,22 @@ def test_fuzz_forcing_regimes():
     assert "12 trials ok" in r.stdout and r.stdout.count(" forcing ") == 12
 
 
+@pytest.mark.parametrize("campaign", ["FUZZ_COOP", "FUZZ_NCYC", ""], ids=["coop", "ncyc", "all"])
+def test_fuzz_pools_scaled_between_launches(campaign):
+    """a fixed-seed slice with FUZZ_EDITS=1: at a trial's random launch cuts the carbon pools of a random subset of members
+    are scaled by a factor in [0.25, 4] through get_state / set_state, and the oracle is given the same overwrites
+    (sipo_run_block_edits); random flag sets, events, kernels and cuts as in the campaign underneath, 20 trials in all"""
+    env = dict(os.environ, FUZZ_EDITS="1", FUZZ_BOUNDED="1")
+    n = "6" if campaign else "8"
+    if campaign:
+        env[campaign] = "1"
+    r = subprocess.run([sys.executable, os.path.join(helpers.REPO, "tools", "fuzz_gpu.py"), n, "2027"],
+                       capture_output=True, text=True, timeout=900, env=env)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert n + " trials ok" in r.stdout and r.stdout.count(" edits(") == int(n)
+
+
 def test_fuzz_in_kernel_sums_on_the_cooperative_layouts():
     """a fixed-seed slice of the round-6 campaign (FUZZ_COOP=1 FUZZ_SUMS=1): every eligible trial (fp64, lean) is run again
     through sipnet_batch_run_sums -- random group lengths, launches cut at random multiples of the group -- and its sums must

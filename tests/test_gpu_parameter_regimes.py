@@ -40,7 +40,7 @@ import torch
 import sipnet_amd as sa
 from sipnet_amd.config import param_index as pi
 from tests import parameter_regimes as pr
-from tests.regime_gpu_common import COOP, KERNELS, batch, bits, family_ok, judge, outputs, same
+from tests.regime_gpu_common import COOP, KERNELS, batch, bits, family_ok, host_sums, judge, outputs, same
 
 pytestmark = pytest.mark.gpu
 DEFAULT_REGIMES = ["wide", "wide_plain", "corners", "edges", "crop_1", "crop_2", "crop_3"]
@@ -185,15 +185,6 @@ def test_regular_tiles_off_change_nothing_under_the_optional_flags(flagset, kern
     flags, members, clim = pr.flags(flagset), ref.members("edges", flagset), ref.clim()
     first = outputs(batch(flags, [clim], members, prec, kernel), zeroed=True)
     same(first, outputs(batch(flags, [clim], members, prec, kernel, sa.KOPT_NO_REGULAR_TILES), zeroed=True), "regular tiles off", ran_only=True)
-
-
-def host_sums(planes, k):
-    """planes [3][T][ncol] -> [3][ceil(T / k)][ncol], added in step order like the kernel"""
-    T = planes.shape[1]
-    out = np.zeros((3, (T + k - 1) // k, planes.shape[2]))
-    for t in range(T):
-        out[:, t // k] += planes[:, t]
-    return out
 
 
 SUM_KERNELS = [(f, p) for f in ("one_wave", "coop_lds", "coop_hbm", "coop_pair", "coop_quad") for p in (sa.F64, sa.F32_MIXED)]

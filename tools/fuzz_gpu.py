@@ -36,6 +36,11 @@ RAGGED = bool(os.environ.get("FUZZ_RAGGED"))
 FORCING = bool(os.environ.get("FUZZ_FORCING"))
 if FORCING:
     from tests import forcing_regimes      # (only this campaign needs the regimes)
+# FUZZ_EDITS=1 (on top of any of the above, or alone; a generator of its own): at the trial's launch cuts -- at least one -- every
+# carbon pool of a random subset of members is scaled by a random factor in [0.25, 4] through get_state / set_state, and the oracle
+# is given the very pools that were written (sipo_run_block_edits); lean launches, no in-kernel sums
+EDITS = bool(os.environ.get("FUZZ_EDITS"))
+CARBON_SLOTS = [0, 1, 2, 4, 6, 7, 12]     # plantWoodC plantLeafC soilC litterC coarseRootC fineRootC plantCAccountingDelta
 trials = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 12345
 only = int(sys.argv[3]) if len(sys.argv) > 3 else -1      # rerun one trial with details
@@ -165,12 +170,13 @@ for trial in range(trials):
                 members[mm, pi("soilOrgNInit")] *= float(10.0 ** -rng.uniform(0, 3))
     fast = bool(rng.random() < 0.7) or COOP_ONLY or NCYC_ONLY or OPT_ONLY
     prec = sa.F32_MIXED if (fast and rng.random() < 0.25) else sa.F64
-    runs = [oracle.run_block(flags, members, c, ev) for c in clims]
     # (rows past a site's last record: nothing is computed there, neither side is looked at)
-    want = np.concatenate([np.concatenate([r[0], np.zeros((3, T - r[0].shape[1], M))], axis=1) for r in runs], axis=2)
     valid = np.concatenate([np.repeat((np.arange(T) < tl)[:, None], M, axis=1) for tl in site_T], axis=1)
-    final = np.concatenate([r[1] for r in runs], axis=0)
-    st = np.concatenate([r[2] for r in runs])
+    if not EDITS:      # (an edited trial's oracle runs after the batch: it is given the pools the batch was given)
+        runs = [oracle.run_block(flags, members, c, ev) for c in clims]
+        want = np.concatenate([np.concatenate([r[0], np.zeros((3, T - r[0].shape[1], M))], axis=1) for r in runs], axis=2)
+        final = np.concatenate([r[1] for r in runs], axis=0)
+        st = np.concatenate([r[2] for r in runs])
     # kernel choice: default policy, or forced one-wave / HBM-ring cooperative / run-time flags
     forced, kern, kopt = "", sa.KERNEL_AUTO, 0
     r = rng.random()
@@ -218,7 +224,7 @@ for trial in range(trials):
     # a third of the trials also ask for the 44-column record and the diagnostics counters (the
     # "full" instantiations of the throughput kernels, or the strict kernel's)
     want_full = bool(rng.random() < 0.33) and kern not in (sa.KERNEL_COOP_QUAD, sa.KERNEL_COOP_NCYCLE, sa.KERNEL_COOP_NCYCLE_PAIR)    # no full-state builds of these
-    if OPT_ONLY: want_full = False       # (round 4's campaigns: lean only)
+    if OPT_ONLY or EDITS: want_full = False       # (round 4's campaigns, and the edited runs: lean only)
     if r5_full:
         want_full = True
         kopt &= ~sa.KOPT_BOUNDED_WAITS   # (the bounded-wait build has lean instantiations only)
@@ -227,7 +233,29 @@ for trial in range(trials):
         forced += " full"
     b.setup()
     cuts = sorted(set([0, T] + [int(x) for x in rng.integers(1, T, size=int(rng.integers(0, 4)))]))
-    runs_g = [b.run(a0, a1 - a0, full=want_full) for a0, a1 in zip(cuts[:-1], cuts[1:])]
+    if EDITS:
+        rng_e = np.random.default_rng(seed0 * 32452843 + trial)
+        if len(cuts) == 2 and T > 1: cuts = [0, int(rng_e.integers(1, T)), T]
+        runs_g, tables = [], []
+        for a0, a1 in zip(cuts[:-1], cuts[1:]):
+            if a0 > 0:      # scale the carbon pools of a random subset of columns; whole rows of the edited members go to the oracle
+                st_e = b.get_state()
+                sub = rng_e.random(S * M) < rng_e.uniform(0.05, 0.6)
+                st_e[np.ix_(sub, CARBON_SLOTS)] *= (0.25 * 16.0 ** rng_e.random(S * M))[sub][:, None]
+                b.set_state(st_e)
+                tables.append(np.where(sub[:, None], st_e[:, :13], np.nan))
+            runs_g.append(b.run(a0, a1 - a0))
+        runs = []
+        for sidx, c in enumerate(clims):      # (an edit at or past a shorter site's last record never reaches its members)
+            keep = [i for i, cut in enumerate(cuts[1:-1]) if cut < site_T[sidx]]
+            runs.append(oracle.run_block_edits(flags, members, c, [cuts[1 + i] for i in keep],
+                                               np.array([tables[i][sidx * M:(sidx + 1) * M] for i in keep]).reshape(len(keep), M, 13), events=ev)[:3])
+        want = np.concatenate([np.concatenate([r[0], np.zeros((3, T - r[0].shape[1], M))], axis=1) for r in runs], axis=2)
+        final = np.concatenate([r[1] for r in runs], axis=0)
+        st = np.concatenate([r[2] for r in runs])
+        forced += f" edits({len(tables)})"
+    else:
+        runs_g = [b.run(a0, a1 - a0, full=want_full) for a0, a1 in zip(cuts[:-1], cuts[1:])]
     got = torch.cat([r_[0] for r_ in runs_g], dim=1).double().cpu().numpy()
     got = np.where(valid[None], got, 0.0)
     if want_full:
@@ -235,7 +263,7 @@ for trial in range(trials):
         diag_g = b.get_diagnostics()
     b_kernel = b.last_launch()["kernel"]
     status = np.asarray(b.get_status()); state = b.get_state()
-    sums_ok = bool(os.environ.get("FUZZ_SUMS")) and not want_full and b.sums_in_kernel()
+    sums_ok = bool(os.environ.get("FUZZ_SUMS")) and not want_full and not EDITS and b.sums_in_kernel()
     b.close()
     if sums_ok:
         # round 6 (FUZZ_SUMS=1; a generator of its own): the same trial through sipnet_batch_run_sums -- every member's sums over
@@ -278,7 +306,9 @@ for trial in range(trials):
         else:
             assert np.array_equal(st_s[okc], state[okc]), f"MISMATCH (state after sums) trial {trial}"
         forced += f" sums(k={k},{len(scuts) - 1} launches,{ks.split('<')[0]})"
-    if only >= 0 and os.environ.get("FUZZ_STOP"):    # pools of one member after N steps, this kernel vs the one-wave kernel
+    if only >= 0 and os.environ.get("FUZZ_STOP") and EDITS:
+        print("           FUZZ_STOP replays a trial without its edits: not done for an edited trial")
+    elif only >= 0 and os.environ.get("FUZZ_STOP"):    # pools of one member after N steps, this kernel vs the one-wave kernel
         nstop, mdbg = int(os.environ["FUZZ_STOP"]), int(os.environ.get("FUZZ_MEMBER", "0"))
         for kk, nm in ((kern, "forced"), (sa.KERNEL_ONE_WAVE, "one-wave")):
             bb = sa.Batch(flags, S, M, prec, fast_math=fast, kernel=kk, kernel_options=kopt)
@@ -357,7 +387,7 @@ for trial in range(trials):
             print("           member", m0, "steps over 1e-9:", steps_bad[:40], "count", len(steps_bad))
             print("           at that step, all members' |dNEE|/scale:", np.round(rel[0, first, :] * 1e6, 2)[:16], "(x1e-6)")
             print("           NEE got/want around:", [(int(tt), float(got[0, tt, ok][m0]), float(want[0, tt, ok][m0])) for tt in range(first - 2, first + 20)])
-            if os.environ.get("FUZZ_REC"):   # the 44-column record of that member around that step, kernel vs oracle
+            if os.environ.get("FUZZ_REC") and not EDITS:   # (replays the trial without edits) the 44-column record of that member around that step, kernel vs oracle
                 bb = sa.Batch(flags, S, M, prec, fast_math=fast, kernel=kern, kernel_options=kopt)
                 for sidx in range(S):
                     if ev is not None: bb.set_events(sidx, ev)

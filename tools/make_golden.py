@@ -197,6 +197,85 @@ def smoke_records():
     np.savez_compressed(os.path.join(GOLD, "ref_smoke_records.npz"), **out)
 
 
+def ref_run_edits(flags, param_file, clim_file, events_file, edit_steps, edit_pools, ring_reset=None):
+    """ref_run for the file's own member with overwrites (oracle/ref_harness.c ref_run_member_edits), in a child
+    process.  -> rec[n_steps][36]"""
+    code = r"""
+import ctypes as C, numpy as np, sys, pickle
+flags, param_file, clim_file, events_file, steps, pools, reset, out_path, so = pickle.load(open(sys.argv[1],'rb'))
+ref = C.CDLL(so)
+fl = (C.c_int*12)(*flags)
+n = ref.ref_init(fl, param_file.encode(), clim_file.encode(), events_file.encode(), b"/dev/null")
+base = np.zeros(ref.ref_num_params()); ref.ref_get_base_params(base.ctypes.data_as(C.c_void_p))
+out = np.zeros((n, ref.ref_rec_len()))
+steps = np.ascontiguousarray(steps, dtype=np.int32); pools = np.ascontiguousarray(pools, dtype=np.float64)
+reset = None if reset is None else np.ascontiguousarray(reset, dtype=np.int32)
+assert ref.ref_run_member_edits(base.ctypes.data_as(C.c_void_p), len(steps), steps.ctypes.data_as(C.c_void_p),
+                                pools.ctypes.data_as(C.c_void_p), None if reset is None else reset.ctypes.data_as(C.c_void_p),
+                                out.ctypes.data_as(C.c_void_p)) == n
+np.save(out_path, out)
+"""
+    import pickle
+    tmp = tempfile.mkdtemp(prefix="mkgold_")
+    out_path, job = os.path.join(tmp, "out.npy"), os.path.join(tmp, "job.pkl")
+    pickle.dump((list(flags), param_file, clim_file, events_file, list(edit_steps), np.asarray(edit_pools),
+                 None if ring_reset is None else list(ring_reset), out_path, REF_SO),
+                open(job, "wb"))
+    subprocess.check_call([sys.executable, "-c", code, job])
+    out = np.load(out_path)
+    shutil.rmtree(tmp)
+    return out
+
+
+EDIT_RECORDS = 2000
+# (case, edit steps): an emptied stand, its restoration, a third edit.  russell_2's second edit falls on the first record
+# of 2016 day 90, which carries its first fertiliser event
+EDIT_CASES = [("niwot", (301, 900, 1501)), ("russell_2", (300, 712, 1500)), ("russell_3", (333, 801, 1502))]
+
+
+def edit_records():
+    """tests/golden/ref_edit_records.npz: the real reference's step loop with `envi` overwritten between records
+    (ref_run_member_edits), one member per case over its first 2 000 records, for tests/test_oracle_edits.py to hold
+    sipo_run_block_edits against.  Stored: the edit table, and the records at the edit steps +- 2 and at the last step; and
+    the same once more with the running mean of NPP reset at the emptying (<case>_rec_reset), as a death step would."""
+    import sipnet_amd as sa
+    out = {}
+    for case, steps in EDIT_CASES:
+        s = os.path.join(REF, "tests", "smoke", case)
+        cfg = sa.read_config(os.path.join(s, "sipnet.in"))
+        flags = [cfg[n] for n in sa.FLAG_NAMES]
+        tmp = tempfile.mkdtemp(prefix="mkgold_edit_")
+        lines = open(os.path.join(s, "sipnet.clim")).readlines()
+        clim_path, ev_path = os.path.join(tmp, "cut.clim"), os.path.join(tmp, "events.in")
+        open(clim_path, "w").writelines(lines[:EDIT_RECORDS])
+        ycol = 1 if case == "niwot" else 0
+        open(ev_path, "w").write(split_events(open(os.path.join(s, "events.in")).read(), lines, EDIT_RECORDS, ycol)[0])
+        args = (flags, os.path.join(s, "sipnet.param"), clim_path, ev_path)
+        nan = np.full(13, np.nan)
+        plain = ref_run_edits(*args, [], np.zeros((0, 13)))
+        assert plain.shape == (EDIT_RECORDS, NREC)
+        if case == "russell_2":
+            y, d = (int(v) for v in lines[steps[1]].split()[:2])
+            y0, d0 = (int(v) for v in lines[steps[1] - 1].split()[:2])
+            assert (y, d) == (2016, 90) and (y0, d0) == (2016, 89)
+        emptied, restored, third = nan.copy(), plain[steps[0] - 1, 14:27].copy(), nan.copy()
+        emptied[[0, 6, 7]] = 0.0                                  # plantWoodC, coarseRootC, fineRootC
+        emptied[3] = 2.0 * plain[steps[0] - 1, 17]                # soilWater doubled
+        third[1], third[5] = 0.0, 30.0                            # plantLeafC 0, snow 30
+        third[[0, 2]] = plain[steps[2] - 1, [14, 16]] * [0.25, 4.0]
+        pools = np.stack([emptied, restored, third])
+        rec = ref_run_edits(*args, steps, pools)
+        rec_reset = ref_run_edits(*args, steps, pools, [1, 0, 0])
+        shutil.rmtree(tmp)
+        idx = np.array(sorted({t + k for t in steps for k in range(-2, 3)} | {EDIT_RECORDS - 1}), dtype=np.int32)
+        assert rec[steps[0], 14] == 0.0 and rec[steps[1], 14] > 1.0 and not np.array_equal(rec[idx], plain[idx])
+        out[f"{case}_steps"], out[f"{case}_pools"] = np.array(steps, dtype=np.int32), pools
+        out[f"{case}_idx"], out[f"{case}_rec"], out[f"{case}_rec_reset"] = idx, rec[idx], rec_reset[idx]
+        assert rec_reset[steps[0], 32] == 0.0 and rec[steps[0], 32] != 0.0 and not np.array_equal(rec_reset[-1], rec[-1])
+        print("edit records", case, steps, "kept", len(idx), "wood after each edit", rec[list(steps), 14])
+    np.savez_compressed(os.path.join(GOLD, "ref_edit_records.npz"), **out)
+
+
 def special_members(base):
     """A small ensemble that walks the rare branches: phenology, mortality, drought."""
     import sipnet_amd as sa
@@ -480,6 +559,7 @@ if __name__ == "__main__":
     subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "oracle"), "ref", "oracle"])
     copy_smoke()
     smoke_records()
+    edit_records()
     synthetic()
     warning_counts()
     restart_cases()
