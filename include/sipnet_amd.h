@@ -647,6 +647,65 @@ int sipnet_batch_pf_resample_sites(sipnet_batch *b, double *d_logw, const double
                                    const double *d_ess_min, int32_t with_params, int32_t *d_ancestors,
                                    int64_t *d_fixed_weights, int64_t *d_site_total, double *d_ess, void *hip_stream);
 
+/* ---- particle rejuvenation: Liu-West parameter jitter and pool noise -----------------------------------------------
+ * SIPNET is deterministic: two copies of a resampled particle stay identical for every later step, so a filter whose
+ * particles carry their parameters only ever loses distinct parameter sets.  This call gives every copy its own values
+ * again: the kernel-shrinkage move of Liu & West (2001) for listed parameter rows, additive noise for pools (which also
+ * serves an EnKF as additive model error).  One pass over rows the batch already holds; nothing is drawn on the host.
+ * The draw is counter-based and part of the contract: Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53,
+ * 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with key = {seed & 0xffffffff, seed >> 32} and ctr = {member, stream,
+ * block, draw}: member the column's index inside its site, stream d_stream[s] (NULL: s), draw the caller's cycle number.
+ * Of the output words x0..x3, u = (x0 + 0.5) 2^-32 and v = (x1 + 0.5) 2^-32 (exact in a double), r = sqrt(-2 ln u),
+ * z0 = r cos(2 pi v), z1 = r sin(2 pi v); z2 and z3 from x2, x3 the same way; |z| <= sqrt(2 ln 2^33) = 6.764.  Listed
+ * parameter k (its position in params) takes normal k & 3 of block k >> 2; state slot p takes normal p & 3 of block
+ * 4 + (p >> 2).  The device's normals are within a few ulp of r of the host's (tests: 8 x 2^-53 r).
+ * sipnet_philox4x32_10, sipnet_rejuvenate_normals: host only, no device: the generator and the four normals of a block.
+ * Sites: a site's live members are the analyses' (state[29] == 0, site plan status OK; n of them).  d_site_total (what
+ * sipnet_batch_pf_resample_sites or _analysis_sites left; NULL: every site) selects the sites whose total is > 0, the ones
+ * that were resampled.
+ * Parameters (params: sipnet_batch_enkf_analysis_joint's descriptors, the rows sipnet_enkf_params_check refuses are
+ * refused, bounds in file units), in converted units: per listed row m the mean and sd = sqrt(sum (x - m)^2 / (n - 1))
+ * over the live members, a = shrink[s], h = sqrt((1 - a)(1 + a)), x' = (m + a (x - m)) + (h sd) z; then one reflection
+ * about a violated bound (lo + (lo - x') or hi - (x' - hi)), then a clip into [lo, hi].  A site whose a is exactly 1
+ * leaves its parameter rows bit-identical.  (With a = (3 delta - 1) / (2 delta), Liu & West's discount delta, the move
+ * keeps the site's mean and variance in expectation.)
+ * Pools: a slot of pool_mask with q = pool_sd[s][p] > 0 becomes x + q z, clipped at 0 from below except
+ * plantCAccountingDelta; a slot with q == 0 stays bit-identical.
+ * A member keeps everything, pools and parameters, when a new value is not finite, when hasSufficientBiomass of the
+ * result fails, or when an allocation (leaf, wood, fineRoot) is listed, the site's a is not 1 and the result fails
+ * ensureAllocation's test.  Otherwise its rows and slots are written, and psnTMax / coarseRootAllocation are rewritten
+ * from the rows they derive from, as in the joint analysis.
+ * site_info[s] = {code, rows + slots perturbed (the listed rows unless a == 1, the masked slots with q > 0), live members,
+ * members kept}.  Code 1 done; 0 fewer than 2 live members; -2 bad input (a not finite or outside (0, 1], a masked pool_sd
+ * not finite or < 0); -3 not selected.  Sites whose code is not 1 are untouched and report {code, 0, live members, 0}.
+ * d_site_info given: nothing is synchronised.  NULL: shrink, pool_sd and the totals are read back first, and a -2 site
+ * gives SIPNET_ERR_BAD_ARGUMENT naming it before anything is written.
+ * SIPNET_ERR_BAD_ARGUMENT before any launch (sipnet_last_error says why): the parameter checks; n_params > 0 without
+ * d_shrink; a mask outside bits 0..12 or without d_pool_sd; nothing to do (n_params == 0 and mask 0); a NULL batch;
+ * ncol > 4 194 304; a batch that was not set up; a batch connected by sipnet_batch_pf_connect.
+ * Bookkeeping as the EnKF analyses: pending set_params rows are flushed first; with n_params > 0 a batch whose parameters
+ * are behind a resampling's index first gets every column its own rows; armed or left log-weights are dropped; the
+ * records-done count is kept.  Bit-identical afterwards: every row and slot not listed, every column that is not live,
+ * every site whose code is not 1, rings, status, the caller's log-weights.
+ * A site's result depends on its own columns, seed, draw, its stream and its shrink and pool_sd rows -- not on n_sites,
+ * not (with d_stream) on where the site sits in the batch, and not on the path: one workgroup per site up to 256
+ * members, else (and under SIPNET_KOPT_PF_MULTI_LAUNCH) per-chunk launches, the same bits; sipnet_batch_pf_info's fused
+ * says which ran.  No atomic, no grid barrier, no spin.
+ * Out of scope: weighted (pre-resampling) moments, jitter on a transformed scale, correlated kernels, connected batches. */
+#define SIPNET_REJUVENATE_INFO_WORDS 4
+enum sipnet_rejuvenate_code {
+  SIPNET_REJUVENATE_DONE = 1, SIPNET_REJUVENATE_TOO_FEW = 0, SIPNET_REJUVENATE_BAD_INPUT = -2,
+  SIPNET_REJUVENATE_NOT_SELECTED = -3
+};
+void sipnet_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+void sipnet_rejuvenate_normals(uint64_t seed, uint32_t draw, uint32_t stream, uint32_t member, uint32_t block,
+                               double z[4]);
+struct sipnet_enkf_param;
+int sipnet_batch_pf_rejuvenate(sipnet_batch *b, int32_t n_params, const struct sipnet_enkf_param *params /* HOST */,
+                               const double *d_shrink, int32_t pool_mask, const double *d_pool_sd, uint64_t seed,
+                               uint32_t draw, const uint32_t *d_stream, const int64_t *d_site_total,
+                               int32_t *d_site_info, void *hip_stream);
+
 /* ---- ensemble Kalman filter analysis of the member pools, a filter per site ------------------------------------
  * Observation operators (h of one member, from its forecast state, planes and converted parameters):
  *   POOLS: h = scale * (sum of the pools in pool_mask) / (param >= 0 ? prm[param] : 1)

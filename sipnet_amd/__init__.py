@@ -17,7 +17,9 @@ from .config import (DEFAULT_FLAGS, FLAG_NAMES, PARAM_NAMES, POOLS, enkf_param, 
 from .io import (ClimTable, format_out_header, format_out_row, read_clim, read_events,
                  read_params, read_restart, check_restart, write_debug_logs, write_events_out, write_out,
                  write_restart)
-from .batch import Batch, PlaneQuantiles, debug_live_bytes, loglik_term, quantile_lds_members, quantile_positions
+from .batch import (Batch, PlaneQuantiles, debug_live_bytes, liu_west_shrink, loglik_term, philox4x32_10, quantile_lds_members,
+                    quantile_positions, rejuvenate_normals)
+from ._lib import (REJUVENATE_BAD_INPUT, REJUVENATE_DONE, REJUVENATE_INFO_WORDS, REJUVENATE_NOT_SELECTED, REJUVENATE_TOO_FEW)
 from .enkf_local import ENKF_BLOCK_MAX_ROWS, EnkfLocalization, enkf_local_rows, enkf_local_schedule, gaspari_cohn
 
 __all__ = [
@@ -28,5 +30,7 @@ __all__ = [
     "KERNEL_AUTO", "KERNEL_ONE_WAVE", "KERNEL_COOP_LDS", "KERNEL_COOP_HBM", "KERNEL_COOP_PAIR", "KERNEL_COOP_QUAD", "KERNEL_COOP_NCYCLE", "KERNEL_COOP_NCYCLE_PAIR", "KERNEL_STRICT",
     "KOPT_ONE_WAVE_PER_SIMD", "KOPT_RUNTIME_FLAGS", "KOPT_FULL_STATE", "KOPT_NO_REGULAR_TILES", "KOPT_STATS_IN_KERNEL", "KOPT_BOUNDED_WAITS", "KOPT_WAIT_SELFTEST", "KOPT_HOST_PLAN", "KOPT_DEVICE_PLAN", "KOPT_PF_MULTI_LAUNCH", "KOPT_PF_MOVE_PARAMS", "PF_VOID_TOTAL",
     "NPARAMS", "NFLAGS", "NCLIM", "NREC", "NSTATE", "RING_SLOTS",
+    "philox4x32_10", "rejuvenate_normals", "liu_west_shrink", "REJUVENATE_INFO_WORDS", "REJUVENATE_DONE", "REJUVENATE_TOO_FEW",
+    "REJUVENATE_BAD_INPUT", "REJUVENATE_NOT_SELECTED",
     "loglik_term", "LOGLIK_GAUSS", "LOGLIK_LAPLACE", "LOGLIK_MAX_TERMS", "LOGLIK_TILE_ROWS",
 ]

@@ -65,6 +65,11 @@ LOGLIK_GAUSS, LOGLIK_LAPLACE = 0, 1   # enum sipnet_loglik_kind
 LOGLIK_TILE_ROWS, LOGLIK_MAX_TERMS = 256, 8   # SIPNET_LOGLIK_TILE_ROWS, SIPNET_LOGLIK_MAX_TERMS
 
 
+# sipnet_batch_pf_rejuvenate: site_info[s] = {code, rows + slots perturbed, live members, members kept}; the codes
+REJUVENATE_INFO_WORDS = 4
+REJUVENATE_DONE, REJUVENATE_TOO_FEW, REJUVENATE_BAD_INPUT, REJUVENATE_NOT_SELECTED = 1, 0, -2, -3
+
+
 class LoglikTerm(C.Structure):
     """struct sipnet_loglik_term: one observed series of sipnet_batch_series_loglik (device arrays); held: the tensors the
     pointers point into"""
@@ -208,6 +213,9 @@ SIGNATURES = {
     "sipnet_batch_series_loglik": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                              _P, _P]),
     "sipnet_batch_pf_resample_sites": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "sipnet_philox4x32_10": (None, [_P, _P, _P]),
+    "sipnet_rejuvenate_normals": (None, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
+    "sipnet_batch_pf_rejuvenate": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
     "sipnet_batch_enkf_analysis_sites": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
                                                    _P, _P, _P, _P]),
     "sipnet_enkf_params_check": (C.c_int, [C.c_int32, _P, _P, _P]),

@@ -12,7 +12,7 @@ import weakref
 import numpy as np
 
 from ._lib import (F64, KERNEL_AUTO, LOGLIK_GAUSS, LOGLIK_LAPLACE, LOGLIK_MAX_TERMS, NDBG, NPARAMS, NREC, NSTATE, RING_SLOTS,
-                   EnkfObs, EnkfParam, EnkfSeries, Event, LaunchInfo, LoglikTerm, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
+                   REJUVENATE_INFO_WORDS, EnkfObs, EnkfParam, EnkfSeries, Event, LaunchInfo, LoglikTerm, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
 from .config import pool_mask
 from .enkf_local import EnkfLocalization
 
@@ -42,6 +42,31 @@ def quantile_positions(n, q):
     g = np.zeros(qs.size)
     check(lib().sipnet_quantile_positions(int(n), int(qs.size), ptr(qs), ptr(lo), ptr(g)), "quantile_positions")
     return lo, g
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 (sipnet_philox4x32_10, host only): counter (4 x uint32), key (2 x uint32) -> uint32 [4]"""
+    c = np.ascontiguousarray(np.asarray(ctr, dtype=np.uint32).reshape(4))
+    k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+    out = np.zeros(4, dtype=np.uint32)
+    lib().sipnet_philox4x32_10(ptr(c), ptr(k), ptr(out))
+    return out
+
+
+def rejuvenate_normals(seed, draw, stream, member, block):
+    """the four normals Batch.pf_rejuvenate gives one block of one member (sipnet_rejuvenate_normals, host only): listed
+    parameter k takes normal k & 3 of block k >> 2, state slot p normal p & 3 of block 4 + (p >> 2); member: the column's
+    index inside its site; stream: the site's stream -> float64 [4]"""
+    z = np.zeros(4)
+    lib().sipnet_rejuvenate_normals(int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff, int(stream) & 0xffffffff,
+                                    int(member) & 0xffffffff, int(block) & 0xffffffff, ptr(z))
+    return z
+
+
+def liu_west_shrink(delta):
+    """the shrink factor a = (3 delta - 1) / (2 delta) of Liu & West's discount delta in (1/3, 1] (0.95 .. 0.99 is usual);
+    Batch.pf_rejuvenate's kernel then has h^2 = 1 - a^2"""
+    return (3.0 * delta - 1.0) / (2.0 * delta)
 
 
 def loglik_term(series, obs, sd, kind=LOGLIK_GAUSS, scale=1.0, sum_steps=1):
@@ -517,6 +542,38 @@ class Batch:
         check(self.L.sipnet_batch_pf_resample_sites(self.h, ptr(logw), ptr(u0), ptr(beta), ptr(ess_min), int(with_params),
                                                     ptr(anc), ptr(fixed), ptr(total_out), ptr(ess_out), self._stream()), what)
         return (anc, fixed) if return_fixed else anc
+
+    def pf_rejuvenate(self, params, shrink, pools=None, pool_sd=None, seed=0, draw=0, streams=None, site_total=None,
+                      info_out=None):
+        """particle rejuvenation after a resampling (sipnet_batch_pf_rejuvenate): the Liu-West move of the listed parameter
+        rows about the site's mean, x' = m + a (x - m) + sqrt(1 - a^2) sd z, reflected and clipped into the bounds, and
+        additive noise q z on pools; z from the counter-based generator (sa.rejuvenate_normals), nothing drawn on the host.
+        params: sa.enkf_param(name, lo, hi), at most sa.ENKF_MAX_PARAMS (() for none); shrink: a in (0, 1] per site
+        (sa.liu_west_shrink(delta); 1 leaves the rows as they are; None with no params); pools: the pool names that get
+        noise, pool_sd: [n_sites][13] their sds by state slot (0: the slot stays); seed, draw: the generator's key and the
+        cycle number; streams: a uint32 per site that names its random stream (None: the site's index); site_total: int64
+        device tensor [n_sites], pf_resample_sites' total_out -- only sites with a total > 0 (the resampled ones) are
+        touched (None: every site); info_out: int32 device tensor [n_sites][4] for {code, rows + slots perturbed, live
+        members, members kept} (no host synchronisation); without it the call checks shrink and pool_sd first and raises
+        before anything is written."""
+        t = self._torch
+        what = "pf_rejuvenate"
+        prm = list(params)
+        mask = pool_mask(pools) if pools else 0
+        shrink = self._upload(what, shrink, self.n_sites, "shrink")
+        pool_sd = self._upload(what, pool_sd, self.n_sites * 13, "pool_sd")
+        if streams is not None:
+            streams = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
+            if streams.size != self.n_sites:
+                raise ValueError(f"{what}: streams needs {self.n_sites} values, got {streams.size}")
+            streams = t.from_numpy(streams.view(np.int32)).to(self.device)
+        if site_total is not None and not _dense(site_total, t.int64, self.n_sites):
+            raise ValueError(f"{what}: site_total must be a contiguous int64 device tensor of {self.n_sites} values")
+        if info_out is not None and not _dense(info_out, t.int32, REJUVENATE_INFO_WORDS * self.n_sites):
+            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x {REJUVENATE_INFO_WORDS}")
+        check(self.L.sipnet_batch_pf_rejuvenate(self.h, len(prm), c_array(EnkfParam, prm), ptr(shrink), mask, ptr(pool_sd),
+                                                int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff, ptr(streams), ptr(site_total),
+                                                ptr(info_out), self._stream()), what)
 
     def enkf_analysis_sites(self, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
         """an ensemble Kalman filter analysis of the member pools, every site a filter of its own, one library call

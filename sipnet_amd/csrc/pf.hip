@@ -26,12 +26,16 @@
 //                    three launches; both from a plane and an observation per site, or from log-weights the caller gives
 //   pf_series.inc    every member's log-likelihood of a window's series against observed series with gaps: LoglikArgs,
 //                    loglikKernel (one launch), loglikTileKernel + loglikCombineKernel (tiles' sums, then their sum in order)
+//   pf_rejuvenate.inc  what gives resampled copies their own values again: the counter-based normals (Philox4x32-10, Box-Muller),
+//                    RejArgs, rejMember (the Liu-West move of parameter rows, pool noise, the limits), rejGroupKernel (a workgroup
+//                    per site) and the split path's rejChunkKernel, rejSiteKernel, rejApplyKernel, rejInfoKernel
 //
 // The host side runs three filters.  One batch (sipnet_batch_pf_analysis): the PfPre match (takePfPre), the one launch
 // (fusedSetup + the one-batch fields) or the launches of their own, the synchronous check (checkTotal), the resampling
 // gather (resampleColumns: settleParams, recvMapOf, launchGatherMember, adoptSpares, widenExponents).  Many sites
 // (sipnet_batch_pf_analysis_sites, and sipnet_batch_pf_resample_sites from given log-weights): the arguments, sitesLaunch,
-// sitesCheck, resampleColumns.  Series weights (sipnet_batch_series_loglik): loglikCheck, the path, the launches.  Across ranks by peer reads:
+// sitesCheck, resampleColumns.  Series weights (sipnet_batch_series_loglik): loglikCheck, the path, the launches.  Rejuvenation (sipnet_batch_pf_rejuvenate): the refusals,
+// rejCheck, the bookkeeping of an analysis that writes parameters, rejScratch, the path, the launches.  Across ranks by peer reads:
 // sipnet_batch_pf_publish, _connect (own descriptor, closePeers, mapPeer, fillBank and the crossing counter) and
 // _resample_peers (peerTable, peerAncestors: fusedSetup + the gathered fields or launches, peerGather, adoptSpares).
 #include <hip/hip_runtime.h>
@@ -59,6 +63,7 @@ namespace {
 #include "pf_plan.inc"
 #include "pf_sites.inc"
 #include "pf_series.inc"
+#include "pf_rejuvenate.inc"
 
 }  // namespace
 }  // namespace sipnet
@@ -218,6 +223,7 @@ struct PfScratch {
   DevBuf<unsigned char> d_sites;        // sipnet_batch_pf_analysis_sites (sitesScratchFor), bytes
   DevBuf<double> d_loglik;              // sipnet_batch_series_loglik, path 2: [terms' tiles][ncol] the tiles' sums
   DevBuf<int32_t> d_loglikUsed;         // ... and [n_sites][terms' tiles] the tiles' rows used
+  DevBuf<unsigned char> d_rejuv;        // sipnet_batch_pf_rejuvenate (rejScratch), bytes
 };
 namespace {
 constexpr int kMaxParts = 256;
@@ -970,6 +976,140 @@ int sipnet_batch_series_loglik(sipnet_batch* b, int32_t n_terms, const sipnet_lo
   hipLaunchKernelGGL(loglikCombineKernel, dim3((unsigned)groups), dim3(256), 0, stream, a);
   HIP_TRY(hipGetLastError());
   return SIPNET_OK;
+}
+
+// ---- rejuvenation ----------------------------------------------------------------------------------------------------
+void sipnet_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out);
+}
+
+void sipnet_rejuvenate_normals(uint64_t seed, uint32_t draw, uint32_t stream, uint32_t member, uint32_t block, double z[4]) {
+  rejNormals((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, stream, member, block, true, z);
+}
+
+static int rejRefuse(const std::string& why) {
+  setError("sipnet_batch_pf_rejuvenate: " + why);
+  return SIPNET_ERR_BAD_ARGUMENT;
+}
+// the synchronous form's check: shrink, pool_sd and the totals read back, the first selected site with bad input named
+static int rejCheck(const sipnet_batch* b, const RejArgs& a, hipStream_t stream) {
+  const size_t nSites = (size_t)b->n_sites;
+  std::vector<double> shrink(a.nPrm > 0 ? nSites : 0), sd(a.mask ? nSites * kRejPools : 0);
+  std::vector<int64_t> total(a.siteTotal ? nSites : 0);
+  if (a.nPrm > 0) HIP_TRY(hipMemcpyAsync(shrink.data(), a.shrink, shrink.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (a.mask) HIP_TRY(hipMemcpyAsync(sd.data(), a.poolSd, sd.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (a.siteTotal) HIP_TRY(hipMemcpyAsync(total.data(), a.siteTotal, total.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (size_t s = 0; s < nSites; s++)
+    if (rejSiteInputs(shrink.data(), sd.data(), a.siteTotal ? total.data() : nullptr, a.nPrm, a.mask, (int64_t)s) == kRejBadInput)
+      return rejRefuse("site " + std::to_string(s) + ": bad input (the shrink factor must lie in (0, 1]; a masked pool sd must be "
+                       "finite and >= 0); nothing was written");
+  return SIPNET_OK;
+}
+// the batch's scratch block carved: the split path's chunk sums and site statistics, the info (a.info is d_site_info where
+// given), the split path's counts and codes
+static int rejScratch(sipnet_batch* b, PfScratch& sc, RejArgs& a, int32_t* d_site_info, bool split) {
+  const size_t nSites = (size_t)b->n_sites, nCnt = split ? nSites * (size_t)a.nCh : 0;
+  const size_t nPart = nCnt * kRejPrm, nStat = split ? nSites * 2 * kRejPrm : 0;
+  const size_t nInt = nSites * 4 + 2 * nCnt + (split ? 2 * nSites : 0);
+  const size_t bytes = (nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t);
+  if (sc.d_rejuv.capacity() < bytes) {
+    RC_TRY(waitIdle(b));   // (the old block may still be read by a launch in flight)
+    RC_TRY(sc.d_rejuv.reserve(bytes));
+  }
+  a.part = (double*)sc.d_rejuv.get();
+  a.stat = a.part + nPart;
+  int32_t* ints = (int32_t*)(a.stat + nStat);
+  a.info = d_site_info ? d_site_info : ints;
+  a.cnt = ints + nSites * 4;
+  a.kept = a.cnt + nCnt;
+  a.site = a.kept + nCnt;
+  return SIPNET_OK;
+}
+
+int sipnet_batch_pf_rejuvenate(sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, const double* d_shrink,
+                               int32_t pool_mask, const double* d_pool_sd, uint64_t seed, uint32_t draw,
+                               const uint32_t* d_stream, const int64_t* d_site_total, int32_t* d_site_info, void* hip_stream) {
+  RejArgs a{};
+  if (sipnet_enkf_params_check(n_params, params, a.lo, a.hi) != SIPNET_OK) {   // (the joint analysis's rows and bounds)
+    const std::string why = sipnet_last_error(), from = "sipnet_enkf_params_check: ";
+    return rejRefuse(why.compare(0, from.size(), from) == 0 ? why.substr(from.size()) : why);
+  }
+  if (n_params > 0 && !d_shrink) return rejRefuse("n_params > 0 needs d_shrink");
+  if (pool_mask & ~((1 << kRejPools) - 1)) return rejRefuse("pool_mask must name pools 0..12");
+  if (pool_mask && !d_pool_sd) return rejRefuse("a pool_mask needs d_pool_sd");
+  if (n_params == 0 && pool_mask == 0) return rejRefuse("nothing to do (n_params == 0 and pool_mask == 0)");
+  if (!b) return rejRefuse("a NULL batch");
+  if (b->ncol > (int64_t)1 << 22) return rejRefuse("at most 4194304 columns");
+  if (b->planDirty) return rejRefuse("needs a batch that was set up (sipnet_batch_setup): the members' status is read");
+  if (b->pfPeers) return rejRefuse("this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
+  int rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int64_t M = b->n_members, nSites = b->n_sites;
+  a.nPrm = n_params;
+  a.mask = pool_mask;
+  a.leaf = a.wood = a.fineRoot = a.opt = a.tmin = -1;
+  for (int k = 0; k < n_params; k++) {
+    const int p = params[k].index;
+    a.prmRow[k] = p;
+    if (p == SP_leafAllocation) a.leaf = k;
+    if (p == SP_woodAllocation) a.wood = k;
+    if (p == SP_fineRootAllocation) a.fineRoot = k;
+    if (p == SP_psnTOpt) a.opt = k;
+    if (p == SP_psnTMin) a.tmin = k;
+  }
+  a.shrink = d_shrink;
+  a.poolSd = d_pool_sd;
+  a.key0 = (uint32_t)(seed & 0xffffffffu);
+  a.key1 = (uint32_t)(seed >> 32);
+  a.draw = draw;
+  a.stream = d_stream;
+  a.siteTotal = d_site_total;
+  a.ncol = b->ncol;
+  a.M = M;
+  a.nCh = (int32_t)((M + 255) / 256);
+  if (!d_site_info) {
+    rc = rejCheck(b, a, stream);
+    if (rc) return rc;
+  }
+  // the bookkeeping of an analysis that writes state and parameters (sipnet_batch_enkf_analysis_joint's)
+  b->pfPre.valid = false;
+  b->pfArm.set = false;
+  rc = orderBehindBusy(b, stream);
+  if (rc) return rc;
+  rc = flushParams(b, stream);
+  if (rc) return rc;
+  if (n_params > 0) {
+    rc = materializeParams(b, stream);   // (every column its own rows: the move writes them)
+    if (rc) return rc;
+  }
+  a.state = b->d_state;
+  a.prm = b->d_prm;
+  a.siteStatus = b->d_siteStatus;
+  // one workgroup per site when the sites are one chunk each, else the per-chunk launches (pf_rejuvenate.inc says why)
+  const bool split = a.nCh > 1 || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
+  rc = rejScratch(b, scratchOf(b), a, d_site_info, split);
+  if (rc) return rc;
+  const dim3 sites((unsigned)nSites), chunks((unsigned)nSites, (unsigned)a.nCh);
+  if (!split) {
+    hipLaunchKernelGGL(rejGroupKernel, sites, dim3(256), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL(rejChunkKernel, chunks, dim3(256), 0, stream, a, 0);
+    hipLaunchKernelGGL(rejSiteKernel, sites, dim3(256), 0, stream, a, 0);
+    if (n_params > 0) {
+      hipLaunchKernelGGL(rejChunkKernel, chunks, dim3(256), 0, stream, a, 1);
+      hipLaunchKernelGGL(rejSiteKernel, sites, dim3(256), 0, stream, a, 1);
+    }
+    hipLaunchKernelGGL(rejApplyKernel, chunks, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(rejInfoKernel, sites, dim3(256), 0, stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  b->pfInfo.fused = split ? 0 : 1;
+  b->pfInfo.grid = split ? 0 : (int32_t)nSites;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = b->ncol;
+  return markBusy(b, stream);
 }
 
 }  // extern "C"

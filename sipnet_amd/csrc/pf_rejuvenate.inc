@@ -1,0 +1,391 @@
+// pf_rejuvenate.inc -- particle rejuvenation after a resampling (sipnet_batch_pf_rejuvenate): the Liu & West (2001) kernel-
+// shrinkage move of some of a site's parameter rows, and additive noise on pools.  SIPNET is deterministic, so two copies of
+// a resampled particle stay identical for ever; this pass gives every copy its own draw again.
+//
+// The draw is COUNTER-BASED (Philox4x32-10, Salmon et al. 2011): no generator state anywhere, nothing drawn on the host.  A
+// normal is a function of (seed, draw, the site's stream, the member's index inside its site, a block number) alone, so the
+// result depends neither on the number of sites, nor on the path, nor on the launch geometry.  One Philox call gives four
+// words, two Box-Muller pairs, four normals: the four rows of one block of a member.
+//
+// Two paths with the same bits.  rejGroupKernel: one workgroup per site, for sites of one chunk (at most 256 members) -- the
+// moments of the listed rows over the site's live members (the means, then the centred sums), then the draw and the limits
+// in a second sweep; the rows are staged in LDS, so HBM is read once.  The split path for larger sites (and under
+// SIPNET_KOPT_PF_MULTI_LAUNCH): rejChunkKernel (a chunk's sums) | rejSiteKernel (the site's, in chunk order) twice -- sums,
+// centred sums --, then rejApplyKernel | rejInfoKernel.  The draw is arithmetic (a double logarithm, square root, sine and
+// cosine per pair of normals), so what counts is how many waves work at it: a workgroup that walked a whole site of several
+// chunks was measured 1.3 to 8 x slower than the per-chunk launches (NOTES.md).  The sums' order is the same in both and
+// depends on M only: the 256 columns of a chunk by an xor butterfly inside each wave, the four waves in order, the chunks in
+// order from 0.0.  No atomic, no grid barrier, no spin.
+constexpr int kRejPrm = SIPNET_ENKF_MAX_PARAMS;   // listed parameter rows at most
+constexpr int kRejPools = 13;                     // state slots 0..12
+constexpr int kRejDone = SIPNET_REJUVENATE_DONE, kRejTooFew = SIPNET_REJUVENATE_TOO_FEW, kRejBadInput = SIPNET_REJUVENATE_BAD_INPUT,
+              kRejNotSelected = SIPNET_REJUVENATE_NOT_SELECTED;
+constexpr double kRejTiny = 0.000001;             // TINY, common/util.h
+
+// Philox4x32-10: ten rounds of two 32 x 32 -> 64 bit products, the key bumped by the Weyl constants between rounds
+__host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t out[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0;
+  out[1] = c1;
+  out[2] = c2;
+  out[3] = c3;
+}
+// two normals from two words: u = (xa + 0.5) 2^-32 and v = (xb + 0.5) 2^-32 (exact), r = sqrt(-2 ln u), r cos(2 pi v) and
+// r sin(2 pi v).  The angle is reduced exactly -- 2 v = k / 2 + f, |f| <= 1/4 -- before pi enters, so its rounding costs a
+// fraction of an ulp instead of 2 pi of them.
+__host__ __device__ inline void boxMuller(uint32_t xa, uint32_t xb, double* za, double* zb) {
+  const double u = ((double)xa + 0.5) * 0x1p-32, v = ((double)xb + 0.5) * 0x1p-32;
+  const double r = sqrt(-2.0 * log(u));
+  const int k = (int)rint(4.0 * v);
+  const double f = 2.0 * v - 0.5 * (double)k;
+#ifdef __HIP_DEVICE_COMPILE__
+  const double sf = sinpi(f), cf = cospi(f);
+#else
+  const double sf = sin(3.14159265358979323846 * f), cf = cos(3.14159265358979323846 * f);
+#endif
+  const double c = (k & 1) ? ((k & 2) ? sf : -sf) : ((k & 2) ? -cf : cf);
+  const double s = (k & 1) ? ((k & 2) ? -cf : cf) : ((k & 2) ? -sf : sf);
+  *za = r * c;
+  *zb = r * s;
+}
+// the four normals of one block of one member: ctr = {member, stream, block, draw}
+__host__ __device__ inline void rejNormals(uint32_t k0, uint32_t k1, uint32_t draw, uint32_t stream, uint32_t member,
+                                           uint32_t block, bool second, double z[4]) {
+  uint32_t x[4];
+  philox4x32_10(member, stream, block, draw, k0, k1, x);
+  boxMuller(x[0], x[1], &z[0], &z[1]);
+  if (second) boxMuller(x[2], x[3], &z[2], &z[3]);
+}
+
+struct RejArgs {
+  int32_t nPrm, mask;
+  int32_t prmRow[kRejPrm];                 // the listed rows of prm, in the caller's order
+  double lo[kRejPrm], hi[kRejPrm];         // their bounds, converted units
+  int32_t leaf, wood, fineRoot, opt, tmin; // where leafAllocation .. psnTMin are among the listed rows, or -1
+  const double* shrink;                    // [n_sites] a, or null (nPrm == 0)
+  const double* poolSd;                    // [n_sites][13], or null (mask == 0)
+  uint32_t key0, key1, draw;
+  const uint32_t* stream;                  // [n_sites] or null: the site's index
+  const int64_t* siteTotal;                // [n_sites] or null: every site
+  int32_t* info;                           // [n_sites][4]
+  double* state;                           // [NSTATE][ncol]
+  double* prm;                             // [NPARAMS][ncol], every column its own rows
+  int64_t ncol, M;
+  const int32_t* siteStatus;
+  int32_t nCh;                             // chunks of 256 members per site
+  // split path
+  double* part;                            // [n_sites][nCh][kRejPrm] a chunk's sums, then its centred sums
+  double* stat;                            // [n_sites][2][kRejPrm] the site's means, then its sds
+  int32_t* cnt;                            // [n_sites][nCh] live members
+  int32_t* kept;                           // [n_sites][nCh] members that kept everything
+  int32_t* site;                           // [n_sites][2] the site's code and live count
+};
+
+__device__ __forceinline__ bool rejLive(const RejArgs& a, int s, int64_t j) {
+  return j < a.M && a.siteStatus[s] == 0 && a.state[(int64_t)ST_status * a.ncol + (int64_t)s * a.M + j] == 0.0;
+}
+// the site's inputs: kRejNotSelected, kRejBadInput, or kRejDone (before the live count)
+__host__ __device__ inline int rejSiteInputs(const double* shrink, const double* poolSd, const int64_t* siteTotal, int nPrm,
+                                             int mask, int64_t s) {
+  if (siteTotal && !(siteTotal[s] > 0)) return kRejNotSelected;
+  if (nPrm > 0) {
+    const double a = shrink[s];
+    if (!(a > 0.0) || !(a <= 1.0)) return kRejBadInput;
+  }
+  for (int p = 0; p < kRejPools; p++)
+    if (mask & (1 << p)) {
+      const double q = poolSd[s * kRejPools + p];
+      if (!(q >= 0.0) || !(q < INFINITY)) return kRejBadInput;
+    }
+  return kRejDone;
+}
+// rows + slots a code-1 site perturbs: the listed rows unless a == 1, the masked slots whose sd is not 0
+__device__ __forceinline__ int rejPerturbed(const RejArgs& a, int s) {
+  int n = (a.nPrm > 0 && a.shrink[s] != 1.0) ? a.nPrm : 0;
+  for (int p = 0; p < kRejPools; p++)
+    if ((a.mask & (1 << p)) && a.poolSd[(int64_t)s * kRejPools + p] > 0.0) n++;
+  return n;
+}
+__device__ __forceinline__ double rejWaveSum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+// the sum of an int over the workgroup's 256 threads, to every thread (ints: any order); smI[4], barriers on both sides
+__device__ __forceinline__ int rejBlockCount(int* smI, int v) {
+  const int tid = (int)threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();
+  if ((tid & 63) == 0) smI[tid >> 6] = v;
+  __syncthreads();
+  return smI[0] + smI[1] + smI[2] + smI[3];
+}
+__device__ __forceinline__ double rejCombine4(const double* smW, int q) {   // smW [4][kRejPrm]: the waves in order
+  return ((smW[q] + smW[kRejPrm + q]) + smW[2 * kRejPrm + q]) + smW[3 * kRejPrm + q];
+}
+
+// One live member of a code-1 site: its listed rows moved (x(k): row k's value now; mean, hsd = h sd per row; shrinkA = a,
+// rows untouched when it is 1), its masked pools perturbed, the limits, and -- unless the member keeps everything -- the
+// write-back.  Every loop is unrolled over its compile-time extent, so the new values live in registers.  false: kept.
+template <class X>
+__device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, double shrinkA, const double* mean,
+                                          const double* hsd, X x) {
+  const int64_t col = (int64_t)s * a.M + j;
+  const uint32_t stream = a.stream ? a.stream[s] : (uint32_t)s, member = (uint32_t)j;
+  const bool rows = a.nPrm > 0 && shrinkA != 1.0;
+  bool ok = true;
+  double nv[kRejPrm];
+  double leaf = 0.0, wood = 0.0, fine = 0.0, opt = 0.0, tmin = 0.0;
+  if (rows) {
+#pragma unroll
+    for (int blk = 0; blk < kRejPrm / 4; blk++) {
+      if (4 * blk >= a.nPrm) break;
+      double z[4] = {0.0, 0.0, 0.0, 0.0};
+      rejNormals(a.key0, a.key1, a.draw, stream, member, (uint32_t)blk, 4 * blk + 2 < a.nPrm, z);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int k = 4 * blk + i;
+        if (k >= a.nPrm) break;
+        const double m = mean[k];
+        double v = (m + shrinkA * (x(k) - m)) + hsd[k] * z[i];
+        if (v < a.lo[k]) v = a.lo[k] + (a.lo[k] - v);
+        else if (v > a.hi[k]) v = a.hi[k] - (v - a.hi[k]);
+        v = v < a.lo[k] ? a.lo[k] : (v > a.hi[k] ? a.hi[k] : v);
+        ok = ok && fabs(v) < INFINITY;
+        nv[k] = v;
+        if (k == a.leaf) leaf = v;
+        if (k == a.wood) wood = v;
+        if (k == a.fineRoot) fine = v;
+        if (k == a.opt) opt = v;
+        if (k == a.tmin) tmin = v;
+      }
+    }
+    if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0) {
+      if (a.leaf < 0) leaf = a.prm[(int64_t)SP_leafAllocation * a.ncol + col];
+      if (a.wood < 0) wood = a.prm[(int64_t)SP_woodAllocation * a.ncol + col];
+      if (a.fineRoot < 0) fine = a.prm[(int64_t)SP_fineRootAllocation * a.ncol + col];
+      if (leaf >= 1.0 || wood >= 1.0 || fine >= 1.0 || 1 - leaf - wood - fine < 0) ok = false;
+    }
+  }
+  // the pools: the masked slots with an sd above 0 perturbed and clipped; hasSufficientBiomass (sipnet.c:1530-1536) of the result
+  double f[kRejPools];
+  bool moved[kRejPools];
+  const double* sd = a.poolSd + (int64_t)s * kRejPools;
+#pragma unroll
+  for (int blk = 0; blk < 4; blk++) {
+    const int bits = (a.mask >> (4 * blk)) & 15;
+    double z[4] = {0.0, 0.0, 0.0, 0.0};
+    if (bits) rejNormals(a.key0, a.key1, a.draw, stream, member, (uint32_t)(4 + blk), (bits & 12) != 0, z);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int p = 4 * blk + i;
+      if (p >= kRejPools) break;
+      const double q = (bits & (1 << i)) ? sd[p] : 0.0;
+      moved[p] = q > 0.0;
+      const bool read = moved[p] || p == ST_plantWoodC || p == ST_plantCAccountingDelta || p == ST_fineRootC || p == ST_coarseRootC;
+      double v = read ? a.state[(int64_t)p * a.ncol + col] : 0.0;
+      if (moved[p]) {
+        v = v + q * z[i];
+        if (p != ST_plantCAccountingDelta && v < 0.0) v = 0.0;
+        ok = ok && fabs(v) < INFINITY;
+      }
+      f[p] = v;
+    }
+  }
+  const double totalWood = f[ST_plantWoodC] + f[ST_plantCAccountingDelta], totalRoot = f[ST_fineRootC] + f[ST_coarseRootC];
+  ok = ok && f[ST_plantWoodC] > kRejTiny && totalWood > kRejTiny && totalRoot > kRejTiny;
+  if (!ok) return false;
+#pragma unroll
+  for (int p = 0; p < kRejPools; p++)
+    if (moved[p]) a.state[(int64_t)p * a.ncol + col] = f[p];
+  if (rows) {
+#pragma unroll
+    for (int k = 0; k < kRejPrm; k++) {
+      if (k >= a.nPrm) break;
+      a.prm[(int64_t)a.prmRow[k] * a.ncol + col] = nv[k];
+    }
+    // the derived rows that depend on listed ones, by convertParamsKernel's expressions
+    if (a.opt >= 0 || a.tmin >= 0) {
+      if (a.opt < 0) opt = a.prm[(int64_t)SP_psnTOpt * a.ncol + col];
+      if (a.tmin < 0) tmin = a.prm[(int64_t)SP_psnTMin * a.ncol + col];
+      a.prm[(int64_t)SP_psnTMax * a.ncol + col] = opt + (opt - tmin);
+    }
+    if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0)
+      a.prm[(int64_t)SP_coarseRootAllocation * a.ncol + col] = 1 - leaf - wood - fine;
+  }
+  return true;
+}
+
+// ---- one workgroup per site: sites of one chunk -----------------------------------------------------------------------
+// A site of at most 256 members is one chunk, and the per-chunk launches would have one workgroup per site too: here their
+// six launches are one, and the listed rows are read from HBM once (staged in LDS for the three sweeps).  The sums are the
+// split path's: the chunk's sum by rejCombine4, added to 0.0.
+struct RejGroupLds {
+  double rows[kRejPrm][256];   // the listed rows of the site's columns
+  double smW[4 * kRejPrm];
+  double mean[kRejPrm], hsd[kRejPrm];
+  int smI[4];
+};
+// the site's sums of val(q), q < V, over the workgroup's threads -> every thread gets the sum of row tid (tid < V)
+template <class F>
+__device__ __forceinline__ double rejSiteSums(RejGroupLds& g, int V, F val) {
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __syncthreads();   // (the last sums have been read)
+  for (int q = 0; q < V; q++) {
+    const double v = rejWaveSum(val(q));
+    if (lane == 0) g.smW[wave * kRejPrm + q] = v;
+  }
+  __syncthreads();
+  double t = 0.0;
+  if (tid < V) t += rejCombine4(g.smW, tid);
+  return t;
+}
+
+__global__ __launch_bounds__(256) void rejGroupKernel(RejArgs a) {
+  __shared__ RejGroupLds g;
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int64_t j = tid, col = (int64_t)s * a.M + j;
+  int code = rejSiteInputs(a.shrink, a.poolSd, a.siteTotal, a.nPrm, a.mask, s);
+  const bool live = rejLive(a, s, j);
+  const int n = rejBlockCount(g.smI, live ? 1 : 0);
+  if (code == kRejDone && n < 2) code = kRejTooFew;
+  if (code != kRejDone) {
+    if (tid == 0) {
+      int32_t* o = a.info + 4 * (int64_t)s;
+      o[0] = code, o[1] = 0, o[2] = n, o[3] = 0;
+    }
+    return;
+  }
+  const double shrinkA = a.nPrm > 0 ? a.shrink[s] : 1.0;
+  if (a.nPrm > 0 && shrinkA != 1.0) {
+    for (int q = 0; q < a.nPrm; q++) g.rows[q][tid] = live ? a.prm[(int64_t)a.prmRow[q] * a.ncol + col] : 0.0;
+    const double sum = rejSiteSums(g, a.nPrm, [&](int q) { return g.rows[q][tid]; });
+    if (tid < a.nPrm) g.mean[tid] = sum / (double)n;
+    __syncthreads();
+    const double csum = rejSiteSums(g, a.nPrm, [&](int q) {
+      const double d = g.rows[q][tid] - g.mean[q];
+      return live ? d * d : 0.0;
+    });
+    if (tid < a.nPrm) g.hsd[tid] = sqrt((1.0 - shrinkA) * (1.0 + shrinkA)) * sqrt(csum / ((double)n - 1.0));
+    __syncthreads();
+  }
+  int kept = 0;
+  if (live) kept = rejMember(a, s, j, shrinkA, g.mean, g.hsd, [&](int k) { return g.rows[k][tid]; }) ? 0 : 1;
+  const int nKept = rejBlockCount(g.smI, kept);
+  if (tid == 0) {
+    int32_t* o = a.info + 4 * (int64_t)s;
+    o[0] = kRejDone, o[1] = rejPerturbed(a, s), o[2] = n, o[3] = nKept;
+  }
+}
+
+// ---- the split path: (site, chunk) launches ----------------------------------------------------------------------------
+// a chunk's sums of the listed rows over its live members (pass 0, with the live count), or of their squared distances from
+// the site's means (pass 1) -> part[s][c][q]
+__global__ __launch_bounds__(256) void rejChunkKernel(RejArgs a, int pass) {
+  __shared__ double smW[4 * kRejPrm];
+  __shared__ int smI[4];
+  const int s = (int)blockIdx.x, c = (int)blockIdx.y, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t j = (int64_t)c * 256 + tid, col = (int64_t)s * a.M + j;
+  const bool live = rejLive(a, s, j);
+  if (pass == 0) {
+    const int n = rejBlockCount(smI, live ? 1 : 0);
+    if (tid == 0) a.cnt[(int64_t)s * a.nCh + c] = n;
+  } else if (a.site[2 * (int64_t)s] != kRejDone) {
+    return;
+  }
+  const double* mean = a.stat + (int64_t)s * 2 * kRejPrm;
+  for (int q = 0; q < a.nPrm; q++) {
+    double v = 0.0;
+    if (live) {
+      const double x = a.prm[(int64_t)a.prmRow[q] * a.ncol + col];
+      if (pass == 0) {
+        v = x;
+      } else {
+        const double d = x - mean[q];
+        v = d * d;
+      }
+    }
+    v = rejWaveSum(v);
+    if (lane == 0) smW[wave * kRejPrm + q] = v;
+  }
+  __syncthreads();
+  if (tid < a.nPrm) a.part[((int64_t)s * a.nCh + c) * kRejPrm + tid] = rejCombine4(smW, tid);
+}
+// the site's sums from its chunks', in chunk order.  pass 0: the live count, the code, the means; pass 1: h sd
+__global__ __launch_bounds__(256) void rejSiteKernel(RejArgs a, int pass) {
+  __shared__ int smI[4];
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
+  int n;
+  if (pass == 0) {
+    int live = 0;
+    for (int c = tid; c < a.nCh; c += 256) live += a.cnt[(int64_t)s * a.nCh + c];
+    n = rejBlockCount(smI, live);
+    int code = rejSiteInputs(a.shrink, a.poolSd, a.siteTotal, a.nPrm, a.mask, s);
+    if (code == kRejDone && n < 2) code = kRejTooFew;
+    if (tid == 0) a.site[2 * (int64_t)s] = code, a.site[2 * (int64_t)s + 1] = n;
+    if (code != kRejDone) return;
+  } else {
+    if (a.site[2 * (int64_t)s] != kRejDone) return;
+    n = a.site[2 * (int64_t)s + 1];
+  }
+  // thread q adds row q's chunk sums in chunk order; the workgroup stages them 64 chunks at a time (coalesced loads in flight
+  // together: one thread reading chunk after chunk pays a memory latency each)
+  __shared__ double tile[64][kRejPrm + 1];
+  const double* part = a.part + (int64_t)s * a.nCh * kRejPrm;
+  double t = 0.0;
+  for (int base = 0; base < a.nCh; base += 64) {
+    const int here = a.nCh - base < 64 ? a.nCh - base : 64;
+    for (int i = tid; i < here * kRejPrm; i += 256) tile[i / kRejPrm][i % kRejPrm] = (i % kRejPrm) < a.nPrm ? part[(int64_t)base * kRejPrm + i] : 0.0;
+    __syncthreads();
+    if (tid < a.nPrm)
+      for (int c = 0; c < here; c++) t += tile[c][tid];
+    __syncthreads();
+  }
+  if (tid >= a.nPrm) return;
+  double* stat = a.stat + (int64_t)s * 2 * kRejPrm;
+  if (pass == 0) {
+    stat[tid] = t / (double)n;
+  } else {
+    const double shrinkA = a.shrink[s];
+    stat[kRejPrm + tid] = sqrt((1.0 - shrinkA) * (1.0 + shrinkA)) * sqrt(t / ((double)n - 1.0));
+  }
+}
+// the draw and the limits of a chunk's live members; kept[s][c] = its members that kept everything
+__global__ __launch_bounds__(256) void rejApplyKernel(RejArgs a) {
+  __shared__ int smI[4];
+  const int s = (int)blockIdx.x, c = (int)blockIdx.y, tid = (int)threadIdx.x;
+  if (a.site[2 * (int64_t)s] != kRejDone) return;
+  const int64_t j = (int64_t)c * 256 + tid, col = (int64_t)s * a.M + j;
+  const double* stat = a.stat + (int64_t)s * 2 * kRejPrm;
+  const double shrinkA = a.nPrm > 0 ? a.shrink[s] : 1.0;
+  int kept = 0;
+  if (rejLive(a, s, j))
+    kept = rejMember(a, s, j, shrinkA, stat, stat + kRejPrm, [&](int k) { return a.prm[(int64_t)a.prmRow[k] * a.ncol + col]; }) ? 0 : 1;
+  const int nKept = rejBlockCount(smI, kept);
+  if (tid == 0) a.kept[(int64_t)s * a.nCh + c] = nKept;
+}
+__global__ __launch_bounds__(256) void rejInfoKernel(RejArgs a) {
+  __shared__ int smI[4];
+  const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int code = a.site[2 * (int64_t)s];
+  int kept = 0;
+  if (code == kRejDone)
+    for (int c = tid; c < a.nCh; c += 256) kept += a.kept[(int64_t)s * a.nCh + c];
+  const int nKept = rejBlockCount(smI, kept);
+  if (tid == 0) {
+    int32_t* o = a.info + 4 * (int64_t)s;
+    o[0] = code, o[1] = code == kRejDone ? rejPerturbed(a, s) : 0, o[2] = a.site[2 * (int64_t)s + 1], o[3] = nKept;
+  }
+}
