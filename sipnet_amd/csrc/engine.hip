@@ -116,6 +116,9 @@ int sipnet_batch_create(const int32_t* flags, int32_t n_sites, int32_t n_members
   if (e == hipSuccess) e = b->d_scratchRow.tryReserve(nc);
   if (e == hipSuccess) e = hipMemset(b->d_prm, 0, nc * SIPNET_NPARAMS * sizeof(double));
   if (e == hipSuccess) e = hipMemset(b->d_state, 0, nc * SIPNET_NSTATE * sizeof(double));
+  // (the slots no step has written yet travel with a member's checkpoint and are read back by get_rings: zeros, not what the
+  // allocation held)
+  if (e == hipSuccess) e = hipMemset(b->d_ring, 0, ringDoubles(b) * sizeof(double));
   if (e == hipSuccess) e = hipEventCreate(&b->ev0);
   if (e == hipSuccess) e = hipEventCreate(&b->ev1);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evBusy, hipEventDisableTiming);

@@ -15,8 +15,10 @@
 // one segment: so that kernel and the per-chunk launches give the same bits.  No grid barrier, no spin, no atomic.
 //
 // This file is the one translation unit and the host side; the device code is in parts, included below in this order:
+//   site_device.h     what pf.hip and quantiles.hip share with this unit: the sums in their one order, the pieces of a member's
+//                     limits, the derived parameter rows (site_host.h: the host's refusals, bookkeeping and scratch growth)
 //   enkf_common.inc   what every kernel is written in: the arguments (EnkfArgs, JointArgs), a site's inputs, predicted(), the
-//                     sums in their one order, the gains, a member's load, inflation and limits.  Every difference between
+//                     gains, a member's load, inflation and limits.  Every difference between
 //                     the joint and the per-site arguments is a function here: no kernel body forks on the argument type.
 //   enkf_sites.inc    enkfSiteKernel (one workgroup per site: enkfSites) and the per-chunk kernels, a launch per stage: load,
 //                     code, partial, final, update (enkfFront, enkfSites), limit, info (enkfEnd); for either arguments
@@ -42,9 +44,11 @@
 #include <vector>
 
 #include "batch_impl.h"
+#include "site_host.h"
 
 namespace {
 
+#include "site_device.h"
 #include "enkf_common.inc"
 #include "enkf_sites.inc"
 #include "enkf_local.inc"
@@ -71,12 +75,6 @@ struct sipnet_enkf_local {
 
 namespace {
 
-// a refusal: "`name`: `why`" is the thread's error
-int refuse(const char* name, const std::string& why) {
-  setError(std::string(name) + ": " + why);
-  return SIPNET_ERR_BAD_ARGUMENT;
-}
-
 // what every analysis is called with, as its extern "C" function received it
 struct EnkfCall {
   sipnet_batch* b;
@@ -94,7 +92,7 @@ struct EnkfCall {
 
 // The checks and the arguments the analyses share, up to the scratch block: 0, or the error (the message names `name`).
 // The synchronous form (no d_site_info) reads obs, sd and inflation back and refuses a bad site before anything is written.
-int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a) {
+int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a, bool ownRows = false) {
   sipnet_batch* const b = c.b;
   const int32_t n_obs = c.n_obs;
   const hipStream_t stream = c.stream;
@@ -118,16 +116,16 @@ int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a) {
     }
   }
   if (planesUsed && (c.n_steps <= 0 || c.ld < b->ncol)) return refuse(name, "planes need n_steps > 0 and ld >= ncol");
-  if (b->ncol > (int64_t)1 << 22) return refuse(name, "at most 4194304 members");
+  if (tooManyColumns(b)) return refuse(name, "at most 4194304 members");
   if (b->pfPeers) return refuse(name, "this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
   int rc = useDevice(b);
   if (rc) return rc;
   const int64_t nSites = b->n_sites, M = b->n_members, ncol = b->ncol;
   if (!c.d_site_info && !c.momentsOnly) {   // the synchronous form: the inputs are checked before anything is launched
-    std::vector<double> obs((size_t)(nSites * n_obs)), sd(obs.size()), infl(c.d_inflation ? (size_t)nSites : 0);
-    HIP_TRY(hipMemcpyAsync(obs.data(), c.d_obs, obs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(sd.data(), c.d_sd, sd.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (c.d_inflation) HIP_TRY(hipMemcpyAsync(infl.data(), c.d_inflation, infl.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    std::vector<double> obs, sd, infl;
+    RC_TRY(readBack(obs, c.d_obs, (size_t)(nSites * n_obs), stream));
+    RC_TRY(readBack(sd, c.d_sd, obs.size(), stream));
+    RC_TRY(readBack(infl, c.d_inflation, (size_t)nSites, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (int64_t s = 0; s < nSites; s++) {
       int used;
@@ -136,14 +134,12 @@ int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a) {
                             "be finite and >= 1); nothing was written");
     }
   }
-  if (!c.momentsOnly) {
-    b->pfPre.valid = false;
-    b->pfArm.set = false;
+  if (c.momentsOnly) {   // (nothing of the batch is written: what a forecast has left stays good)
+    RC_TRY(orderBehindBusy(b, stream));
+    RC_TRY(flushParams(b, stream));
+  } else {
+    RC_TRY(beginWrite(b, stream, ownRows));
   }
-  rc = orderBehindBusy(b, stream);
-  if (rc) return rc;
-  rc = flushParams(b, stream);
-  if (rc) return rc;
 
   a = EnkfArgs{};
   a.nObs = n_obs;
@@ -210,10 +206,7 @@ int enkfScratch(sipnet_batch* b, DevBuf<unsigned char>& block, EnkfArgs& a, int3
   const size_t nSite = perChunk ? 2 * nSites : 0;
   const size_t nInt = nSites * 4 + 2 * nCnt + nSite + (withSrc ? nSites : 0);
   const size_t bytes = (nWork + nPart + nStat + nMat) * sizeof(double) + nInt * sizeof(int32_t);
-  if (block.capacity() < bytes) {
-    RC_TRY(waitIdle(b));   // (the old block may still be read by a launch in flight)
-    RC_TRY(block.reserve(bytes));   // (this block alone: the other may be in use by this very call)
-  }
+  RC_TRY(growScratch(b, block, bytes));
   a.work = (double*)block.get();
   a.part = a.work + nWork;
   a.stat = a.part + nPart;
@@ -263,10 +256,7 @@ int enkfEnd(const EnkfCall& c, const A& a, bool perChunk, int32_t fused, int32_t
     hipLaunchKernelGGL(enkfInfoKernel<A>, siteGrid(b), dim3(256), 0, c.stream, a);
   }
   HIP_TRY(hipGetLastError());
-  b->pfInfo.fused = fused;
-  b->pfInfo.grid = grid;
-  b->pfInfo.budget = 0;
-  b->pfInfo.nSlots = b->ncol;
+  reportPath(b, fused != 0, grid);
   return markBusy(b, c.stream);
 }
 
@@ -536,38 +526,25 @@ int jointCall(const char* name, const EnkfCall& c, int32_t n_params, const sipne
   if (b && d_param_inflation && !c.d_site_info && !b->pfPeers) {   // the synchronous form: checked before anything is launched
     rc = useDevice(b);
     if (rc) return rc;
-    std::vector<double> infl((size_t)b->n_sites);
-    HIP_TRY(hipMemcpyAsync(infl.data(), d_param_inflation, infl.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    std::vector<double> infl;
+    RC_TRY(readBack(infl, d_param_inflation, (size_t)b->n_sites, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (size_t s = 0; s < infl.size(); s++)
       if (!(infl[s] >= 1.0) || !(infl[s] < INFINITY))
         return refuse(name, "site " + std::to_string(s) + ": bad input (the parameter inflation must be finite and >= 1); "
                             "nothing was written");
   }
-  // (enkfBegin fills the arguments the analyses share and leaves the bounds alone)
-  rc = enkfBegin(name, c, a);
+  // (enkfBegin fills the arguments the analyses share and leaves the bounds alone; every column its own rows: the limits
+  // write them, and a.prm is b->d_prm in column order)
+  rc = enkfBegin(name, c, a, /*ownRows=*/true);
   if (rc) return rc;
-  rc = materializeParams(b, stream);   // (every column its own rows: the limits write them)
-  if (rc) return rc;
-  a.prm = b->d_prm;
-  a.prmPitch = b->ncol;
-  a.prmId = nullptr;
   a.prmOut = b->d_prm;
   a.prmInfl = d_param_inflation;
   a.nPool = a.nA;
   a.nPrm = n_params;
   a.nA += n_params;
   a.nv += n_params;
-  a.leaf = a.wood = a.fineRoot = a.opt = a.tmin = -1;
-  for (int k = 0; k < n_params; k++) {
-    const int p = params[k].index;
-    a.prmRow[k] = p;
-    if (p == SP_leafAllocation) a.leaf = k;
-    if (p == SP_woodAllocation) a.wood = k;
-    if (p == SP_fineRootAllocation) a.fineRoot = k;
-    if (p == SP_psnTOpt) a.opt = k;
-    if (p == SP_psnTMin) a.tmin = k;
-  }
+  a.rows = derivedRowsOf(n_params, params, a.prmRow);
   if (n_series == 0) return enkfSites(c, a);
   SmoothStage st;
   rc = smoothFront(c, a, n_series, series, st);

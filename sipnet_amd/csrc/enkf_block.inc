@@ -57,8 +57,7 @@ __global__ __launch_bounds__(kBlockThreads) void enkfBlockKernel(EnkfArgs a, con
     int missing = 0;
     if (splitCode(a, u) == kAnalysed)
       for (int64_t j = lane; j < M; j += 64) missing += g.live[j] && !liveAt(a, u, j) ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) missing += __shfl_xor(missing, off, 64);
+    missing = waveSum(missing);
     if (lane == 0) g.srcOk[k] = missing == 0;
   }
   if (tid < nIn && in[in0 + tid] < t && (tid + 1 == nIn || in[in0 + tid + 1] > t)) g.selfPos = tid + 1;   // (one writer)

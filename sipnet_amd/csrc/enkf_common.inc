@@ -5,7 +5,6 @@ constexpr int kPools = 13;                 // state slots 0..12: the Envi pools
 constexpr int kMaxVars = kPools + kMaxObs;
 constexpr int kMaxGroupChunks = 16;        // one workgroup per site: sites of at most 16 x 256 members
 constexpr int kLdsWork = 40 * 1024;        // ... whose working copies fit here stay in LDS, else in the scratch block
-constexpr double kTiny = 0.000001;         // TINY, common/util.h
 constexpr int kMaxPrm = SIPNET_ENKF_MAX_PARAMS;   // the joint analysis: analysed parameters, between the pools and the h
 constexpr int kJointVars = kMaxVars + kMaxPrm;
 constexpr int kAnalysed = 1, kNoObs = -1, kBadInput = -2, kTooFew = 0;
@@ -52,7 +51,7 @@ struct JointArgs : EnkfArgs {
   double lo[kMaxPrm], hi[kMaxPrm];         // their bounds, converted units
   const double* prmInfl;                   // [n_sites] or null: lambda of the parameter variables
   double* prmOut;                          // d_prm [NPARAMS][ncol], every column its own rows: read by the load, written by the limits
-  int32_t leaf, wood, fineRoot, opt, tmin; // where leafAllocation .. psnTMin are among the analysed parameters, or -1
+  DerivedRows rows;                        // where leafAllocation .. psnTMin are among the analysed parameters
 };
 
 __device__ __forceinline__ bool liveAt(const EnkfArgs& a, int s, int64_t j) {
@@ -120,25 +119,6 @@ __device__ double predicted(const EnkfArgs& a, int i, int64_t col) {
   return h;
 }
 
-__device__ __forceinline__ double waveSum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// the sum of an int over the workgroup's 256 threads (ints: any order), to every thread: every wave by an xor-shuffle
-// butterfly, the four wave totals through smI[4] (a second sum through the same smI needs a barrier first)
-__device__ __forceinline__ int blockSum(int* smI, int v) {
-  const int tid = (int)threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((tid & 63) == 0) smI[tid >> 6] = v;
-  __syncthreads();
-  return smI[0] + smI[1] + smI[2] + smI[3];
-}
-template <int kCap>
-__device__ __forceinline__ double combine4(const double* smW, int q) {   // smW [4][kCap]: the waves in order
-  return ((smW[q] + smW[kCap + q]) + smW[2 * kCap + q]) + smW[3 * kCap + q];
-}
 // chunks per segment of a site of nCh chunks: at most 64 segments
 constexpr int kMaxSegs = 64;
 __device__ __forceinline__ int segLen(int nCh) { return nCh <= 16 * kMaxSegs ? 16 : (nCh + kMaxSegs - 1) / kMaxSegs; }
@@ -192,14 +172,12 @@ __device__ bool limited(const EnkfArgs& a, int nPool, int64_t col, const double*
   for (int p = 0; p < kPools; p++) f[p] = a.state[(int64_t)p * a.ncol + col];
   bool finite = true;
   for (int q = 0; q < nPool; q++) {
-    double v = W[(int64_t)q * ldw + j];
-    if (a.pool[q] != ST_plantCAccountingDelta && v < 0.0) v = 0.0;
+    const double v = poolLimit(a.pool[q], W[(int64_t)q * ldw + j]);
     finite = finite && fabs(v) < INFINITY;
     fin[q] = v;
     f[a.pool[q]] = v;
   }
-  const double totalWood = f[ST_plantWoodC] + f[ST_plantCAccountingDelta], totalRoot = f[ST_fineRootC] + f[ST_coarseRootC];
-  return finite && f[ST_plantWoodC] > kTiny && totalWood > kTiny && totalRoot > kTiny;
+  return finite && sufficientBiomass(f[ST_plantWoodC], f[ST_plantCAccountingDelta], f[ST_fineRootC], f[ST_coarseRootC]);
 }
 
 // the joint analysis's limits of one live member's parameters, after limited(): every analysed parameter clipped into its
@@ -217,25 +195,12 @@ __device__ bool limitedParams(const JointArgs& a, int64_t col, double* W, int64_
     ok = ok && fabs(v) < INFINITY;
     *x = v;
   }
-  if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0) {
-    const double leaf = prmNow(a, W, ldw, j, col, a.leaf, SP_leafAllocation), wood = prmNow(a, W, ldw, j, col, a.wood, SP_woodAllocation),
-                 fine = prmNow(a, W, ldw, j, col, a.fineRoot, SP_fineRootAllocation);
-    if (leaf >= 1.0 || wood >= 1.0 || fine >= 1.0 || 1 - leaf - wood - fine < 0) ok = false;
-  }
-  return ok;
+  return allocationsOk(a.rows, [&](int k, int row) { return prmNow(a, W, ldw, j, col, k, row); }) && ok;
 }
 // ... and its rows written: the analysed ones, then the derived rows that depend on them, by convertParamsKernel's expressions
 __device__ void writeParams(const JointArgs& a, int64_t col, const double* W, int64_t ldw, int64_t j) {
   for (int k = 0; k < a.nPrm; k++) a.prmOut[(int64_t)a.prmRow[k] * a.ncol + col] = W[(int64_t)(a.nPool + k) * ldw + j];
-  if (a.opt >= 0 || a.tmin >= 0) {
-    const double opt = prmNow(a, W, ldw, j, col, a.opt, SP_psnTOpt), tmin = prmNow(a, W, ldw, j, col, a.tmin, SP_psnTMin);
-    a.prmOut[(int64_t)SP_psnTMax * a.ncol + col] = opt + (opt - tmin);
-  }
-  if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0) {
-    const double leaf = prmNow(a, W, ldw, j, col, a.leaf, SP_leafAllocation), wood = prmNow(a, W, ldw, j, col, a.wood, SP_woodAllocation),
-                 fine = prmNow(a, W, ldw, j, col, a.fineRoot, SP_fineRootAllocation);
-    a.prmOut[(int64_t)SP_coarseRootAllocation * a.ncol + col] = 1 - leaf - wood - fine;
-  }
+  writeDerivedRows(a.prmOut, a.ncol, col, a.rows, [&](int k, int row) { return prmNow(a, W, ldw, j, col, k, row); });
 }
 // one live member through the limits and, unless it keeps its forecast, written back: its analysed pools (and parameters)
 template <class A>
@@ -262,31 +227,6 @@ struct GroupLdsOf {
   int smI[4];
 };
 using GroupLds = GroupLdsOf<kMaxVars>;
-// the site's sums of val(j, q), q < V, in the fixed order -> g.tot
-template <class G, class F>
-__device__ void siteSums(G& g, int V, int nCh, F val) {
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int q = 0; q < V; q++)
-    for (int c = 0; c < nCh; c++) {
-      const double v = waveSum(val((int64_t)c * 256 + tid, q));
-      if (lane == 0) g.smW[c][wave * G::kCap + q] = v;
-    }
-  __syncthreads();
-  for (int k = tid; k < V * nCh; k += 256) g.chunkTot[k / V][k % V] = combine4<G::kCap>(g.smW[k / V], k % V);
-  __syncthreads();
-  if (tid < V) {
-    double t = 0.0;
-    for (int c = 0; c < nCh; c++) t += g.chunkTot[c][tid];
-    g.tot[tid] = t;
-  }
-  __syncthreads();
-}
-template <class G>
-__device__ int blockCount(G& g, int v) {
-  const int n = blockSum(g.smI, v);
-  __syncthreads();
-  return n;
-}
 
 // the site's code, as enkfCodeKernel left it
 __device__ __forceinline__ int splitCode(const EnkfArgs& a, int s) { return a.site[2 * (int64_t)s]; }

@@ -72,8 +72,7 @@ __global__ __launch_bounds__(256) void enkfShardTotalKernel(EnkfArgs a, int cap,
   }
   int n = 0;
   for (int c = lane; c < a.nCh; c += 64) n += a.cnt[(int64_t)s * a.nCh + c];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+  n = waveSum(n);
   if (lane == 0) {
     block[2 + e] = n > 0 ? t / (double)n : 0.0;
     if (e == 0) {

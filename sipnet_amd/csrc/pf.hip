@@ -12,32 +12,17 @@
 // blockIdx.y = row, so reads of the index vector and writes are coalesced; after systematic
 // resampling ancestors are non-decreasing, so the gathered reads are near-coalesced too.
 //
-// This file is the one translation unit (the one tools/build_variants.py compiles with -DSIPNET_PF_*) and the host side;
-// the device code is in parts, included below in this order:
-//   pf_gather.inc    the gathers of a member's checkpoint: gatherMemberKernel (own columns and received packed blocks, RecvMap),
-//                    gatherPeerKernel (straight out of the peers' matrices, PeerPtrs), exponentCheckKernel, iotaKernel,
-//                    copyRowsKernel; and the host's one launch of gatherMemberKernel (GatherCall, launchGatherMember)
-//   pf_weights.inc   the analysis as launches of their own: logWeightKernel and the block maxima, pfFixedWeight and the two
-//                    kernels that apply it (one batch's log-weights, the ranks' gathered blocks), ancestorKernel
-//   pf_fused.inc     the analysis in ONE launch: the SIPNET_PF_* defaults, the PF_STAMP probe, FusedArgs, the two-level grid
-//                    barrier in device memory, pfFusedKernel (why one launch, residency, the barrier: explained there)
-//   pf_plan.inc      the exchange plan of a resampling whose checkpoints travel in packed blocks: the four plan*Kernels
-//   pf_sites.inc     the analysis of a batch of many sites: SitesArgs, pfSitesKernel (a workgroup per site), the split path's
-//                    three launches; both from a plane and an observation per site, or from log-weights the caller gives
-//   pf_series.inc    every member's log-likelihood of a window's series against observed series with gaps: LoglikArgs,
-//                    loglikKernel (one launch), loglikTileKernel + loglikCombineKernel (tiles' sums, then their sum in order)
-//   pf_rejuvenate.inc  what gives resampled copies their own values again: the counter-based normals (Philox4x32-10, Box-Muller),
-//                    RejArgs, rejMember (the Liu-West move of parameter rows, pool noise, the limits), rejGroupKernel (a workgroup
-//                    per site) and the split path's rejChunkKernel, rejSiteKernel, rejApplyKernel, rejInfoKernel
+// This file is the one translation unit (the one tools/build_variants.py compiles with -DSIPNET_PF_*) and the host side; the
+// device code is in parts, each with its own header comment, included below in this order: site_device.h (the sums in their
+// one order, a member's limits and derived rows, shared with enkf.hip), pf_gather.inc, pf_weights.inc, pf_fused.inc,
+// pf_plan.inc, pf_sites.inc, pf_series.inc, pf_rejuvenate.inc.  Refusals, the bookkeeping of a call that writes the batch, the
+// scratch blocks' growth and the synchronous forms' copies are site_host.h's.
 //
-// The host side runs three filters.  One batch (sipnet_batch_pf_analysis): the PfPre match (takePfPre), the one launch
-// (fusedSetup + the one-batch fields) or the launches of their own, the synchronous check (checkTotal), the resampling
-// gather (resampleColumns: settleParams, recvMapOf, launchGatherMember, adoptSpares, widenExponents).  Many sites
-// (sipnet_batch_pf_analysis_sites, and sipnet_batch_pf_resample_sites from given log-weights): the arguments, sitesLaunch,
-// sitesCheck, resampleColumns.  Series weights (sipnet_batch_series_loglik): loglikCheck, the path, the launches.  Rejuvenation (sipnet_batch_pf_rejuvenate): the refusals,
-// rejCheck, the bookkeeping of an analysis that writes parameters, rejScratch, the path, the launches.  Across ranks by peer reads:
-// sipnet_batch_pf_publish, _connect (own descriptor, closePeers, mapPeer, fillBank and the crossing counter) and
-// _resample_peers (peerTable, peerAncestors: fusedSetup + the gathered fields or launches, peerGather, adoptSpares).
+// The host side runs three filters.  One batch (sipnet_batch_pf_analysis): takePfPre, the one launch (fusedSetup) or the
+// launches of their own, checkTotal, the resampling gather (resampleColumns).  Many sites (sipnet_batch_pf_analysis_sites, and
+// sipnet_batch_pf_resample_sites from given log-weights): sitesBegin, the weights' source, sitesFinish.  Across ranks by peer
+// reads: sipnet_batch_pf_publish, _connect (mapPeer, fillBank) and _resample_peers (peerTable, peerAncestors, peerGather).
+// Beside them the series weights (sipnet_batch_series_loglik) and the rejuvenation (sipnet_batch_pf_rejuvenate).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -53,10 +38,12 @@
 
 #include "../../include/sipnet_amd.h"
 #include "batch_impl.h"
+#include "site_host.h"
 
 namespace sipnet {
 namespace {
 
+#include "site_device.h"
 #include "pf_gather.inc"
 #include "pf_weights.inc"
 #include "pf_fused.inc"
@@ -177,10 +164,8 @@ int32_t sipnet_batch_member_words(const sipnet_batch* b, int32_t with_params) {
 // (npad >= ncol: log-weight slots to fill, the ones past the batch's particles with -inf)
 static int logWeights(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps, int64_t ld,
                       double obs, double sigma, double* d_logw, double* d_part, void* hip_stream, int64_t npad = 0) {
-  if (!b || !d_plane || !d_logw || n_steps <= 0 || ld < b->ncol || !(sigma > 0)) {
-    setError("sipnet_batch_pf_log_weights: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !d_plane || !d_logw || n_steps <= 0 || ld < b->ncol || !(sigma > 0))
+    return refuse("sipnet_batch_pf_log_weights", "bad argument");
   int rc = useDevice(b);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -298,10 +283,7 @@ static void fusedBarrier(PfScratch& sc, FusedArgs* fa, int spinBudget) {
 // a launch the runtime refused has not touched its set (nor cleared the one ahead): the next one takes the same set
 static int fusedLaunched(PfScratch& sc) {
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    setError(std::string("pfFusedKernel: ") + hipGetErrorString(e));
-    return SIPNET_ERR_INTERNAL;
-  }
+  if (e != hipSuccess) return refuse("pfFusedKernel", hipGetErrorString(e), SIPNET_ERR_INTERNAL);
   sc.launches++;
   return SIPNET_OK;
 }
@@ -349,14 +331,8 @@ static int checkTotal(PfScratch& sc, const int64_t* d_total, const char* who, hi
   int64_t total = 0;
   HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  if (total == kPfVoid) {
-    setError(std::string(who) + ": " + fusedStuckReport(sc, stream));
-    return SIPNET_ERR_INTERNAL;
-  }
-  if (total <= 0) {
-    setError(std::string(who) + ": every particle has zero weight");
-    return SIPNET_ERR_BAD_PARAMETER;
-  }
+  if (total == kPfVoid) return refuse(who, fusedStuckReport(sc, stream), SIPNET_ERR_INTERNAL);
+  if (total <= 0) return refuse(who, "every particle has zero weight", SIPNET_ERR_BAD_PARAMETER);
   return SIPNET_OK;
 }
 // Has the forecast's own launch left the log-weights of exactly this plane, observation and sigma in d_logw
@@ -375,10 +351,8 @@ static bool takePfPre(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32,
 static int ancestorsImpl(PfScratch& sc, const double* d_logw, int64_t n, double u0, int32_t* d_ancestors,
                          int64_t* d_fixed_weights, int64_t* d_total, int partsGiven, void* hip_stream,
                          const double* partPtr = nullptr) {
-  if (!d_logw || !d_ancestors || n <= 0 || n > (int64_t)1 << 22 || !(u0 >= 0.0) || !(u0 < 1.0)) {
-    setError("sipnet_pf_systematic_ancestors: bad argument (n <= 4194304, 0 <= u0 < 1)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!d_logw || !d_ancestors || n <= 0 || n > kMaxColumns || !(u0 >= 0.0) || !(u0 < 1.0))
+    return refuse("sipnet_pf_systematic_ancestors", "bad argument (n <= 4194304, 0 <= u0 < 1)");
   hipStream_t stream = (hipStream_t)hip_stream;
   int rc = pfScratchFor(sc, n, stream);
   if (rc) return rc;
@@ -433,10 +407,8 @@ int sipnet_pf_exchange_plan(const int32_t* d_ancestors, int64_t n_local, int32_t
                             int64_t* recv_counts, void* hip_stream) {
   if (!d_ancestors || !d_send_cols || !d_src || !send_counts || !recv_counts || n_local <= 0 ||
       world < 1 || world > kMaxWorld || rank < 0 || rank >= world ||
-      n_local * world > (int64_t)1 << 30) {
-    setError("sipnet_pf_exchange_plan: bad argument (world <= 64)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+      n_local * world > (int64_t)1 << 30)
+    return refuse("sipnet_pf_exchange_plan", "bad argument (world <= 64)");
   hipStream_t stream = (hipStream_t)hip_stream;
   const int64_t total = n_local * world;
   int dev = 0;
@@ -471,10 +443,8 @@ int sipnet_pf_exchange_plan(const int32_t* d_ancestors, int64_t n_local, int32_t
   int64_t h[4 * kMaxWorld + 1];
   HIP_TRY(hipMemcpyAsync(h, sc.d_counts, (size_t)(4 * kMaxWorld + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  if (h[4 * kMaxWorld] != 0) {
-    setError("sipnet_pf_exchange_plan: the ancestor vector is not non-decreasing inside [0, world * n_local)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (h[4 * kMaxWorld] != 0)
+    return refuse("sipnet_pf_exchange_plan", "the ancestor vector is not non-decreasing inside [0, world * n_local)");
   for (int q = 0; q < world; q++) {
     send_counts[q] = h[q];
     recv_counts[q] = h[world + q];
@@ -491,10 +461,8 @@ void sipnet_pf_release_scratch(void) {
 
 int sipnet_batch_pack_members(sipnet_batch* b, const int32_t* d_cols, int64_t n,
                               int32_t with_params, double* d_buf, void* hip_stream) {
-  if (!b || n < 0 || (n > 0 && (!d_cols || !d_buf))) {
-    setError("sipnet_batch_pack_members: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || n < 0 || (n > 0 && (!d_cols || !d_buf)))
+    return refuse("sipnet_batch_pack_members", "bad argument");
   int rc = useDevice(b);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -547,10 +515,8 @@ static int recvMapOf(int32_t n_blocks, const int64_t* block_cols, int words, con
   map->nBlocks = n_blocks;
   int64_t start = 0, off = 0;
   for (int s = 0; s < n_blocks; s++) {
-    if (block_cols[s] < 0) {
-      setError("sipnet_batch_resample: negative block size");
-      return SIPNET_ERR_BAD_ARGUMENT;
-    }
+    if (block_cols[s] < 0)
+      return refuse("sipnet_batch_resample", "negative block size");
     map->start[s] = start;
     map->off[s] = off;
     map->n[s] = block_cols[s];
@@ -558,10 +524,8 @@ static int recvMapOf(int32_t n_blocks, const int64_t* block_cols, int words, con
     off += block_cols[s] * words;
   }
   map->start[n_blocks] = start;
-  if (start > 0 && !d_recv) {
-    setError("sipnet_batch_resample: received columns announced but no buffer given");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (start > 0 && !d_recv)
+    return refuse("sipnet_batch_resample", "received columns announced but no buffer given");
   return SIPNET_OK;
 }
 // resampleColumns, after the gather: parameters that arrived from other ranks may change which kernel variant the batch
@@ -593,11 +557,9 @@ static int resampleColumns(sipnet_batch* b, const int32_t* d_src, const double* 
   if (rc) return rc;
   RC_TRY(ensureSpares(b, /*state=*/true, /*params=*/false, /*index=*/false));
   const bool byIndex = with_params && n_blocks == 0;
-  if (b->d_prmBank && !with_params) {
-    setError("sipnet_batch_resample: this batch is connected to a filter whose particles carry their parameters "
-             "(sipnet_batch_pf_connect): resample with_params");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (b->d_prmBank && !with_params)
+    return refuse("sipnet_batch_resample", "this batch is connected to a filter whose particles carry their parameters "
+                  "(sipnet_batch_pf_connect): resample with_params");
   rc = settleParams(b, with_params != 0, byIndex, stream);
   if (rc) return rc;
   GatherCall g;
@@ -628,34 +590,26 @@ static int resampleColumns(sipnet_batch* b, const int32_t* d_src, const double* 
 int sipnet_batch_resample(sipnet_batch* b, const int32_t* d_src, const double* d_recv,
                           int32_t n_blocks, const int64_t* block_cols, int32_t with_params,
                           void* hip_stream) {
-  if (!b || !d_src || n_blocks < 0 || n_blocks > kMaxBlocks || (n_blocks > 0 && !block_cols)) {
-    setError("sipnet_batch_resample: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  if (b->n_sites != 1) {
-    setError("sipnet_batch_resample: particles of different sites must not mix (n_sites must be 1)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !d_src || n_blocks < 0 || n_blocks > kMaxBlocks || (n_blocks > 0 && !block_cols))
+    return refuse("sipnet_batch_resample", "bad argument");
+  if (b->n_sites != 1)
+    return refuse("sipnet_batch_resample", "particles of different sites must not mix (n_sites must be 1)");
   return resampleColumns(b, d_src, d_recv, n_blocks, block_cols, with_params, hip_stream);
 }
 
 int sipnet_batch_pf_analysis(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps,
                              int64_t ld, double obs, double sigma, double u0, int32_t with_params,
                              double* d_logw, int32_t* d_ancestors, int64_t* d_total, void* hip_stream) {
-  if (!b || !d_logw || !d_ancestors) {
-    setError("sipnet_batch_pf_analysis: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !d_logw || !d_ancestors)
+    return refuse("sipnet_batch_pf_analysis", "bad argument");
   int rc = useDevice(b);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   PfScratch& sc = scratchOf(b);
   rc = pfScratchFor(sc, b->ncol, stream);
   if (rc) return rc;
-  if (!d_plane || n_steps <= 0 || ld < b->ncol || !(sigma > 0) || !(u0 >= 0.0) || !(u0 < 1.0) || b->ncol > (int64_t)1 << 22) {
-    setError("sipnet_batch_pf_analysis: bad argument (sigma > 0, 0 <= u0 < 1, at most 4194304 particles)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!d_plane || n_steps <= 0 || ld < b->ncol || !(sigma > 0) || !(u0 >= 0.0) || !(u0 < 1.0) || tooManyColumns(b))
+    return refuse("sipnet_batch_pf_analysis", "bad argument (sigma > 0, 0 <= u0 < 1, at most 4194304 particles)");
   const bool havePre = takePfPre(b, d_plane, elem_is_f32, n_steps, ld, obs, sigma, d_logw);
   int64_t* d_sum = sc.d_blockSum + kFusedBlocks;   // the total weight, whichever path wrote it
   FusedArgs fa{};
@@ -705,14 +659,13 @@ int sipnet_batch_pf_analysis(sipnet_batch* b, const void* d_plane, int32_t elem_
 
 // scratch of the many-site analysis: the sites' totals, and for the split path the chunks' maxima, sums and threads' sums
 // (and, behind them, the chunks' sums of squares that given weights' effective sample size needs)
-static int sitesScratchFor(PfScratch& sc, int64_t nSites, int64_t nChunks) {
-  const size_t bytes = (size_t)(nSites + nChunks * (2 + 256 + 2)) * sizeof(int64_t);
-  return sc.d_sites.reserve(bytes);
+static int sitesScratchFor(sipnet_batch* b, PfScratch& sc, int64_t nSites, int64_t nChunks) {
+  return growScratch(b, sc.d_sites, (size_t)(nSites + nChunks * (2 + 256 + 2)) * sizeof(int64_t));
 }
 
 // the many-site analysis on the device: one workgroup per site in one launch, or (split) chunks of sa.chunk columns in three
 // (given: the weight source is the caller's log-weights, sipnet_batch_pf_resample_sites)
-static void sitesLaunch(SitesArgs& sa, PfScratch& sc, int64_t nSites, bool split, bool f32, hipStream_t stream, bool given = false) {
+static void sitesLaunch(SitesArgs& sa, PfScratch& sc, int64_t nSites, bool split, bool f32, hipStream_t stream, bool given) {
   const dim3 sites((unsigned)nSites);
   if (!split) {
     if (given) hipLaunchKernelGGL((pfSitesKernel<double, true>), sites, dim3(256), 0, stream, sa);
@@ -740,21 +693,16 @@ static void sitesLaunch(SitesArgs& sa, PfScratch& sc, int64_t nSites, bool split
 }
 // the synchronous checks of the many-site analysis, before anything is resampled: the sites' totals, read back
 // (who: the entry point; invalid: what makes a site's arguments bad there)
-static int sitesCheck(PfScratch& sc, int64_t nSites, hipStream_t stream, const char* who = "sipnet_batch_pf_analysis_sites",
-                      const char* invalid = "a finite obs needs a finite sigma > 0; 0 <= u0 < 1") {
-  std::vector<int64_t> tot((size_t)nSites);
-  HIP_TRY(hipMemcpyAsync(tot.data(), sc.d_sites, (size_t)nSites * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+static int sitesCheck(PfScratch& sc, int64_t nSites, hipStream_t stream, const char* who, const char* invalid) {
+  std::vector<int64_t> tot;
+  RC_TRY(readBack(tot, (const int64_t*)sc.d_sites.get(), (size_t)nSites, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   for (int64_t s = 0; s < nSites; s++)
-    if (tot[(size_t)s] == kSiteInvalid) {
-      setError(std::string(who) + ": site " + std::to_string(s) + ": bad argument (" + invalid + "); nothing was resampled");
-      return SIPNET_ERR_BAD_ARGUMENT;
-    }
+    if (tot[(size_t)s] == kSiteInvalid)
+      return refuse(who, "site " + std::to_string(s) + ": bad argument (" + invalid + "); nothing was resampled");
   for (int64_t s = 0; s < nSites; s++)
-    if (tot[(size_t)s] == 0) {
-      setError(std::string(who) + ": site " + std::to_string(s) + ": every particle has zero weight; nothing was resampled");
-      return SIPNET_ERR_BAD_PARAMETER;
-    }
+    if (tot[(size_t)s] == 0)
+      return refuse(who, "site " + std::to_string(s) + ": every particle has zero weight; nothing was resampled", SIPNET_ERR_BAD_PARAMETER);
   return SIPNET_OK;
 }
 // the many-site analysis' path and the split path's chunks (256 x a power of two columns, at most kSitesMaxChunks per site).
@@ -767,91 +715,22 @@ static bool sitesGeometry(const sipnet_batch* b, int* chunk, int* nChunks) {
   *nChunks = (int)((M + *chunk - 1) / *chunk);
   return M > kSitesLds || b->n_sites < b->numCUs || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
 }
-// what sipnet_batch_pf_info reports of a many-site analysis
-static void sitesInfo(sipnet_batch* b, bool split) {
-  b->pfInfo.fused = split ? 0 : 1;
-  b->pfInfo.grid = split ? 0 : (int32_t)b->n_sites;
-  b->pfInfo.budget = 0;
-  b->pfInfo.nSlots = b->ncol;
-}
 
-int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps, int64_t ld,
-                                   const double* d_obs, const double* d_sigma, const double* d_u0, int32_t with_params,
-                                   double* d_logw, int32_t* d_ancestors, int64_t* d_fixed_weights, int64_t* d_site_total,
-                                   void* hip_stream) {
-  if (!b || !d_plane || !d_obs || !d_sigma || !d_u0 || !d_logw || !d_ancestors || n_steps <= 0 || ld < b->ncol ||
-      b->ncol > (int64_t)1 << 22) {
-    setError("sipnet_batch_pf_analysis_sites: bad argument (device pointers, n_steps > 0, ld >= ncol, at most 4194304 particles)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  if (b->pfPeers) {
-    setError("sipnet_batch_pf_analysis_sites: this batch is connected to a filter across ranks (sipnet_batch_pf_connect): "
-             "resample through sipnet_batch_pf_resample_peers");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  int rc = useDevice(b);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
+// What the two many-site entry points do before their own arguments: the refusal of a connected batch, the device, whatever a
+// forecast has left is spent, the scratch, the path (*split) and the geometry, and of sa what does not depend on the weights' source
+static int sitesBegin(const char* who, sipnet_batch* b, const double* d_u0, double* d_logw, int32_t* d_ancestors,
+                      int64_t* d_fixed_weights, int64_t* d_site_total, hipStream_t stream, SitesArgs& sa, bool* split) {
+  if (b->pfPeers)
+    return refuse(who, "this batch is connected to a filter across ranks (sipnet_batch_pf_connect): resample through "
+                       "sipnet_batch_pf_resample_peers");
+  RC_TRY(useDevice(b));
   b->pfPre.valid = false;
   PfScratch& sc = scratchOf(b);
-  rc = pfScratchFor(sc, b->ncol, stream);
-  if (rc) return rc;
-  const int64_t M = b->n_members, nSites = b->n_sites;
+  RC_TRY(pfScratchFor(sc, b->ncol, stream));
   int chunk, nChunks;
-  const bool split = sitesGeometry(b, &chunk, &nChunks);
-  rc = sitesScratchFor(sc, nSites, split ? nSites * nChunks : 0);
-  if (rc) return rc;
-  SitesArgs sa{};
-  sa.plane = d_plane;
-  sa.nSteps = n_steps;
-  sa.ld = ld;
-  sa.M = M;
-  sa.nChunks = nChunks;
-  sa.chunk = chunk;
-  sa.status = b->d_state + (size_t)ST_status * b->ncol;
-  sa.obs = d_obs;
-  sa.sigma = d_sigma;
-  sa.u0 = d_u0;
-  sa.logw = d_logw;
-  sa.w = d_fixed_weights;
-  sa.anc = d_ancestors;
-  sa.total = (int64_t*)sc.d_sites.get();
-  sa.totalOut = d_site_total;
-  sitesLaunch(sa, sc, nSites, split, elem_is_f32 != 0, stream);
-  HIP_TRY(hipGetLastError());
-  sitesInfo(b, split);
-  if (!d_site_total) {
-    rc = sitesCheck(sc, nSites, stream);
-    if (rc) return rc;
-  }
-  return resampleColumns(b, d_ancestors, nullptr, 0, nullptr, with_params, hip_stream);
-}
-
-int sipnet_batch_pf_resample_sites(sipnet_batch* b, double* d_logw, const double* d_u0, const double* d_beta,
-                                   const double* d_ess_min, int32_t with_params, int32_t* d_ancestors,
-                                   int64_t* d_fixed_weights, int64_t* d_site_total, double* d_ess, void* hip_stream) {
-  if (!b || !d_logw || !d_u0 || !d_ancestors || b->ncol > (int64_t)1 << 22) {
-    setError("sipnet_batch_pf_resample_sites: bad argument (device pointers d_logw, d_u0, d_ancestors; at most 4194304 particles)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  if (b->pfPeers) {
-    setError("sipnet_batch_pf_resample_sites: this batch is connected to a filter across ranks (sipnet_batch_pf_connect): "
-             "resample through sipnet_batch_pf_resample_peers");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  int rc = useDevice(b);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  b->pfPre.valid = false;
-  PfScratch& sc = scratchOf(b);
-  rc = pfScratchFor(sc, b->ncol, stream);
-  if (rc) return rc;
-  const int64_t nSites = b->n_sites;
-  int chunk, nChunks;
-  const bool split = sitesGeometry(b, &chunk, &nChunks);
-  rc = sitesScratchFor(sc, nSites, split ? nSites * nChunks : 0);
-  if (rc) return rc;
-  SitesArgs sa{};
+  *split = sitesGeometry(b, &chunk, &nChunks);
+  RC_TRY(sitesScratchFor(b, sc, b->n_sites, *split ? (int64_t)b->n_sites * nChunks : 0));
+  sa = SitesArgs{};
   sa.M = b->n_members;
   sa.nChunks = nChunks;
   sa.chunk = chunk;
@@ -861,34 +740,67 @@ int sipnet_batch_pf_resample_sites(sipnet_batch* b, double* d_logw, const double
   sa.anc = d_ancestors;
   sa.total = (int64_t*)sc.d_sites.get();
   sa.totalOut = d_site_total;
+  return SIPNET_OK;
+}
+// ... and after them: the launches and their error, what sipnet_batch_pf_info reports, the synchronous form's check (invalid:
+// what makes a site's arguments bad at this entry point), the resampling
+static int sitesFinish(const char* who, sipnet_batch* b, SitesArgs& sa, bool split, bool f32, bool given, const char* invalid,
+                       int32_t with_params, hipStream_t stream) {
+  PfScratch& sc = scratchOf(b);
+  sitesLaunch(sa, sc, b->n_sites, split, f32, stream, given);
+  HIP_TRY(hipGetLastError());
+  reportPath(b, !split, split ? 0 : (int32_t)b->n_sites);
+  if (!sa.totalOut) RC_TRY(sitesCheck(sc, b->n_sites, stream, who, invalid));
+  return resampleColumns(b, sa.anc, nullptr, 0, nullptr, with_params, stream);
+}
+
+int sipnet_batch_pf_analysis_sites(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps, int64_t ld,
+                                   const double* d_obs, const double* d_sigma, const double* d_u0, int32_t with_params,
+                                   double* d_logw, int32_t* d_ancestors, int64_t* d_fixed_weights, int64_t* d_site_total,
+                                   void* hip_stream) {
+  const char* who = "sipnet_batch_pf_analysis_sites";
+  if (!b || !d_plane || !d_obs || !d_sigma || !d_u0 || !d_logw || !d_ancestors || n_steps <= 0 || ld < b->ncol ||
+      tooManyColumns(b))
+    return refuse(who, "bad argument (device pointers, n_steps > 0, ld >= ncol, at most 4194304 particles)");
+  SitesArgs sa;
+  bool split;
+  RC_TRY(sitesBegin(who, b, d_u0, d_logw, d_ancestors, d_fixed_weights, d_site_total, (hipStream_t)hip_stream, sa, &split));
+  sa.plane = d_plane;
+  sa.nSteps = n_steps;
+  sa.ld = ld;
+  sa.status = b->d_state + (size_t)ST_status * b->ncol;
+  sa.obs = d_obs;
+  sa.sigma = d_sigma;
+  return sitesFinish(who, b, sa, split, elem_is_f32 != 0, /*given=*/false, "a finite obs needs a finite sigma > 0; 0 <= u0 < 1",
+                     with_params, (hipStream_t)hip_stream);
+}
+
+int sipnet_batch_pf_resample_sites(sipnet_batch* b, double* d_logw, const double* d_u0, const double* d_beta,
+                                   const double* d_ess_min, int32_t with_params, int32_t* d_ancestors,
+                                   int64_t* d_fixed_weights, int64_t* d_site_total, double* d_ess, void* hip_stream) {
+  const char* who = "sipnet_batch_pf_resample_sites";
+  if (!b || !d_logw || !d_u0 || !d_ancestors || tooManyColumns(b))
+    return refuse(who, "bad argument (device pointers d_logw, d_u0, d_ancestors; at most 4194304 particles)");
+  SitesArgs sa;
+  bool split;
+  RC_TRY(sitesBegin(who, b, d_u0, d_logw, d_ancestors, d_fixed_weights, d_site_total, (hipStream_t)hip_stream, sa, &split));
   sa.beta = d_beta;
   sa.essMin = d_ess_min;
   sa.ess = d_ess;
-  sitesLaunch(sa, sc, nSites, split, false, stream, /*given=*/true);
-  HIP_TRY(hipGetLastError());
-  sitesInfo(b, split);
-  if (!d_site_total) {
-    rc = sitesCheck(sc, nSites, stream, "sipnet_batch_pf_resample_sites",
-                    "0 <= u0 < 1, a finite beta > 0, an ess_min that is not NaN, no +inf log-weight");
-    if (rc) return rc;
-  }
-  return resampleColumns(b, d_ancestors, nullptr, 0, nullptr, with_params, hip_stream);
+  return sitesFinish(who, b, sa, split, false, /*given=*/true,
+                     "0 <= u0 < 1, a finite beta > 0, an ess_min that is not NaN, no +inf log-weight", with_params,
+                     (hipStream_t)hip_stream);
 }
 
 // ---- series likelihood weights ---------------------------------------------------------------------------------------
-static int loglikRefuse(const std::string& why) {
-  setError("sipnet_batch_series_loglik: " + why);
-  return SIPNET_ERR_BAD_ARGUMENT;
-}
+static int loglikRefuse(const std::string& why) { return refuse("sipnet_batch_series_loglik", why); }
 // the synchronous form's check: obs and sd read back, the first site and term with bad input named
 static int loglikCheck(const sipnet_batch* b, int32_t n_terms, const sipnet_loglik_term* terms, hipStream_t stream) {
   std::vector<double> obs, sd;
   for (int q = 0; q < n_terms; q++) {
     const size_t n = (size_t)b->n_sites * (size_t)terms[q].rows;
-    obs.resize(n);
-    sd.resize(n);
-    HIP_TRY(hipMemcpyAsync(obs.data(), terms[q].d_obs, n * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(sd.data(), terms[q].d_sd, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    RC_TRY(readBack(obs, terms[q].d_obs, n, stream));
+    RC_TRY(readBack(sd, terms[q].d_sd, n, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (size_t i = 0; i < n; i++) {
       const double y = obs[i];
@@ -908,7 +820,7 @@ int sipnet_batch_series_loglik(sipnet_batch* b, int32_t n_terms, const sipnet_lo
   if (!b || !terms || !d_loglik) return loglikRefuse("a NULL batch, terms or d_loglik");
   if (n_terms < 1 || n_terms > kLoglikMaxTerms) return loglikRefuse("n_terms must be 1.." + std::to_string(kLoglikMaxTerms));
   if (ld < b->ncol) return loglikRefuse("ld < ncol");
-  if (b->ncol > (int64_t)1 << 22) return loglikRefuse("at most 4194304 columns");
+  if (tooManyColumns(b)) return loglikRefuse("at most 4194304 columns");
   if (path < 0 || path > 2) return loglikRefuse("path must be 0 (auto), 1 or 2");
   LoglikArgs a{};
   int64_t tilesTotal = 0;
@@ -966,8 +878,8 @@ int sipnet_batch_series_loglik(sipnet_batch* b, int32_t n_terms, const sipnet_lo
     return SIPNET_OK;
   }
   PfScratch& sc = scratchOf(b);
-  RC_TRY(sc.d_loglik.reserve((size_t)tilesTotal * (size_t)b->ncol));
-  RC_TRY(sc.d_loglikUsed.reserve((size_t)tilesTotal * (size_t)nSites));
+  RC_TRY(growScratch(b, sc.d_loglik, (size_t)tilesTotal * (size_t)b->ncol));
+  RC_TRY(growScratch(b, sc.d_loglikUsed, (size_t)tilesTotal * (size_t)nSites));
   a.partial = sc.d_loglik;
   a.tileUsed = sc.d_loglikUsed;
   const dim3 grid((unsigned)(groups * tilesTotal));
@@ -987,18 +899,15 @@ void sipnet_rejuvenate_normals(uint64_t seed, uint32_t draw, uint32_t stream, ui
   rejNormals((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, stream, member, block, true, z);
 }
 
-static int rejRefuse(const std::string& why) {
-  setError("sipnet_batch_pf_rejuvenate: " + why);
-  return SIPNET_ERR_BAD_ARGUMENT;
-}
+static int rejRefuse(const std::string& why) { return refuse("sipnet_batch_pf_rejuvenate", why); }
 // the synchronous form's check: shrink, pool_sd and the totals read back, the first selected site with bad input named
 static int rejCheck(const sipnet_batch* b, const RejArgs& a, hipStream_t stream) {
   const size_t nSites = (size_t)b->n_sites;
-  std::vector<double> shrink(a.nPrm > 0 ? nSites : 0), sd(a.mask ? nSites * kRejPools : 0);
-  std::vector<int64_t> total(a.siteTotal ? nSites : 0);
-  if (a.nPrm > 0) HIP_TRY(hipMemcpyAsync(shrink.data(), a.shrink, shrink.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (a.mask) HIP_TRY(hipMemcpyAsync(sd.data(), a.poolSd, sd.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (a.siteTotal) HIP_TRY(hipMemcpyAsync(total.data(), a.siteTotal, total.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  std::vector<double> shrink, sd;
+  std::vector<int64_t> total;
+  RC_TRY(readBack(shrink, a.nPrm > 0 ? a.shrink : nullptr, nSites, stream));
+  RC_TRY(readBack(sd, a.mask ? a.poolSd : nullptr, nSites * kRejPools, stream));
+  RC_TRY(readBack(total, a.siteTotal, nSites, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   for (size_t s = 0; s < nSites; s++)
     if (rejSiteInputs(shrink.data(), sd.data(), a.siteTotal ? total.data() : nullptr, a.nPrm, a.mask, (int64_t)s) == kRejBadInput)
@@ -1013,10 +922,7 @@ static int rejScratch(sipnet_batch* b, PfScratch& sc, RejArgs& a, int32_t* d_sit
   const size_t nPart = nCnt * kRejPrm, nStat = split ? nSites * 2 * kRejPrm : 0;
   const size_t nInt = nSites * 4 + 2 * nCnt + (split ? 2 * nSites : 0);
   const size_t bytes = (nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t);
-  if (sc.d_rejuv.capacity() < bytes) {
-    RC_TRY(waitIdle(b));   // (the old block may still be read by a launch in flight)
-    RC_TRY(sc.d_rejuv.reserve(bytes));
-  }
+  RC_TRY(growScratch(b, sc.d_rejuv, bytes));
   a.part = (double*)sc.d_rejuv.get();
   a.stat = a.part + nPart;
   int32_t* ints = (int32_t*)(a.stat + nStat);
@@ -1040,7 +946,7 @@ int sipnet_batch_pf_rejuvenate(sipnet_batch* b, int32_t n_params, const sipnet_e
   if (pool_mask && !d_pool_sd) return rejRefuse("a pool_mask needs d_pool_sd");
   if (n_params == 0 && pool_mask == 0) return rejRefuse("nothing to do (n_params == 0 and pool_mask == 0)");
   if (!b) return rejRefuse("a NULL batch");
-  if (b->ncol > (int64_t)1 << 22) return rejRefuse("at most 4194304 columns");
+  if (tooManyColumns(b)) return rejRefuse("at most 4194304 columns");
   if (b->planDirty) return rejRefuse("needs a batch that was set up (sipnet_batch_setup): the members' status is read");
   if (b->pfPeers) return rejRefuse("this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
   int rc = useDevice(b);
@@ -1049,16 +955,7 @@ int sipnet_batch_pf_rejuvenate(sipnet_batch* b, int32_t n_params, const sipnet_e
   const int64_t M = b->n_members, nSites = b->n_sites;
   a.nPrm = n_params;
   a.mask = pool_mask;
-  a.leaf = a.wood = a.fineRoot = a.opt = a.tmin = -1;
-  for (int k = 0; k < n_params; k++) {
-    const int p = params[k].index;
-    a.prmRow[k] = p;
-    if (p == SP_leafAllocation) a.leaf = k;
-    if (p == SP_woodAllocation) a.wood = k;
-    if (p == SP_fineRootAllocation) a.fineRoot = k;
-    if (p == SP_psnTOpt) a.opt = k;
-    if (p == SP_psnTMin) a.tmin = k;
-  }
+  a.rows = derivedRowsOf(n_params, params, a.prmRow);
   a.shrink = d_shrink;
   a.poolSd = d_pool_sd;
   a.key0 = (uint32_t)(seed & 0xffffffffu);
@@ -1073,17 +970,8 @@ int sipnet_batch_pf_rejuvenate(sipnet_batch* b, int32_t n_params, const sipnet_e
     rc = rejCheck(b, a, stream);
     if (rc) return rc;
   }
-  // the bookkeeping of an analysis that writes state and parameters (sipnet_batch_enkf_analysis_joint's)
-  b->pfPre.valid = false;
-  b->pfArm.set = false;
-  rc = orderBehindBusy(b, stream);
+  rc = beginWrite(b, stream, /*ownRows=*/n_params > 0);   // (every column its own rows: the move writes them)
   if (rc) return rc;
-  rc = flushParams(b, stream);
-  if (rc) return rc;
-  if (n_params > 0) {
-    rc = materializeParams(b, stream);   // (every column its own rows: the move writes them)
-    if (rc) return rc;
-  }
   a.state = b->d_state;
   a.prm = b->d_prm;
   a.siteStatus = b->d_siteStatus;
@@ -1105,10 +993,7 @@ int sipnet_batch_pf_rejuvenate(sipnet_batch* b, int32_t n_params, const sipnet_e
     hipLaunchKernelGGL(rejInfoKernel, sites, dim3(256), 0, stream, a);
   }
   HIP_TRY(hipGetLastError());
-  b->pfInfo.fused = split ? 0 : 1;
-  b->pfInfo.grid = split ? 0 : (int32_t)nSites;
-  b->pfInfo.budget = 0;
-  b->pfInfo.nSlots = b->ncol;
+  reportPath(b, !split, split ? 0 : (int32_t)nSites);
   return markBusy(b, stream);
 }
 
@@ -1127,14 +1012,10 @@ static_assert(sizeof(hipIpcMemHandle_t) <= sizeof(((sipnet_pf_peer*)nullptr)->ip
 extern "C" {
 
 int sipnet_batch_pf_publish(sipnet_batch* b, int32_t with_params, sipnet_pf_peer* out) {
-  if (!b || !out) {
-    setError("sipnet_batch_pf_publish: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  if (b->n_sites != 1) {
-    setError("sipnet_batch_pf_publish: particles of different sites must not mix (n_sites must be 1)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !out)
+    return refuse("sipnet_batch_pf_publish", "bad argument");
+  if (b->n_sites != 1)
+    return refuse("sipnet_batch_pf_publish", "particles of different sites must not mix (n_sites must be 1)");
   int rc = useDevice(b);
   if (rc) return rc;
   rc = ensureSpares(b, /*state=*/true, /*params=*/with_params != 0, /*index=*/false);
@@ -1177,10 +1058,7 @@ int sipnet_batch_pf_publish(sipnet_batch* b, int32_t with_params, sipnet_pf_peer
 }
 
 // (a refusal of connect; the caller takes the half-made table down: closePeers)
-static int connectRefused(const std::string& why, int code) {
-  setError("sipnet_batch_pf_connect: " + why);
-  return code;
-}
+static int connectRefused(const std::string& why, int code) { return refuse("sipnet_batch_pf_connect", why, code); }
 // connect, for rank s: its descriptor agrees with mine, its particles are counted, and its eight matrices are addressable
 // from here -- same process (the node object): the addresses themselves, and peer access to its device; another process:
 // its allocations mapped (dmabuf IPC)
@@ -1251,10 +1129,8 @@ static int fillBank(sipnet_batch* b, const PfPeers* pp) {
 // Four steps: my own descriptor is this batch as it stands | the old connection goes (before the peers are looked at: a failed
 // connect leaves none) | every peer is mapped (mapPeer) | the parameter bank (fillBank) and the crossing counter
 int sipnet_batch_pf_connect(sipnet_batch* b, int32_t world, int32_t rank, const sipnet_pf_peer* peers) {
-  if (!b || !peers || world < 1 || world > kMaxPeers || rank < 0 || rank >= world) {
-    setError("sipnet_batch_pf_connect: bad argument (world <= 16)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !peers || world < 1 || world > kMaxPeers || rank < 0 || rank >= world)
+    return refuse("sipnet_batch_pf_connect", "bad argument (world <= 16)");
   int rc = useDevice(b);
   if (rc) return rc;
   const sipnet_pf_peer& me = peers[rank];
@@ -1278,7 +1154,7 @@ int sipnet_batch_pf_connect(sipnet_batch* b, int32_t world, int32_t rank, const 
     if (rc) return fail(rc);
     generic = generic || peers[s].generic_exponents != 0;
   }
-  if ((int64_t)world * pp->nmax > (int64_t)1 << 22) return fail(connectRefused("more than 4 194 304 weight slots", SIPNET_ERR_BAD_ARGUMENT));
+  if ((int64_t)world * pp->nmax > kMaxColumns) return fail(connectRefused("more than 4 194 304 weight slots", SIPNET_ERR_BAD_ARGUMENT));
   // particles carry their parameters between ranks: every rank runs the kernel variant the most general
   // parameter set anywhere needs (decided here, once -- not by a device -> host check after every exchange)
   if (generic && me.with_params) b->genericExponents = true;
@@ -1307,10 +1183,8 @@ int64_t sipnet_batch_pf_block_len(const sipnet_batch* b) {
 
 int sipnet_batch_pf_local_weights(sipnet_batch* b, const void* d_plane, int32_t elem_is_f32, int32_t n_steps,
                                   int64_t ld, double obs, double sigma, double* d_block, void* hip_stream) {
-  if (!b || !d_block) {
-    setError("sipnet_batch_pf_local_weights: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !d_block)
+    return refuse("sipnet_batch_pf_local_weights", "bad argument");
   const int64_t nmax = b->pfPeers ? b->pfPeers->nmax : b->ncol;
   // the forecast's launch was told of this analysis (sipnet_batch_pf_arm with d_logw = this block) and has left the
   // log-weights in it: only the 256-wide maxima and the empty slots remain (wavefront k covers columns 64 k .. 64 k + 63
@@ -1361,10 +1235,8 @@ static int peerTable(const sipnet_batch* b, PeerFilter* f) {
   f->nTotal = pp.nTotal;
   f->first = pp.first;
   f->withParams = pp.withParams != 0;
-  if (tab.state[pp.rank] != b->d_state || (f->byIndex && tab.third[pp.rank] != (const void*)b->d_prmId)) {
-    setError("sipnet_batch_pf_resample_peers: the batch was resampled behind the peers' back");
-    return SIPNET_ERR_INTERNAL;
-  }
+  if (tab.state[pp.rank] != b->d_state || (f->byIndex && tab.third[pp.rank] != (const void*)b->d_prmId))
+    return refuse("sipnet_batch_pf_resample_peers", "the batch was resampled behind the peers' back", SIPNET_ERR_INTERNAL);
   tab.crossing = b->d_pfCrossing;
   return SIPNET_OK;
 }
@@ -1428,14 +1300,10 @@ static int peerGather(sipnet_batch* b, const PeerFilter& f, const int32_t* d_anc
 
 int sipnet_batch_pf_resample_peers(sipnet_batch* b, const double* d_gathered, double u0, int32_t* d_ancestors,
                                    int64_t* d_total, void* hip_stream) {
-  if (!b || !d_gathered || !d_ancestors || !(u0 >= 0.0) || !(u0 < 1.0)) {
-    setError("sipnet_batch_pf_resample_peers: bad argument (0 <= u0 < 1)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
-  if (b->n_sites != 1) {
-    setError("sipnet_batch_pf_resample_peers: particles of different sites must not mix (n_sites must be 1)");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !d_gathered || !d_ancestors || !(u0 >= 0.0) || !(u0 < 1.0))
+    return refuse("sipnet_batch_pf_resample_peers", "bad argument (0 <= u0 < 1)");
+  if (b->n_sites != 1)
+    return refuse("sipnet_batch_pf_resample_peers", "particles of different sites must not mix (n_sites must be 1)");
   int rc = useDevice(b);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -1443,11 +1311,9 @@ int sipnet_batch_pf_resample_peers(sipnet_batch* b, const double* d_gathered, do
   if (rc) return rc;
   PeerFilter f;
   f.byIndex = b->pfPeers && b->pfPeers->byIndex;
-  if (f.byIndex && (b->pfPeers->bankLost || !b->d_prmBank)) {
-    setError("sipnet_batch_pf_resample_peers: this rank's parameters were set anew (or moved as rows by sipnet_batch_resample) after "
-             "sipnet_batch_pf_connect replicated them on every rank: publish and connect again");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (f.byIndex && (b->pfPeers->bankLost || !b->d_prmBank))
+    return refuse("sipnet_batch_pf_resample_peers", "this rank's parameters were set anew (or moved as rows by "
+                  "sipnet_batch_resample) after sipnet_batch_pf_connect replicated them on every rank: publish and connect again");
   if (!f.byIndex) {
     rc = materializeParams(b, stream);   // (peers read a particle's parameter rows by its column)
     if (rc) return rc;
@@ -1471,10 +1337,8 @@ int sipnet_batch_pf_resample_peers(sipnet_batch* b, const double* d_gathered, do
 
 // what the last analysis did, and how many of this rank's particles have crossed ranks (see sipnet_amd.h)
 int sipnet_batch_pf_info(sipnet_batch* b, sipnet_pf_info* out, void* hip_stream) {
-  if (!b || !out) {
-    setError("sipnet_batch_pf_info: bad argument");
-    return SIPNET_ERR_BAD_ARGUMENT;
-  }
+  if (!b || !out)
+    return refuse("sipnet_batch_pf_info", "bad argument");
   int rc = useDevice(b);
   if (rc) return rc;
   memset(out, 0, sizeof *out);

@@ -20,7 +20,6 @@ constexpr int kRejPrm = SIPNET_ENKF_MAX_PARAMS;   // listed parameter rows at mo
 constexpr int kRejPools = 13;                     // state slots 0..12
 constexpr int kRejDone = SIPNET_REJUVENATE_DONE, kRejTooFew = SIPNET_REJUVENATE_TOO_FEW, kRejBadInput = SIPNET_REJUVENATE_BAD_INPUT,
               kRejNotSelected = SIPNET_REJUVENATE_NOT_SELECTED;
-constexpr double kRejTiny = 0.000001;             // TINY, common/util.h
 
 // Philox4x32-10: ten rounds of two 32 x 32 -> 64 bit products, the key bumped by the Weyl constants between rounds
 __host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -72,7 +71,7 @@ struct RejArgs {
   int32_t nPrm, mask;
   int32_t prmRow[kRejPrm];                 // the listed rows of prm, in the caller's order
   double lo[kRejPrm], hi[kRejPrm];         // their bounds, converted units
-  int32_t leaf, wood, fineRoot, opt, tmin; // where leafAllocation .. psnTMin are among the listed rows, or -1
+  DerivedRows rows;                        // where leafAllocation .. psnTMin are among the listed rows
   const double* shrink;                    // [n_sites] a, or null (nPrm == 0)
   const double* poolSd;                    // [n_sites][13], or null (mask == 0)
   uint32_t key0, key1, draw;
@@ -117,24 +116,6 @@ __device__ __forceinline__ int rejPerturbed(const RejArgs& a, int s) {
     if ((a.mask & (1 << p)) && a.poolSd[(int64_t)s * kRejPools + p] > 0.0) n++;
   return n;
 }
-__device__ __forceinline__ double rejWaveSum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// the sum of an int over the workgroup's 256 threads, to every thread (ints: any order); smI[4], barriers on both sides
-__device__ __forceinline__ int rejBlockCount(int* smI, int v) {
-  const int tid = (int)threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) smI[tid >> 6] = v;
-  __syncthreads();
-  return smI[0] + smI[1] + smI[2] + smI[3];
-}
-__device__ __forceinline__ double rejCombine4(const double* smW, int q) {   // smW [4][kRejPrm]: the waves in order
-  return ((smW[q] + smW[kRejPrm + q]) + smW[2 * kRejPrm + q]) + smW[3 * kRejPrm + q];
-}
 
 // One live member of a code-1 site: its listed rows moved (x(k): row k's value now; mean, hsd = h sd per row; shrinkA = a,
 // rows untouched when it is 1), its masked pools perturbed, the limits, and -- unless the member keeps everything -- the
@@ -148,6 +129,11 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
   bool ok = true;
   double nv[kRejPrm];
   double leaf = 0.0, wood = 0.0, fine = 0.0, opt = 0.0, tmin = 0.0;
+  // the member's value of one of the five rows that the derived rows depend on: a listed one's from its register
+  const auto now = [&](int k, int row) {
+    if (k < 0) return a.prm[(int64_t)row * a.ncol + col];
+    return row == SP_leafAllocation ? leaf : row == SP_woodAllocation ? wood : row == SP_fineRootAllocation ? fine : row == SP_psnTOpt ? opt : tmin;
+  };
   if (rows) {
 #pragma unroll
     for (int blk = 0; blk < kRejPrm / 4; blk++) {
@@ -165,19 +151,14 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
         v = v < a.lo[k] ? a.lo[k] : (v > a.hi[k] ? a.hi[k] : v);
         ok = ok && fabs(v) < INFINITY;
         nv[k] = v;
-        if (k == a.leaf) leaf = v;
-        if (k == a.wood) wood = v;
-        if (k == a.fineRoot) fine = v;
-        if (k == a.opt) opt = v;
-        if (k == a.tmin) tmin = v;
+        if (k == a.rows.leaf) leaf = v;
+        if (k == a.rows.wood) wood = v;
+        if (k == a.rows.fineRoot) fine = v;
+        if (k == a.rows.opt) opt = v;
+        if (k == a.rows.tmin) tmin = v;
       }
     }
-    if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0) {
-      if (a.leaf < 0) leaf = a.prm[(int64_t)SP_leafAllocation * a.ncol + col];
-      if (a.wood < 0) wood = a.prm[(int64_t)SP_woodAllocation * a.ncol + col];
-      if (a.fineRoot < 0) fine = a.prm[(int64_t)SP_fineRootAllocation * a.ncol + col];
-      if (leaf >= 1.0 || wood >= 1.0 || fine >= 1.0 || 1 - leaf - wood - fine < 0) ok = false;
-    }
+    ok = allocationsOk(a.rows, now) && ok;
   }
   // the pools: the masked slots with an sd above 0 perturbed and clipped; hasSufficientBiomass (sipnet.c:1530-1536) of the result
   double f[kRejPools];
@@ -197,15 +178,13 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
       const bool read = moved[p] || p == ST_plantWoodC || p == ST_plantCAccountingDelta || p == ST_fineRootC || p == ST_coarseRootC;
       double v = read ? a.state[(int64_t)p * a.ncol + col] : 0.0;
       if (moved[p]) {
-        v = v + q * z[i];
-        if (p != ST_plantCAccountingDelta && v < 0.0) v = 0.0;
+        v = poolLimit(p, v + q * z[i]);
         ok = ok && fabs(v) < INFINITY;
       }
       f[p] = v;
     }
   }
-  const double totalWood = f[ST_plantWoodC] + f[ST_plantCAccountingDelta], totalRoot = f[ST_fineRootC] + f[ST_coarseRootC];
-  ok = ok && f[ST_plantWoodC] > kRejTiny && totalWood > kRejTiny && totalRoot > kRejTiny;
+  ok = ok && sufficientBiomass(f[ST_plantWoodC], f[ST_plantCAccountingDelta], f[ST_fineRootC], f[ST_coarseRootC]);
   if (!ok) return false;
 #pragma unroll
   for (int p = 0; p < kRejPools; p++)
@@ -216,14 +195,7 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
       if (k >= a.nPrm) break;
       a.prm[(int64_t)a.prmRow[k] * a.ncol + col] = nv[k];
     }
-    // the derived rows that depend on listed ones, by convertParamsKernel's expressions
-    if (a.opt >= 0 || a.tmin >= 0) {
-      if (a.opt < 0) opt = a.prm[(int64_t)SP_psnTOpt * a.ncol + col];
-      if (a.tmin < 0) tmin = a.prm[(int64_t)SP_psnTMin * a.ncol + col];
-      a.prm[(int64_t)SP_psnTMax * a.ncol + col] = opt + (opt - tmin);
-    }
-    if (a.leaf >= 0 || a.wood >= 0 || a.fineRoot >= 0)
-      a.prm[(int64_t)SP_coarseRootAllocation * a.ncol + col] = 1 - leaf - wood - fine;
+    writeDerivedRows(a.prm, a.ncol, col, a.rows, now);
   }
   return true;
 }
@@ -231,27 +203,14 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
 // ---- one workgroup per site: sites of one chunk -----------------------------------------------------------------------
 // A site of at most 256 members is one chunk, and the per-chunk launches would have one workgroup per site too: here their
 // six launches are one, and the listed rows are read from HBM once (staged in LDS for the three sweeps).  The sums are the
-// split path's: the chunk's sum by rejCombine4, added to 0.0.
+// split path's: the chunk's sum by combine4, added to 0.0 (the one-chunk siteSums).
 struct RejGroupLds {
+  static constexpr int kCap = kRejPrm;
   double rows[kRejPrm][256];   // the listed rows of the site's columns
   double smW[4 * kRejPrm];
   double mean[kRejPrm], hsd[kRejPrm];
   int smI[4];
 };
-// the site's sums of val(q), q < V, over the workgroup's threads -> every thread gets the sum of row tid (tid < V)
-template <class F>
-__device__ __forceinline__ double rejSiteSums(RejGroupLds& g, int V, F val) {
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  __syncthreads();   // (the last sums have been read)
-  for (int q = 0; q < V; q++) {
-    const double v = rejWaveSum(val(q));
-    if (lane == 0) g.smW[wave * kRejPrm + q] = v;
-  }
-  __syncthreads();
-  double t = 0.0;
-  if (tid < V) t += rejCombine4(g.smW, tid);
-  return t;
-}
 
 __global__ __launch_bounds__(256) void rejGroupKernel(RejArgs a) {
   __shared__ RejGroupLds g;
@@ -259,7 +218,7 @@ __global__ __launch_bounds__(256) void rejGroupKernel(RejArgs a) {
   const int64_t j = tid, col = (int64_t)s * a.M + j;
   int code = rejSiteInputs(a.shrink, a.poolSd, a.siteTotal, a.nPrm, a.mask, s);
   const bool live = rejLive(a, s, j);
-  const int n = rejBlockCount(g.smI, live ? 1 : 0);
+  const int n = blockCount(g, live ? 1 : 0);
   if (code == kRejDone && n < 2) code = kRejTooFew;
   if (code != kRejDone) {
     if (tid == 0) {
@@ -271,10 +230,10 @@ __global__ __launch_bounds__(256) void rejGroupKernel(RejArgs a) {
   const double shrinkA = a.nPrm > 0 ? a.shrink[s] : 1.0;
   if (a.nPrm > 0 && shrinkA != 1.0) {
     for (int q = 0; q < a.nPrm; q++) g.rows[q][tid] = live ? a.prm[(int64_t)a.prmRow[q] * a.ncol + col] : 0.0;
-    const double sum = rejSiteSums(g, a.nPrm, [&](int q) { return g.rows[q][tid]; });
+    const double sum = siteSums(g, a.nPrm, [&](int q) { return g.rows[q][tid]; });
     if (tid < a.nPrm) g.mean[tid] = sum / (double)n;
     __syncthreads();
-    const double csum = rejSiteSums(g, a.nPrm, [&](int q) {
+    const double csum = siteSums(g, a.nPrm, [&](int q) {
       const double d = g.rows[q][tid] - g.mean[q];
       return live ? d * d : 0.0;
     });
@@ -283,7 +242,7 @@ __global__ __launch_bounds__(256) void rejGroupKernel(RejArgs a) {
   }
   int kept = 0;
   if (live) kept = rejMember(a, s, j, shrinkA, g.mean, g.hsd, [&](int k) { return g.rows[k][tid]; }) ? 0 : 1;
-  const int nKept = rejBlockCount(g.smI, kept);
+  const int nKept = blockSum(g.smI, kept);
   if (tid == 0) {
     int32_t* o = a.info + 4 * (int64_t)s;
     o[0] = kRejDone, o[1] = rejPerturbed(a, s), o[2] = n, o[3] = nKept;
@@ -300,7 +259,7 @@ __global__ __launch_bounds__(256) void rejChunkKernel(RejArgs a, int pass) {
   const int64_t j = (int64_t)c * 256 + tid, col = (int64_t)s * a.M + j;
   const bool live = rejLive(a, s, j);
   if (pass == 0) {
-    const int n = rejBlockCount(smI, live ? 1 : 0);
+    const int n = blockSum(smI, live ? 1 : 0);
     if (tid == 0) a.cnt[(int64_t)s * a.nCh + c] = n;
   } else if (a.site[2 * (int64_t)s] != kRejDone) {
     return;
@@ -317,11 +276,11 @@ __global__ __launch_bounds__(256) void rejChunkKernel(RejArgs a, int pass) {
         v = d * d;
       }
     }
-    v = rejWaveSum(v);
+    v = waveSum(v);
     if (lane == 0) smW[wave * kRejPrm + q] = v;
   }
   __syncthreads();
-  if (tid < a.nPrm) a.part[((int64_t)s * a.nCh + c) * kRejPrm + tid] = rejCombine4(smW, tid);
+  if (tid < a.nPrm) a.part[((int64_t)s * a.nCh + c) * kRejPrm + tid] = combine4<kRejPrm>(smW, tid);
 }
 // the site's sums from its chunks', in chunk order.  pass 0: the live count, the code, the means; pass 1: h sd
 __global__ __launch_bounds__(256) void rejSiteKernel(RejArgs a, int pass) {
@@ -331,7 +290,7 @@ __global__ __launch_bounds__(256) void rejSiteKernel(RejArgs a, int pass) {
   if (pass == 0) {
     int live = 0;
     for (int c = tid; c < a.nCh; c += 256) live += a.cnt[(int64_t)s * a.nCh + c];
-    n = rejBlockCount(smI, live);
+    n = blockSum(smI, live);
     int code = rejSiteInputs(a.shrink, a.poolSd, a.siteTotal, a.nPrm, a.mask, s);
     if (code == kRejDone && n < 2) code = kRejTooFew;
     if (tid == 0) a.site[2 * (int64_t)s] = code, a.site[2 * (int64_t)s + 1] = n;
@@ -373,7 +332,7 @@ __global__ __launch_bounds__(256) void rejApplyKernel(RejArgs a) {
   int kept = 0;
   if (rejLive(a, s, j))
     kept = rejMember(a, s, j, shrinkA, stat, stat + kRejPrm, [&](int k) { return a.prm[(int64_t)a.prmRow[k] * a.ncol + col]; }) ? 0 : 1;
-  const int nKept = rejBlockCount(smI, kept);
+  const int nKept = blockSum(smI, kept);
   if (tid == 0) a.kept[(int64_t)s * a.nCh + c] = nKept;
 }
 __global__ __launch_bounds__(256) void rejInfoKernel(RejArgs a) {
@@ -383,7 +342,7 @@ __global__ __launch_bounds__(256) void rejInfoKernel(RejArgs a) {
   int kept = 0;
   if (code == kRejDone)
     for (int c = tid; c < a.nCh; c += 256) kept += a.kept[(int64_t)s * a.nCh + c];
-  const int nKept = rejBlockCount(smI, kept);
+  const int nKept = blockSum(smI, kept);
   if (tid == 0) {
     int32_t* o = a.info + 4 * (int64_t)s;
     o[0] = code, o[1] = code == kRejDone ? rejPerturbed(a, s) : 0, o[2] = a.site[2 * (int64_t)s + 1], o[3] = nKept;

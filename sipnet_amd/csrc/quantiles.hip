@@ -28,8 +28,11 @@
 #include <string>
 
 #include "batch_impl.h"
+#include "site_host.h"
 
 namespace {
+
+#include "site_device.h"
 
 constexpr int kQMax = SIPNET_QUANTILES_MAX;
 constexpr int kTargets = 2 * kQMax;              // order statistics of a call at most: x_(lo) and x_(lo+1) per quantile
@@ -276,11 +279,8 @@ __global__ __launch_bounds__(256) void quantSortKernel(QuantArgs a, int P) {
         s1 += fabs(d);
         s2 += (double)(2 * (i + 1) - n - 1) * d;
       }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      s1 += __shfl_xor(s1, off, 64);
-      s2 += __shfl_xor(s2, off, 64);
-    }
+    s1 = waveSum(s1);
+    s2 = waveSum(s2);
     if ((tid & 63) == 0) {
       sW[2 * (tid >> 6)] = s1;
       sW[2 * (tid >> 6) + 1] = s2;
@@ -397,11 +397,6 @@ __global__ __launch_bounds__(256) void quantSelectKernel(QuantArgs a) {
     positionOf(n, a.q[tid], &lo, &g);
     a.quant[(int64_t)tid * a.cells + c.cell] = quantileOf(valueOf(prefix[slot[2 * tid]]), valueOf(prefix[slot[2 * tid + 1]]), g);
   }
-}
-
-int refuse(const char* name, const std::string& why) {
-  setError(std::string(name) + ": " + why);
-  return SIPNET_ERR_BAD_ARGUMENT;
 }
 
 // n_q and the q of a call: 0, or the refusal

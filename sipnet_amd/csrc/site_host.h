@@ -1,0 +1,59 @@
+// site_host.h -- the host side that the per-site analyses share (enkf.hip, pf.hip, quantiles.hip): a refusal, the limit on a
+// batch's columns, the bookkeeping of a call that writes the batch, a scratch block grown, what sipnet_batch_pf_info reports
+// of the last call, and the copies of a synchronous form's check.  batch_impl.h stays the batch object and the stream bookkeeping.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "batch_impl.h"
+
+namespace sipnet {
+
+// a refusal: "`name`: `why`" is the thread's error, `code` the status
+inline int refuse(const char* name, const std::string& why, int code = SIPNET_ERR_BAD_ARGUMENT) {
+  setError(std::string(name) + ": " + why);
+  return code;
+}
+
+// the columns a batch may have in these calls (4 194 304); every caller words its own refusal
+constexpr int64_t kMaxColumns = (int64_t)1 << 22;
+inline bool tooManyColumns(const sipnet_batch* b) { return b->ncol > kMaxColumns; }
+
+// An analysis is about to write the batch's state on `stream`: a forecast's log-weights belong to the particles as they
+// were, the stream goes behind the batch's last launch, pending parameters are converted; ownRows: and every column gets
+// its own parameter rows, because the analysis writes them too.
+inline int beginWrite(sipnet_batch* b, hipStream_t stream, bool ownRows) {
+  b->pfPre.valid = false;
+  b->pfArm.set = false;
+  RC_TRY(orderBehindBusy(b, stream));
+  RC_TRY(flushParams(b, stream));
+  return ownRows ? materializeParams(b, stream) : SIPNET_OK;
+}
+
+// A scratch block of the batch with room for `count` elements, as dev_buf.h asks: the host waits for the batch's launches
+// before the block grows (the old one may still be read by a launch in flight), and only then.  This block alone: another
+// may be in use by this very call.
+template <class T>
+int growScratch(sipnet_batch* b, DevBuf<T>& block, size_t count) {
+  if (block.capacity() >= count) return SIPNET_OK;
+  RC_TRY(waitIdle(b));
+  return block.reserve(count);
+}
+
+// what sipnet_batch_pf_info reports of a per-site call: one workgroup per site (fused, grid = the sites) or launches per stage
+inline void reportPath(sipnet_batch* b, bool fused, int32_t grid) {
+  b->pfInfo.fused = fused ? 1 : 0;
+  b->pfInfo.grid = grid;
+  b->pfInfo.budget = 0;
+  b->pfInfo.nSlots = b->ncol;
+}
+
+// a synchronous form's check: n elements at d (null: none) queued for h on `stream`; the caller waits for the stream once
+template <class T>
+int readBack(std::vector<T>& h, const T* d, size_t n, hipStream_t stream) {
+  h.resize(d ? n : 0);
+  if (!h.empty()) HIP_TRY(hipMemcpyAsync(h.data(), d, h.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+  return SIPNET_OK;
+}
+
+}  // namespace sipnet
