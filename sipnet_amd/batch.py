@@ -243,27 +243,40 @@ class Batch:
     def run_stats(self, step0=0, n_steps=None, planes=None, stats=None):
         """run() + the ensemble statistics of the three planes from the same launch
         (sipnet_batch_run_stats): stats[3][n_steps][n_sites][2] = sum, sum of squares over each
-        site's members.  Returns (planes, stats)."""
+        site's members.  planes: a [3][>= n_steps][ld >= ncol] device tensor of the batch's output
+        dtype whose three planes are contiguous (a slice along the step axis is; the row pitch is
+        ld, columns past ncol are neither read nor written).  Returns (planes, stats)."""
         t = self._torch
         n_steps = self._steps(step0, n_steps)
         if planes is None:
             planes, _ = self.alloc_outputs(n_steps, False)
+        ok = (t.is_tensor(planes) and planes.is_cuda and planes.dim() == 3 and planes.shape[0] == 3
+              and planes.dtype == self.out_dtype and planes.shape[1] >= n_steps and planes.shape[2] >= self.ncol)
+        nee, gpp, et = (planes[0], planes[1], planes[2]) if ok else (None, None, None)
+        if not ok or not (nee.is_contiguous() and gpp.is_contiguous() and et.is_contiguous()):
+            raise ValueError(f"run_stats: planes must be a [3][>= {n_steps}][ld >= {self.ncol}] {self.out_dtype} device tensor "
+                             "with contiguous planes")
         if stats is None:
             stats = t.empty((3, n_steps, self.n_sites, 2), dtype=t.float64, device=self.device)
         assert _dense(stats, t.float64)
-        check(self.L.sipnet_batch_run_stats(self.h, step0, n_steps, ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), self.ncol,
-                                            ptr(stats), self._stream()), "run_stats")
+        check(self.L.sipnet_batch_run_stats(self.h, step0, n_steps, ptr(nee), ptr(gpp), ptr(et), planes.shape[2], ptr(stats),
+                                            self._stream()), "run_stats")
         return planes, stats
 
     def reduce_plane(self, plane, stats=None):
-        """Per (step, site) ensemble sum and sum of squares of one output plane
-        [n_steps][ncol] -> stats[n_steps][n_sites][2] (float64, on device)."""
+        """Per (row, site) ensemble sum and sum of squares of one plane: a contiguous 2-D float32 /
+        float64 device tensor [rows][ld >= ncol] (the row pitch is ld; columns past ncol are not read)
+        -> stats[rows][n_sites][2] (float64, on device)."""
         t = self._torch
+        if (not t.is_tensor(plane) or not plane.is_cuda or plane.dim() != 2 or plane.dtype not in (t.float32, t.float64)
+                or not plane.is_contiguous() or plane.shape[1] < self.ncol):
+            raise ValueError(f"reduce_plane: plane must be a contiguous 2-D float32 / float64 device tensor [rows][ld >= {self.ncol}]")
         n_steps = plane.shape[0]
         if stats is None:
             stats = t.empty((n_steps, self.n_sites, 2), dtype=t.float64, device=self.device)
-        check(self.L.sipnet_batch_reduce_plane(self.h, ptr(plane), int(plane.dtype == t.float32), n_steps, self.ncol,
-                                               ptr(stats), self._stream()), "reduce_plane")
+        elif not t.is_tensor(stats) or not _dense(stats, t.float64, n_steps * self.n_sites * 2):
+            raise ValueError(f"reduce_plane: stats must be a contiguous float64 device tensor of {n_steps} x {self.n_sites} x 2")
+        check(self.L.sipnet_batch_reduce_plane(self.h, *self._plane(plane), ptr(stats), self._stream()), "reduce_plane")
         return stats
 
     def plane_quantiles(self, series, q, live_only=True, obs=None, want_crps=None, want_rank=None, path=0, out=None):

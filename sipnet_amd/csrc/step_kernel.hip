@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 
 namespace sipnet {
@@ -1204,102 +1205,112 @@ __global__ __launch_bounds__(64) void stepKernel(KernelArgs a) {
 // ensemble statistics of an output plane: per (step, site) sum and sum of
 // squares over members.  One wavefront per (step, site); lanes stride over the
 // site's members (coalesced), then a DPP/shuffle butterfly folds the 64 lanes.
-// HBM-bound streaming read.
+// HBM-bound streaming read.  Strided: the grid is capped (launchReducePlane) and a
+// wavefront takes every (wavefronts of the grid)-th cell, indexed in 64 bits; else
+// the one cell of its index (a loop around a short row costs it a fifth: measured).
 // -----------------------------------------------------------------------------
-template <class T>
+template <class T, bool Strided>
 __global__ __launch_bounds__(256) void reducePlaneKernel(const T* __restrict__ plane,
                                                          int32_t n_steps, int64_t ld,
                                                          int32_t n_sites, int32_t n_members,
                                                          double* __restrict__ stats) {
-  const int wave = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
   const int lane = threadIdx.x & 63;
   const int64_t nItems = (int64_t)n_steps * n_sites;
+  const int64_t nWaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (wave >= nItems) return;
-  const int t = wave / n_sites, site = wave % n_sites;
-  const T* __restrict__ row = plane + (int64_t)t * ld + (int64_t)site * n_members;
-  // 16-byte loads, four independent accumulator pairs: enough bytes in flight per wave to
-  // stream at HBM rate; a scalar tail / fallback covers odd lengths and unaligned rows
-  double a1 = 0.0, a2 = 0.0, b1 = 0.0, b2 = 0.0, c1 = 0.0, c2 = 0.0, d1 = 0.0, d2 = 0.0;
-  constexpr int kPer = 16 / (int)sizeof(T);  // elements per 16-byte load
-  int done = 0;
-  if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
-    typedef T vec_t __attribute__((ext_vector_type(kPer)));
-    const vec_t* __restrict__ rv = reinterpret_cast<const vec_t*>(row);
-    const int nVec = n_members / kPer;
-    int i = lane;
-    for (; i + 192 < nVec; i += 256) {
-      const vec_t v0 = rv[i], v1 = rv[i + 64], v2 = rv[i + 128], v3 = rv[i + 192];
+  do {
+    const int64_t t = Strided ? wave / n_sites : (int64_t)((int)wave / n_sites), site = wave - t * n_sites;
+    const T* __restrict__ row = plane + t * ld + site * n_members;
+    // 16-byte loads, four independent accumulator pairs: enough bytes in flight per wave to
+    // stream at HBM rate; a scalar tail / fallback covers odd lengths and unaligned rows
+    double a1 = 0.0, a2 = 0.0, b1 = 0.0, b2 = 0.0, c1 = 0.0, c2 = 0.0, d1 = 0.0, d2 = 0.0;
+    constexpr int kPer = 16 / (int)sizeof(T);  // elements per 16-byte load
+    int done = 0;
+    if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+      typedef T vec_t __attribute__((ext_vector_type(kPer)));
+      const vec_t* __restrict__ rv = reinterpret_cast<const vec_t*>(row);
+      const int nVec = n_members / kPer;
+      int i = lane;
+      for (; i + 192 < nVec; i += 256) {
+        const vec_t v0 = rv[i], v1 = rv[i + 64], v2 = rv[i + 128], v3 = rv[i + 192];
 #pragma unroll
-      for (int k = 0; k < kPer; k++) {
-        const double x0 = (double)v0[k], x1 = (double)v1[k], x2 = (double)v2[k], x3 = (double)v3[k];
-        a1 += x0; a2 += x0 * x0;
-        b1 += x1; b2 += x1 * x1;
-        c1 += x2; c2 += x2 * x2;
-        d1 += x3; d2 += x3 * x3;
+        for (int k = 0; k < kPer; k++) {
+          const double x0 = (double)v0[k], x1 = (double)v1[k], x2 = (double)v2[k], x3 = (double)v3[k];
+          a1 += x0; a2 += x0 * x0;
+          b1 += x1; b2 += x1 * x1;
+          c1 += x2; c2 += x2 * x2;
+          d1 += x3; d2 += x3 * x3;
+        }
       }
-    }
-    for (; i < nVec; i += 64) {
-      const vec_t v0 = rv[i];
+      for (; i < nVec; i += 64) {
+        const vec_t v0 = rv[i];
 #pragma unroll
-      for (int k = 0; k < kPer; k++) {
-        const double x0 = (double)v0[k];
-        a1 += x0; a2 += x0 * x0;
+        for (int k = 0; k < kPer; k++) {
+          const double x0 = (double)v0[k];
+          a1 += x0; a2 += x0 * x0;
+        }
       }
+      done = nVec * kPer;
     }
-    done = nVec * kPer;
-  }
-  for (int m = done + lane; m < n_members; m += 64) {
-    const double v = (double)row[m];
-    a1 += v;
-    a2 += v * v;
-  }
-  double s1 = (a1 + b1) + (c1 + d1), s2 = (a2 + b2) + (c2 + d2);
+    for (int m = done + lane; m < n_members; m += 64) {
+      const double v = (double)row[m];
+      a1 += v;
+      a2 += v * v;
+    }
+    double s1 = (a1 + b1) + (c1 + d1), s2 = (a2 + b2) + (c2 + d2);
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s1 += __shfl_xor(s1, off, 64);
-    s2 += __shfl_xor(s2, off, 64);
-  }
-  if (lane == 0) {
-    stats[(int64_t)wave * 2 + 0] = s1;
-    stats[(int64_t)wave * 2 + 1] = s2;
-  }
+    for (int off = 32; off > 0; off >>= 1) {
+      s1 += __shfl_xor(s1, off, 64);
+      s2 += __shfl_xor(s2, off, 64);
+    }
+    if (lane == 0) {
+      stats[wave * 2 + 0] = s1;
+      stats[wave * 2 + 1] = s2;
+    }
+  } while (Strided && (wave += nWaves) < nItems);
 }
 
 // second stage of the in-kernel ensemble statistics (step_coop.hip, wave L): one thread per
 // (plane, step, site) adds up the site's per-chunk partial sums, chunk by chunk in index order
-// (deterministic); neighbouring threads read neighbouring steps
+// (deterministic); neighbouring threads read neighbouring steps.  Strided: the grid is capped
+// (launchFinishStats) and a thread takes every (threads of the grid)-th cell.
+template <bool Strided>
 __global__ __launch_bounds__(256) void finishStatsKernel(const double* __restrict__ part, int32_t n_steps,
                                                          int32_t n_sites, int32_t chunksPerSite,
                                                          double* __restrict__ stats) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t perPlane = (int64_t)n_steps * n_sites;
+  const int64_t nThreads = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= 3 * perPlane) return;
-  const int p = (int)(i / perPlane);
-  const int64_t rem = i - (int64_t)p * perPlane;
-  const int site = (int)(rem / n_steps), t = (int)(rem % n_steps);
-  typedef double d2 __attribute__((ext_vector_type(2)));
-  const d2* __restrict__ src =
-      reinterpret_cast<const d2*>(part) + ((int64_t)p * n_sites + site) * chunksPerSite * n_steps + t;
-  double s1 = 0.0, s2 = 0.0;
-  int c = 0;
-  for (; c + 8 <= chunksPerSite; c += 8) {   // eight loads in flight, added in chunk order (1 024 chunks at C3:
-    d2 v[8];                                 // one dependent load at a time took 0.5 ms)
+  do {
+    const int p = (int)(i / perPlane);
+    const int64_t rem = i - (int64_t)p * perPlane;
+    const int site = (int)(rem / n_steps), t = (int)(rem % n_steps);
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const d2* __restrict__ src =
+        reinterpret_cast<const d2*>(part) + ((int64_t)p * n_sites + site) * chunksPerSite * n_steps + t;
+    double s1 = 0.0, s2 = 0.0;
+    int c = 0;
+    for (; c + 8 <= chunksPerSite; c += 8) {   // eight loads in flight, added in chunk order (1 024 chunks at C3:
+      d2 v[8];                                 // one dependent load at a time took 0.5 ms)
 #pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = src[(int64_t)(c + k) * n_steps];
+      for (int k = 0; k < 8; k++) v[k] = src[(int64_t)(c + k) * n_steps];
 #pragma unroll
-    for (int k = 0; k < 8; k++) {
-      s1 += v[k].x;
-      s2 += v[k].y;
+      for (int k = 0; k < 8; k++) {
+        s1 += v[k].x;
+        s2 += v[k].y;
+      }
     }
-  }
-  for (; c < chunksPerSite; c++) {
-    const d2 v = src[(int64_t)c * n_steps];
-    s1 += v.x;
-    s2 += v.y;
-  }
-  double* dst = stats + (((int64_t)p * n_steps + t) * n_sites + site) * 2;
-  dst[0] = s1;
-  dst[1] = s2;
+    for (; c < chunksPerSite; c++) {
+      const d2 v = src[(int64_t)c * n_steps];
+      s1 += v.x;
+      s2 += v.y;
+    }
+    double* dst = stats + (((int64_t)p * n_steps + t) * n_sites + site) * 2;
+    dst[0] = s1;
+    dst[1] = s2;
+  } while (Strided && (i += nThreads) < 3 * perPlane);
 }
 
 template <class C>
@@ -1311,11 +1322,19 @@ void launchOne(const KernelArgs& a, hipStream_t stream) {
 
 }  // namespace
 
+// A grid's x dimension times the 256 threads of a workgroup must stay below 2^32 (quantiles.hip), which a workgroup per
+// four (step, site) cells passes at n_steps * n_sites = 2^26 -- a half-hourly year of 3 831 sites.  Beyond kMaxGrid
+// workgroups the statistics kernels stride over their cells with a grid of that size.
+constexpr int64_t kMaxGrid = (int64_t)1 << 20;
+
 void launchFinishStats(const double* statsPart, int32_t n_steps, int32_t n_sites, int32_t chunksPerSite,
                        double* stats, hipStream_t stream) {
   const int64_t n = (int64_t)3 * n_steps * n_sites;
-  hipLaunchKernelGGL(finishStatsKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, statsPart,
-                     n_steps, n_sites, chunksPerSite, stats);
+  const int64_t grid = (n + 255) / 256;
+  if (grid <= kMaxGrid) hipLaunchKernelGGL(finishStatsKernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, statsPart,
+                                           n_steps, n_sites, chunksPerSite, stats);
+  else hipLaunchKernelGGL(finishStatsKernel<true>, dim3((unsigned)kMaxGrid), dim3(256), 0, stream, statsPart,
+                          n_steps, n_sites, chunksPerSite, stats);
 }
 void launchSetup(const SetupArgs& a, hipStream_t stream) {
   const int grid = (int)((a.ncol + 255) / 256);
@@ -1384,15 +1403,19 @@ void launchStep(const KernelArgs& a, int precision, bool fastMath, hipStream_t s
 void launchReducePlane(const void* plane, bool isF32, int32_t n_steps, int64_t ld,
                        int32_t n_sites, int32_t n_members, double* stats,
                        hipStream_t stream) {
-  const int64_t waves = (int64_t)n_steps * n_sites;
-  const int grid = (int)((waves * 64 + 255) / 256);
+  const int64_t grid = ((int64_t)n_steps * n_sites + 3) / 4;   // four wavefronts, four cells per workgroup
+  const bool strided = grid > kMaxGrid;
+  const dim3 g((unsigned)std::min(grid, kMaxGrid));
+#define REDUCE_PLANE(T, S) \
+  hipLaunchKernelGGL((reducePlaneKernel<T, S>), g, dim3(256), 0, stream, (const T*)plane, n_steps, ld, n_sites, n_members, stats)
   if (isF32) {
-    hipLaunchKernelGGL(reducePlaneKernel<float>, dim3(grid), dim3(256), 0, stream,
-                       (const float*)plane, n_steps, ld, n_sites, n_members, stats);
+    if (strided) REDUCE_PLANE(float, true);
+    else REDUCE_PLANE(float, false);
   } else {
-    hipLaunchKernelGGL(reducePlaneKernel<double>, dim3(grid), dim3(256), 0, stream,
-                       (const double*)plane, n_steps, ld, n_sites, n_members, stats);
+    if (strided) REDUCE_PLANE(double, true);
+    else REDUCE_PLANE(double, false);
   }
+#undef REDUCE_PLANE
 }
 
 }  // namespace sipnet
