@@ -706,6 +706,80 @@ int sipnet_batch_pf_rejuvenate(sipnet_batch *b, int32_t n_params, const struct s
                                uint32_t draw, const uint32_t *d_stream, const int64_t *d_site_total,
                                int32_t *d_site_info, void *hip_stream);
 
+/* ---- a Metropolis move over members: differential-evolution proposal and accept on the device --------------------
+ * The rejuvenation above is an approximation (it keeps mean and variance in expectation only).  This pair is an exact
+ * Metropolis-Hastings move of listed parameter rows, a population sampler whose chains are the members of a site:
+ *   propose -> sipnet_batch_setup -> sipnet_batch_run / _run_sums -> sipnet_batch_series_loglik (out = d_logp_new) -> accept
+ * with no host decision, either as a calibration loop or as the move of a resample-move filter after
+ * sipnet_batch_pf_resample_sites (in place of, or after, the rejuvenation).
+ * A CHAIN is a live member of a site (state[29] == 0, site plan status OK, as in the analyses).  A site's members form two
+ * HALVES by the parity of the member's index j inside its site (not of its rank among the live ones: a death moves nobody
+ * between halves).  One call moves one half (half = 0: even j, 1: odd j) and draws both partners of every moving chain
+ * from the live members of the OTHER half only: B, in ascending j, nB of them.  This is the complementary-ensemble
+ * construction of Foreman-Mackey et al. (2013) applied to the DE-MC proposal of ter Braak (2006): given the other half the
+ * moving chains are conditionally independent and the proposal is symmetric, so detailed balance holds exactly with all of
+ * a half moved at once.  A call that moves everybody from everybody is not offered: it is not a valid sampler.  A sweep is
+ * two calls, half = 0 and half = 1.
+ * Draws: one Philox4x32-10 call per member with the rejuvenation's key and counter layout, ctr = {member, stream, 8, draw}
+ * (blocks 0..7 are the rejuvenation's, so a cycle may use one draw number for both calls).  Of its words x0..x3:
+ *   i1 = (x0 * nB) >> 32, i2 = (x1 * (nB - 1)) >> 32, i2 += (i2 >= i1)   (64-bit products; 0 <= i1 != i2 < nB),
+ * the partners are r1 = B[i1] and r2 = B[i2]; u = (x2 + 0.5) 2^-32 is the accept step's uniform.
+ * sipnet_mcmc_draws: host only, no device: i1, i2 and u of one member (n_other = nB >= 2).
+ * sipnet_batch_mcmc_propose.  params: sipnet_batch_enkf_analysis_joint's descriptors; what sipnet_enkf_params_check refuses
+ * is refused; bounds in file units, arithmetic in converted units.  d_gamma [n_sites] (2.38 / sqrt(2 n_params) is usual),
+ * d_jitter [n_sites] or NULL, d_stream [n_sites] or NULL (the site's index), d_site_total [n_sites] or NULL (every site;
+ * else the sites whose total is > 0, as in the rejuvenation): DEVICE.  Per listed row k of a moving chain j:
+ *   v = x_j + gamma[s] (x_r1 - x_r2), and with w = jitter[s] > 0: v + (w (hi_k - lo_k)) z_k,
+ * z_k normal k & 3 of block 12 + (k >> 2) (the rejuvenation's Box-Muller normals); with d_jitter NULL or w == 0 no normal
+ * is drawn and no term is added.  The proposal is NOT MADE when some v is not finite, when some v lies outside [lo_k, hi_k],
+ * or when an allocation row (leaf, wood, fineRoot) is listed and the result fails ensureAllocation's test: no reflection,
+ * no clipping, so the prior is uniform on the box and the move stays symmetric; the member keeps its rows, d_moved[col] = 0.
+ * Otherwise d_saved[k][col] (DEVICE [n_params][ncol] doubles) receives the old rows, the new rows are written, psnTMax /
+ * coarseRootAllocation are rewritten from the rows they derive from, and d_moved[col] = 1.  d_moved (DEVICE [ncol] int32) is
+ * written, 0 or 1, for EVERY column of the batch; d_saved only where d_moved is 1.
+ * site_info[s] = {code, members proposed, live members of the moving half, nB}.  Code 1 done; 0 nB < 2; -2 gamma not finite,
+ * or a jitter not finite or < 0; -3 not selected.  A site whose code is not 1 is untouched.  State, rings and status are
+ * never written by this call.
+ * sipnet_batch_mcmc_accept.  d_logp_new, d_logp_cur [ncol], d_beta [n_sites] or NULL (1; a tempering exponent): DEVICE; seed,
+ * draw and d_stream as given to the proposal.  For each column with d_moved == 1 the proposal is ACCEPTED iff
+ *   new < +inf and beta[s] (new - cur) > log(u):
+ * every NaN compares false and is a rejection (-inf - -inf is one); cur = -inf with a finite new is an acceptance.  On
+ * acceptance d_logp_cur[col] = new.  On rejection the listed rows are restored from d_saved and the derived rows are derived
+ * again: the column's 80 parameter rows are bit-identical to what they were before the proposal.  Columns with d_moved == 0
+ * keep their rows and their d_logp_cur.  d_moved is cleared for the columns handled, so a second accept is a no-op.  Whether
+ * the member is still live is not asked: one that died in the proposal's run has -inf from sipnet_batch_series_loglik and is
+ * put back.  site_info[s] = {code, proposed, accepted, live members}; code 1, or -2 for a beta that is not finite or <= 0
+ * (the site is untouched, its d_moved too).  d_logp_new is never written.
+ * After a rejection the column's MODEL STATE is still that of the rejected run: a caller that wants states ends the
+ * sampling with one sipnet_batch_setup + run.  The two arrays hold log-POSTERIORS of the caller's making: the prior of the
+ * move itself is uniform on the box, and a caller that wants another adds its log prior to what it passes.
+ * Both calls.  Bookkeeping as the per-site analyses: pending set_params rows are flushed; a batch whose parameters are behind
+ * a resampling's index first gets every column its own rows; armed log-weights are dropped.  SIPNET_ERR_BAD_ARGUMENT before
+ * any launch (sipnet_last_error says why): n_params outside 1..16 and the parameter checks; a half that is not 0 or 1; a
+ * NULL required array (d_gamma, d_saved, d_moved; d_logp_new, d_logp_cur); a NULL batch; ncol > 4 194 304; a batch that was
+ * not set up; a batch connected by sipnet_batch_pf_connect.  d_site_info given: nothing is synchronised.  NULL: gamma and
+ * jitter (beta) and the totals are read back first, and a -2 site gives SIPNET_ERR_BAD_ARGUMENT naming it before anything
+ * is written.  A site's result depends on its own columns, seed, draw, its stream and its own gamma / jitter / beta -- not
+ * on n_sites, not (with d_stream) on where the site sits in the batch, and not on the path: the proposal runs as one
+ * workgroup per site up to 256 members, else (and under SIPNET_KOPT_PF_MULTI_LAUNCH) as per-chunk launches, the same bits;
+ * sipnet_batch_pf_info's fused says which ran.  No atomic, no grid barrier, no spin.
+ * Out of scope: snooker and crossover updates, a past-state archive (DE-MCzs), initial-condition rows
+ * (sipnet_enkf_params_check refuses them), the node object and the CLI, connected batches. */
+#define SIPNET_MCMC_INFO_WORDS 4
+enum sipnet_mcmc_code {
+  SIPNET_MCMC_DONE = 1, SIPNET_MCMC_TOO_FEW = 0, SIPNET_MCMC_BAD_INPUT = -2, SIPNET_MCMC_NOT_SELECTED = -3
+};
+int sipnet_mcmc_draws(uint64_t seed, uint32_t draw, uint32_t stream, uint32_t member, int32_t n_other, int32_t idx[2],
+                      double *u);
+int sipnet_batch_mcmc_propose(sipnet_batch *b, int32_t n_params, const struct sipnet_enkf_param *params /* HOST */,
+                              const double *d_gamma, const double *d_jitter, int32_t half, uint64_t seed, uint32_t draw,
+                              const uint32_t *d_stream, const int64_t *d_site_total, double *d_saved, int32_t *d_moved,
+                              int32_t *d_site_info, void *hip_stream);
+int sipnet_batch_mcmc_accept(sipnet_batch *b, int32_t n_params, const struct sipnet_enkf_param *params /* HOST */,
+                             const double *d_saved, int32_t *d_moved, const double *d_logp_new, double *d_logp_cur,
+                             const double *d_beta, uint64_t seed, uint32_t draw, const uint32_t *d_stream,
+                             int32_t *d_site_info, void *hip_stream);
+
 /* ---- ensemble Kalman filter analysis of the member pools, a filter per site ------------------------------------
  * Observation operators (h of one member, from its forecast state, planes and converted parameters):
  *   POOLS: h = scale * (sum of the pools in pool_mask) / (param >= 0 ? prm[param] : 1)

@@ -18,8 +18,9 @@ from .io import (ClimTable, format_out_header, format_out_row, read_clim, read_e
                  read_params, read_restart, check_restart, write_debug_logs, write_events_out, write_out,
                  write_restart)
 from .batch import (Batch, PlaneQuantiles, debug_live_bytes, liu_west_shrink, loglik_term, philox4x32_10, quantile_lds_members,
-                    quantile_positions, rejuvenate_normals)
+                    quantile_positions, rejuvenate_normals, demc_gamma, mcmc_draws)
 from ._lib import (REJUVENATE_BAD_INPUT, REJUVENATE_DONE, REJUVENATE_INFO_WORDS, REJUVENATE_NOT_SELECTED, REJUVENATE_TOO_FEW)
+from ._lib import (MCMC_BAD_INPUT, MCMC_DONE, MCMC_INFO_WORDS, MCMC_NOT_SELECTED, MCMC_TOO_FEW)
 from .enkf_local import ENKF_BLOCK_MAX_ROWS, EnkfLocalization, enkf_local_rows, enkf_local_schedule, gaspari_cohn
 
 __all__ = [
@@ -32,5 +33,6 @@ __all__ = [
     "NPARAMS", "NFLAGS", "NCLIM", "NREC", "NSTATE", "RING_SLOTS",
     "philox4x32_10", "rejuvenate_normals", "liu_west_shrink", "REJUVENATE_INFO_WORDS", "REJUVENATE_DONE", "REJUVENATE_TOO_FEW",
     "REJUVENATE_BAD_INPUT", "REJUVENATE_NOT_SELECTED",
+    "mcmc_draws", "demc_gamma", "MCMC_INFO_WORDS", "MCMC_DONE", "MCMC_TOO_FEW", "MCMC_BAD_INPUT", "MCMC_NOT_SELECTED",
     "loglik_term", "LOGLIK_GAUSS", "LOGLIK_LAPLACE", "LOGLIK_MAX_TERMS", "LOGLIK_TILE_ROWS",
 ]

@@ -68,6 +68,10 @@ LOGLIK_TILE_ROWS, LOGLIK_MAX_TERMS = 256, 8   # SIPNET_LOGLIK_TILE_ROWS, SIPNET_
 # sipnet_batch_pf_rejuvenate: site_info[s] = {code, rows + slots perturbed, live members, members kept}; the codes
 REJUVENATE_INFO_WORDS = 4
 REJUVENATE_DONE, REJUVENATE_TOO_FEW, REJUVENATE_BAD_INPUT, REJUVENATE_NOT_SELECTED = 1, 0, -2, -3
+# sipnet_batch_mcmc_propose: site_info[s] = {code, members proposed, live members of the moving half, live members of the
+# other half}; sipnet_batch_mcmc_accept: {code, proposed, accepted, live members}; the codes
+MCMC_INFO_WORDS = 4
+MCMC_DONE, MCMC_TOO_FEW, MCMC_BAD_INPUT, MCMC_NOT_SELECTED = 1, 0, -2, -3
 
 
 class LoglikTerm(C.Structure):
@@ -216,6 +220,9 @@ SIGNATURES = {
     "sipnet_philox4x32_10": (None, [_P, _P, _P]),
     "sipnet_rejuvenate_normals": (None, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
     "sipnet_batch_pf_rejuvenate": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
+    "sipnet_mcmc_draws": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _P, _P]),
+    "sipnet_batch_mcmc_propose": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "sipnet_batch_mcmc_accept": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
     "sipnet_batch_enkf_analysis_sites": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
                                                    _P, _P, _P, _P]),
     "sipnet_enkf_params_check": (C.c_int, [C.c_int32, _P, _P, _P]),

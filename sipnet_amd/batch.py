@@ -11,7 +11,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import (F64, KERNEL_AUTO, LOGLIK_GAUSS, LOGLIK_LAPLACE, LOGLIK_MAX_TERMS, NDBG, NPARAMS, NREC, NSTATE, RING_SLOTS,
+from ._lib import (F64, KERNEL_AUTO, LOGLIK_GAUSS, LOGLIK_LAPLACE, LOGLIK_MAX_TERMS, MCMC_INFO_WORDS, NDBG, NPARAMS, NREC, NSTATE, RING_SLOTS,
                    REJUVENATE_INFO_WORDS, EnkfObs, EnkfParam, EnkfSeries, Event, LaunchInfo, LoglikTerm, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
 from .config import pool_mask
 from .enkf_local import EnkfLocalization
@@ -67,6 +67,22 @@ def liu_west_shrink(delta):
     """the shrink factor a = (3 delta - 1) / (2 delta) of Liu & West's discount delta in (1/3, 1] (0.95 .. 0.99 is usual);
     Batch.pf_rejuvenate's kernel then has h^2 = 1 - a^2"""
     return (3.0 * delta - 1.0) / (2.0 * delta)
+
+
+def mcmc_draws(seed, draw, stream, member, n_other):
+    """what Batch.mcmc_propose / mcmc_accept draw for one member (sipnet_mcmc_draws, host only): the ranks i1 != i2 of its two
+    partners among the n_other >= 2 live members of the other half, in ascending member index, and the accept step's
+    uniform u in (0, 1) -> (i1, i2, u)"""
+    idx = np.zeros(2, dtype=np.int32)
+    u = np.zeros(1)
+    check(lib().sipnet_mcmc_draws(int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff, int(stream) & 0xffffffff,
+                                  int(member) & 0xffffffff, int(n_other), ptr(idx), ptr(u)), "mcmc_draws")
+    return int(idx[0]), int(idx[1]), float(u[0])
+
+
+def demc_gamma(n_params):
+    """ter Braak's (2006) scale of the differential-evolution proposal for n_params moved rows: 2.38 / sqrt(2 n_params)"""
+    return 2.38 / np.sqrt(2.0 * n_params)
 
 
 def loglik_term(series, obs, sd, kind=LOGLIK_GAUSS, scale=1.0, sum_steps=1):
@@ -587,6 +603,69 @@ class Batch:
         check(self.L.sipnet_batch_pf_rejuvenate(self.h, len(prm), c_array(EnkfParam, prm), ptr(shrink), mask, ptr(pool_sd),
                                                 int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff, ptr(streams), ptr(site_total),
                                                 ptr(info_out), self._stream()), what)
+
+    def _mcmc_common(self, what, streams, info_out):
+        """the uint32 streams on the device (None stays None); info_out checked"""
+        t = self._torch
+        if streams is not None:
+            streams = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
+            if streams.size != self.n_sites:
+                raise ValueError(f"{what}: streams needs {self.n_sites} values, got {streams.size}")
+            streams = t.from_numpy(streams.view(np.int32)).to(self.device)
+        if info_out is not None and not _dense(info_out, t.int32, MCMC_INFO_WORDS * self.n_sites):
+            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x {MCMC_INFO_WORDS}")
+        return streams
+
+    def mcmc_propose(self, params, gamma, jitter=None, half=0, seed=0, draw=0, streams=None, site_total=None, saved=None,
+                     moved=None, info_out=None):
+        """the proposal of a Metropolis move over the members of every site (sipnet_batch_mcmc_propose): the live members
+        of one half (half = 0: even member index, 1: odd) get x' = x + gamma (x_r1 - x_r2) (+ jitter (hi - lo) z) in the
+        listed parameter rows, both partners drawn from the live members of the other half (sa.mcmc_draws); a proposal
+        outside the bounds is not made.  params: sa.enkf_param(name, lo, hi), 1..sa.ENKF_MAX_PARAMS; gamma
+        (sa.demc_gamma(n)) and jitter (None: none): one value per site; seed, draw, streams, site_total: as pf_rejuvenate;
+        saved: float64 device tensor [n_params][ncol], moved: int32 device tensor [ncol] (made when None); info_out: int32
+        device tensor [n_sites][4] for {code, proposed, live members of the half, live members of the other half} (no host
+        synchronisation); without it gamma and jitter are checked first.  -> (saved, moved), for mcmc_accept after
+        setup(), run() and series_loglik()."""
+        t = self._torch
+        what = "mcmc_propose"
+        prm = list(params)
+        gamma = self._upload(what, gamma, self.n_sites, "gamma")
+        jitter = self._upload(what, jitter, self.n_sites, "jitter")
+        if gamma is None:
+            raise ValueError(f"{what}: gamma needs {self.n_sites} values")
+        streams = self._mcmc_common(what, streams, info_out)
+        if site_total is not None and not _dense(site_total, t.int64, self.n_sites):
+            raise ValueError(f"{what}: site_total must be a contiguous int64 device tensor of {self.n_sites} values")
+        if saved is None:
+            saved = t.zeros((max(len(prm), 1), self.ncol), dtype=t.float64, device=self.device)
+        if moved is None:
+            moved = t.zeros(self.ncol, dtype=t.int32, device=self.device)
+        if not _dense(saved, t.float64, max(len(prm), 1) * self.ncol) or not _dense(moved, t.int32, self.ncol):
+            raise ValueError(f"{what}: saved must be a contiguous float64 device tensor [n_params][{self.ncol}], moved an int32 one [{self.ncol}]")
+        check(self.L.sipnet_batch_mcmc_propose(self.h, len(prm), c_array(EnkfParam, prm), ptr(gamma), ptr(jitter), int(half),
+                                               int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff, ptr(streams), ptr(site_total),
+                                               ptr(saved), ptr(moved), ptr(info_out), self._stream()), what)
+        return saved, moved
+
+    def mcmc_accept(self, params, saved, moved, logp_new, logp_cur, beta=None, seed=0, draw=0, streams=None, info_out=None):
+        """the accept step of the move (sipnet_batch_mcmc_accept): a column with moved == 1 keeps its proposal iff
+        logp_new < inf and beta (logp_new - logp_cur) > log u, and then logp_cur takes logp_new; else its listed rows come
+        back from saved, bit for bit.  params, seed, draw, streams: as given to mcmc_propose; logp_new, logp_cur: float64
+        device tensors [ncol] (logp_cur is updated in place); beta: one value per site (None: 1); info_out: int32 device
+        tensor [n_sites][4] for {code, proposed, accepted, live members}.  moved is cleared."""
+        t = self._torch
+        what = "mcmc_accept"
+        prm = list(params)
+        beta = self._upload(what, beta, self.n_sites, "beta")
+        streams = self._mcmc_common(what, streams, info_out)
+        for x, dtype, n, name in ((saved, t.float64, max(len(prm), 1) * self.ncol, "saved"), (moved, t.int32, self.ncol, "moved"),
+                                  (logp_new, t.float64, self.ncol, "logp_new"), (logp_cur, t.float64, self.ncol, "logp_cur")):
+            if not t.is_tensor(x) or not _dense(x, dtype, n):
+                raise ValueError(f"{what}: {name} must be a contiguous device tensor of {n} {dtype} values")
+        check(self.L.sipnet_batch_mcmc_accept(self.h, len(prm), c_array(EnkfParam, prm), ptr(saved), ptr(moved), ptr(logp_new),
+                                              ptr(logp_cur), ptr(beta), int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff,
+                                              ptr(streams), ptr(info_out), self._stream()), what)
 
     def enkf_analysis_sites(self, obs, sd, operators, analysed, planes=None, inflation=None, info_out=None):
         """an ensemble Kalman filter analysis of the member pools, every site a filter of its own, one library call

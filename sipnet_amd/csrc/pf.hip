@@ -15,14 +15,15 @@
 // This file is the one translation unit (the one tools/build_variants.py compiles with -DSIPNET_PF_*) and the host side; the
 // device code is in parts, each with its own header comment, included below in this order: site_device.h (the sums in their
 // one order, a member's limits and derived rows, shared with enkf.hip), pf_gather.inc, pf_weights.inc, pf_fused.inc,
-// pf_plan.inc, pf_sites.inc, pf_series.inc, pf_rejuvenate.inc.  Refusals, the bookkeeping of a call that writes the batch, the
+// pf_plan.inc, pf_sites.inc, pf_series.inc, pf_rejuvenate.inc, pf_metropolis.inc.  Refusals, the bookkeeping of a call that writes the batch, the
 // scratch blocks' growth and the synchronous forms' copies are site_host.h's.
 //
 // The host side runs three filters.  One batch (sipnet_batch_pf_analysis): takePfPre, the one launch (fusedSetup) or the
 // launches of their own, checkTotal, the resampling gather (resampleColumns).  Many sites (sipnet_batch_pf_analysis_sites, and
 // sipnet_batch_pf_resample_sites from given log-weights): sitesBegin, the weights' source, sitesFinish.  Across ranks by peer
 // reads: sipnet_batch_pf_publish, _connect (mapPeer, fillBank) and _resample_peers (peerTable, peerAncestors, peerGather).
-// Beside them the series weights (sipnet_batch_series_loglik) and the rejuvenation (sipnet_batch_pf_rejuvenate).
+// Beside them the series weights (sipnet_batch_series_loglik), the rejuvenation (sipnet_batch_pf_rejuvenate) and the Metropolis
+// move over members (sipnet_batch_mcmc_propose, sipnet_batch_mcmc_accept).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -51,6 +52,7 @@ namespace {
 #include "pf_sites.inc"
 #include "pf_series.inc"
 #include "pf_rejuvenate.inc"
+#include "pf_metropolis.inc"
 
 }  // namespace
 }  // namespace sipnet
@@ -209,6 +211,7 @@ struct PfScratch {
   DevBuf<double> d_loglik;              // sipnet_batch_series_loglik, path 2: [terms' tiles][ncol] the tiles' sums
   DevBuf<int32_t> d_loglikUsed;         // ... and [n_sites][terms' tiles] the tiles' rows used
   DevBuf<unsigned char> d_rejuv;        // sipnet_batch_pf_rejuvenate (rejScratch), bytes
+  DevBuf<unsigned char> d_mcmc;         // sipnet_batch_mcmc_propose / _accept (mcScratch), bytes
 };
 namespace {
 constexpr int kMaxParts = 256;
@@ -994,6 +997,156 @@ int sipnet_batch_pf_rejuvenate(sipnet_batch* b, int32_t n_params, const sipnet_e
   }
   HIP_TRY(hipGetLastError());
   reportPath(b, !split, split ? 0 : (int32_t)nSites);
+  return markBusy(b, stream);
+}
+
+// ---- the Metropolis move over members ------------------------------------------------------------------------------------
+int sipnet_mcmc_draws(uint64_t seed, uint32_t draw, uint32_t stream, uint32_t member, int32_t n_other, int32_t idx[2], double* u) {
+  if (n_other < 2 || !idx || !u) return refuse("sipnet_mcmc_draws", "n_other must be at least 2; idx and u must not be NULL");
+  uint32_t x2;
+  mcDraws((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, stream, member, (uint32_t)n_other, &idx[0], &idx[1], &x2);
+  *u = ((double)x2 + 0.5) * 0x1p-32;
+  return SIPNET_OK;
+}
+
+// What both calls of the move refuse before any launch, in this order: the listed rows (the joint analysis's checks; the
+// bounds converted into a), the half, a NULL required array (named by `missing`), then the batch.
+static int mcBegin(const char* who, sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, int32_t half,
+                   const char* missing, McArgs& a) {
+  if (n_params < 1 || n_params > kRejPrm) return refuse(who, "n_params must be 1.." + std::to_string(kRejPrm));
+  if (sipnet_enkf_params_check(n_params, params, a.lo, a.hi) != SIPNET_OK) {   // (the joint analysis's rows and bounds)
+    const std::string why = sipnet_last_error(), from = "sipnet_enkf_params_check: ";
+    return refuse(who, why.compare(0, from.size(), from) == 0 ? why.substr(from.size()) : why);
+  }
+  if (half != 0 && half != 1) return refuse(who, "half must be 0 or 1");
+  if (missing) return refuse(who, std::string("a NULL ") + missing);
+  if (!b) return refuse(who, "a NULL batch");
+  if (tooManyColumns(b)) return refuse(who, "at most 4194304 columns");
+  if (b->planDirty) return refuse(who, "needs a batch that was set up (sipnet_batch_setup): the members' status is read");
+  if (b->pfPeers) return refuse(who, "this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
+  a.nPrm = n_params;
+  a.half = half;
+  a.rows = derivedRowsOf(n_params, params, a.prmRow);
+  a.ncol = b->ncol;
+  a.M = b->n_members;
+  a.nCh = (int32_t)((b->n_members + 255) / 256);
+  return SIPNET_OK;
+}
+// the batch's scratch block carved: the chunks' masks, the fallback info (a.info is d_site_info where given), the chunks'
+// counts and the sites' codes
+static int mcScratch(sipnet_batch* b, McArgs& a, int32_t* d_site_info) {
+  PfScratch& sc = scratchOf(b);
+  const size_t nSites = (size_t)b->n_sites, nCnt = nSites * (size_t)a.nCh;
+  const size_t bytes = 4 * nCnt * sizeof(uint64_t) + (4 * nSites + 5 * nCnt + 3 * nSites) * sizeof(int32_t);
+  RC_TRY(growScratch(b, sc.d_mcmc, bytes));
+  a.masks = (uint64_t*)sc.d_mcmc.get();
+  int32_t* ints = (int32_t*)(a.masks + 4 * nCnt);
+  a.info = d_site_info ? d_site_info : ints;
+  a.cntB = ints + 4 * nSites;
+  a.off = a.cntB + nCnt;
+  a.cntA = a.off + nCnt;
+  a.made = a.cntA + nCnt;
+  a.taken = a.made + nCnt;
+  a.site = a.taken + nCnt;
+  return SIPNET_OK;
+}
+static void mcKey(McArgs& a, uint64_t seed, uint32_t draw, const uint32_t* d_stream) {
+  a.key0 = (uint32_t)(seed & 0xffffffffu);
+  a.key1 = (uint32_t)(seed >> 32);
+  a.draw = draw;
+  a.stream = d_stream;
+}
+
+int sipnet_batch_mcmc_propose(sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, const double* d_gamma,
+                              const double* d_jitter, int32_t half, uint64_t seed, uint32_t draw, const uint32_t* d_stream,
+                              const int64_t* d_site_total, double* d_saved, int32_t* d_moved, int32_t* d_site_info,
+                              void* hip_stream) {
+  const char* who = "sipnet_batch_mcmc_propose";
+  McArgs a{};
+  int rc = mcBegin(who, b, n_params, params, half, !d_gamma ? "d_gamma" : !d_saved ? "d_saved" : !d_moved ? "d_moved" : nullptr, a);
+  if (rc) return rc;
+  rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int64_t nSites = b->n_sites;
+  a.gamma = d_gamma;
+  a.jitter = d_jitter;
+  a.siteTotal = d_site_total;
+  a.saved = d_saved;
+  a.moved = d_moved;
+  mcKey(a, seed, draw, d_stream);
+  if (!d_site_info) {   // the synchronous form's check: gamma, jitter and the totals read back, the first bad selected site named
+    std::vector<double> gamma, jitter;
+    std::vector<int64_t> total;
+    RC_TRY(readBack(gamma, d_gamma, (size_t)nSites, stream));
+    RC_TRY(readBack(jitter, d_jitter, (size_t)nSites, stream));
+    RC_TRY(readBack(total, d_site_total, (size_t)nSites, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int64_t s = 0; s < nSites; s++)
+      if (mcProposeInputs(gamma.data(), d_jitter ? jitter.data() : nullptr, d_site_total ? total.data() : nullptr, s) == kMcBadInput)
+        return refuse(who, "site " + std::to_string(s) + ": bad input (gamma must be finite; a jitter must be finite and >= 0); nothing was written");
+  }
+  rc = beginWrite(b, stream, /*ownRows=*/true);   // (every column its own rows: the move writes them)
+  if (rc) return rc;
+  a.state = b->d_state;
+  a.prm = b->d_prm;
+  a.siteStatus = b->d_siteStatus;
+  rc = mcScratch(b, a, d_site_info);
+  if (rc) return rc;
+  // one workgroup per site when the sites are one chunk each, else the per-chunk launches (pf_metropolis.inc)
+  const bool split = a.nCh > 1 || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
+  const dim3 sites((unsigned)nSites), chunks((unsigned)nSites, (unsigned)a.nCh);
+  if (!split) {
+    hipLaunchKernelGGL(mcGroupKernel, sites, dim3(256), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL(mcMaskKernel, chunks, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mcSiteKernel, sites, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mcProposeKernel, chunks, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mcInfoKernel, sites, dim3(256), 0, stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  reportPath(b, !split, split ? 0 : (int32_t)nSites);
+  return markBusy(b, stream);
+}
+
+int sipnet_batch_mcmc_accept(sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, const double* d_saved,
+                             int32_t* d_moved, const double* d_logp_new, double* d_logp_cur, const double* d_beta, uint64_t seed,
+                             uint32_t draw, const uint32_t* d_stream, int32_t* d_site_info, void* hip_stream) {
+  const char* who = "sipnet_batch_mcmc_accept";
+  McArgs a{};
+  int rc = mcBegin(who, b, n_params, params, 0,
+                   !d_saved ? "d_saved" : !d_moved ? "d_moved" : !d_logp_new ? "d_logp_new" : !d_logp_cur ? "d_logp_cur" : nullptr, a);
+  if (rc) return rc;
+  rc = useDevice(b);
+  if (rc) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int64_t nSites = b->n_sites;
+  a.beta = d_beta;
+  a.saved = const_cast<double*>(d_saved);
+  a.moved = d_moved;
+  a.logpNew = d_logp_new;
+  a.logpCur = d_logp_cur;
+  mcKey(a, seed, draw, d_stream);
+  if (!d_site_info && d_beta) {   // the synchronous form's check: beta read back, the first bad site named
+    std::vector<double> beta;
+    RC_TRY(readBack(beta, d_beta, (size_t)nSites, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int64_t s = 0; s < nSites; s++)
+      if (mcAcceptInputs(beta.data(), s) == kMcBadInput)
+        return refuse(who, "site " + std::to_string(s) + ": bad input (beta must be finite and > 0); nothing was written");
+  }
+  rc = beginWrite(b, stream, /*ownRows=*/true);
+  if (rc) return rc;
+  a.state = b->d_state;
+  a.prm = b->d_prm;
+  a.siteStatus = b->d_siteStatus;
+  rc = mcScratch(b, a, d_site_info);
+  if (rc) return rc;
+  const bool direct = a.nCh == 1;   // (a site of one chunk writes its info itself; the counts of more chunks meet in a launch of their own)
+  hipLaunchKernelGGL(mcAcceptKernel, dim3((unsigned)nSites, (unsigned)a.nCh), dim3(256), 0, stream, a, direct ? 1 : 0);
+  if (!direct) hipLaunchKernelGGL(mcAcceptInfoKernel, dim3((unsigned)nSites), dim3(256), 0, stream, a);
+  HIP_TRY(hipGetLastError());
+  reportPath(b, direct, direct ? (int32_t)nSites : 0);
   return markBusy(b, stream);
 }
 
