@@ -646,6 +646,44 @@ int sipnet_batch_series_loglik(sipnet_batch *b, int32_t n_terms, const sipnet_lo
 int sipnet_batch_pf_resample_sites(sipnet_batch *b, double *d_logw, const double *d_u0, const double *d_beta,
                                    const double *d_ess_min, int32_t with_params, int32_t *d_ancestors,
                                    int64_t *d_fixed_weights, int64_t *d_site_total, double *d_ess, void *hip_stream);
+/* The tempering exponent of every site, chosen on the device: the largest step d in (0, delta_max] that keeps the effective
+ * sample size of the tempered weights at a target (adaptive tempering: Jasra et al. 2011; Del Moral, Doucet & Jasra 2012).
+ * All pointers DEVICE.  d_loglik [ncol]: every member's log-likelihood (sipnet_batch_series_loglik's, or anything else);
+ * d_base [ncol] or NULL (0): the log-weights carried so far; d_delta_max [n_sites] or NULL (1): the largest step, in a
+ * tempering run 1 - phi_s; d_ess_target [n_sites]: the ESS to keep.  The tempered log-weight of column c at step d is
+ * v_c(d) = the one rounded product d * loglik[c] with d_base NULL (exactly what sipnet_batch_pf_resample_sites forms from
+ * beta = d), and fma(d, loglik[c], base[c]), one rounding, with d_base given.  ESS_s(d) is S^2 / sum w^2 of the integers w =
+ * the fixed-point weight of v_c(d) under max_c v_c(d) over the site's columns (NaN and -inf weigh nothing; 0 when S = 0): the
+ * functions of sipnet_batch_pf_resample_sites, sum w^2 exact.  So d_delta as d_beta there (with d_base: d_logw_out as d_logw,
+ * d_beta NULL) gives exactly the d_ess of this call.
+ * The search is part of the contract (SIPNET_TEMPER_SECTIONS, SIPNET_TEMPER_ROUNDS):
+ *  1. ESS(0): no member weighs anything -> code 0, delta = delta_hi = 0, ess = 0; ESS(0) < target -> code -1 (the target
+ *     cannot be reached), delta = delta_hi = 0, ess = ESS(0).
+ *  2. ESS(delta_max) >= target -> code 2 (the end is reached), delta = delta_hi = delta_max, ess = ESS(delta_max).
+ *  3. else lo = 0, hi = delta_max and SIPNET_TEMPER_ROUNDS rounds: the candidates b_i = lo + (hi - lo) * (i * 0.0625), i = 1 ..
+ *     15 (product, then sum, each rounded on its own, no fma); k = the number of LEADING candidates with ESS(b_i) >= target
+ *     (the count stops at the first failure); lo = b_k (k = 0: stays), hi = b_(k+1) (k = 15: stays).  A candidate equal to lo
+ *     or hi is evaluated like any other.
+ *  4. code 1, delta = lo, delta_hi = hi, ess = ESS(lo): ESS(lo) >= target > ESS(hi) by evaluation, hi - lo about delta_max 2^-32.
+ * Code -2, bad input: a delta_max not finite or <= 0, a target NaN or <= 0, a +inf among the site's loglik or base; such a
+ * site gets its code (and a count of 0), delta = delta_hi = 0, ess = 0 and nothing else.  d_delta, d_delta_hi, d_ess
+ * [n_sites] (the latter two may be NULL).  d_logw_out [ncol] or NULL (may be d_base itself): v_c(delta) for every column of a
+ * site with code 1 or 2; other sites keep what was there.  d_site_info [n_sites][2] or NULL: {code, members whose value at
+ * d = 0 is finite}.  Given: nothing is synchronised.  NULL: the arguments are read back first, and a site with bad input
+ * gives SIPNET_ERR_BAD_ARGUMENT naming it before anything is written.  SIPNET_ERR_BAD_ARGUMENT before any launch: a NULL
+ * batch, d_loglik, d_ess_target or d_delta; ncol > 4 194 304; a batch connected by sipnet_batch_pf_connect.  The batch itself
+ * is neither read nor changed (no status, no parameters, no flush).  A site's results depend on its own columns and its own
+ * scalars only: not on n_sites, its place in the batch or the path.  Two paths by the many-site analysis's rule, the same
+ * bits: one workgroup per site (sites of at most 4096 members that fill the device, d_base NULL; the whole search is one
+ * launch), else (under SIPNET_KOPT_PF_MULTI_LAUNCH, and always with d_base) launches per chunk and stage,
+ * SIPNET_TEMPER_ROUNDS + 3 of them, with d_base about twice that; sipnet_batch_pf_info's fused says which ran.
+ * Not here: the conditional ESS of Zhou, Johansen & Aston; targets relative to the current ESS; connected batches; the node
+ * object; the CLI. */
+#define SIPNET_TEMPER_SECTIONS 16
+#define SIPNET_TEMPER_ROUNDS 8
+int sipnet_batch_pf_temper_sites(sipnet_batch *b, const double *d_loglik, const double *d_base, const double *d_delta_max,
+                                 const double *d_ess_target, double *d_delta, double *d_delta_hi, double *d_ess,
+                                 double *d_logw_out, int32_t *d_site_info, void *hip_stream);
 
 /* ---- particle rejuvenation: Liu-West parameter jitter and pool noise -----------------------------------------------
  * SIPNET is deterministic: two copies of a resampled particle stay identical for every later step, so a filter whose

@@ -21,6 +21,8 @@ from .batch import (Batch, PlaneQuantiles, debug_live_bytes, liu_west_shrink, lo
                     quantile_positions, rejuvenate_normals, demc_gamma, mcmc_draws)
 from ._lib import (REJUVENATE_BAD_INPUT, REJUVENATE_DONE, REJUVENATE_INFO_WORDS, REJUVENATE_NOT_SELECTED, REJUVENATE_TOO_FEW)
 from ._lib import (MCMC_BAD_INPUT, MCMC_DONE, MCMC_INFO_WORDS, MCMC_NOT_SELECTED, MCMC_TOO_FEW)
+from ._lib import (TEMPER_BAD_INPUT, TEMPER_END, TEMPER_FOUND, TEMPER_INFO_WORDS, TEMPER_NO_WEIGHT, TEMPER_ROUNDS, TEMPER_SECTIONS,
+                   TEMPER_UNREACHABLE)
 from .enkf_local import ENKF_BLOCK_MAX_ROWS, EnkfLocalization, enkf_local_rows, enkf_local_schedule, gaspari_cohn
 
 __all__ = [
@@ -34,5 +36,7 @@ __all__ = [
     "philox4x32_10", "rejuvenate_normals", "liu_west_shrink", "REJUVENATE_INFO_WORDS", "REJUVENATE_DONE", "REJUVENATE_TOO_FEW",
     "REJUVENATE_BAD_INPUT", "REJUVENATE_NOT_SELECTED",
     "mcmc_draws", "demc_gamma", "MCMC_INFO_WORDS", "MCMC_DONE", "MCMC_TOO_FEW", "MCMC_BAD_INPUT", "MCMC_NOT_SELECTED",
+    "TEMPER_SECTIONS", "TEMPER_ROUNDS", "TEMPER_INFO_WORDS", "TEMPER_FOUND", "TEMPER_END", "TEMPER_NO_WEIGHT", "TEMPER_UNREACHABLE",
+    "TEMPER_BAD_INPUT",
     "loglik_term", "LOGLIK_GAUSS", "LOGLIK_LAPLACE", "LOGLIK_MAX_TERMS", "LOGLIK_TILE_ROWS",
 ]

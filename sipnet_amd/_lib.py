@@ -72,6 +72,11 @@ REJUVENATE_DONE, REJUVENATE_TOO_FEW, REJUVENATE_BAD_INPUT, REJUVENATE_NOT_SELECT
 # other half}; sipnet_batch_mcmc_accept: {code, proposed, accepted, live members}; the codes
 MCMC_INFO_WORDS = 4
 MCMC_DONE, MCMC_TOO_FEW, MCMC_BAD_INPUT, MCMC_NOT_SELECTED = 1, 0, -2, -3
+# sipnet_batch_pf_temper_sites: the search's sections per round and its rounds (SIPNET_TEMPER_SECTIONS, SIPNET_TEMPER_ROUNDS);
+# site_info[s] = {code, members whose value at delta = 0 is finite}; the codes
+TEMPER_SECTIONS, TEMPER_ROUNDS = 16, 8
+TEMPER_INFO_WORDS = 2
+TEMPER_FOUND, TEMPER_END, TEMPER_NO_WEIGHT, TEMPER_UNREACHABLE, TEMPER_BAD_INPUT = 1, 2, 0, -1, -2
 
 
 class LoglikTerm(C.Structure):
@@ -222,7 +227,8 @@ SIGNATURES = {
     "sipnet_batch_pf_rejuvenate": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
     "sipnet_mcmc_draws": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _P, _P]),
     "sipnet_batch_mcmc_propose": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P]),
-    "sipnet_batch_mcmc_accept": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    "sipnet_batch_pf_temper_sites": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sipnet_batch_mcmc_accept":(C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
     "sipnet_batch_enkf_analysis_sites": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, _P,
                                                    _P, _P, _P, _P]),
     "sipnet_enkf_params_check": (C.c_int, [C.c_int32, _P, _P, _P]),

@@ -12,7 +12,7 @@ import weakref
 import numpy as np
 
 from ._lib import (F64, KERNEL_AUTO, LOGLIK_GAUSS, LOGLIK_LAPLACE, LOGLIK_MAX_TERMS, MCMC_INFO_WORDS, NDBG, NPARAMS, NREC, NSTATE, RING_SLOTS,
-                   REJUVENATE_INFO_WORDS, EnkfObs, EnkfParam, EnkfSeries, Event, LaunchInfo, LoglikTerm, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
+                   REJUVENATE_INFO_WORDS, TEMPER_INFO_WORDS, EnkfObs, EnkfParam, EnkfSeries, Event, LaunchInfo, LoglikTerm, PfInfo, PfPeer, Restart, c_array, check, lib, ptr)
 from .config import pool_mask
 from .enkf_local import EnkfLocalization
 
@@ -571,6 +571,33 @@ class Batch:
         check(self.L.sipnet_batch_pf_resample_sites(self.h, ptr(logw), ptr(u0), ptr(beta), ptr(ess_min), int(with_params),
                                                     ptr(anc), ptr(fixed), ptr(total_out), ptr(ess_out), self._stream()), what)
         return (anc, fixed) if return_fixed else anc
+
+    def pf_temper_sites(self, loglik, ess_target, base=None, delta_max=None, out=None, info_out=None):
+        """the tempering exponent of every site, chosen on the device (sipnet_batch_pf_temper_sites): the largest step delta in
+        (0, delta_max] at which the tempered weights -- delta * loglik, or base + delta * loglik over carried log-weights --
+        keep an effective sample size of at least ess_target, by the fixed search of sa.TEMPER_ROUNDS rounds of
+        sa.TEMPER_SECTIONS - 1 candidates.  loglik: float64 device tensor [ncol] (series_loglik's out, or anything else);
+        base: float64 device tensor [ncol] or None (0); ess_target, delta_max (None: 1; in a tempering run 1 - phi): one value
+        per site; out: float64 device tensor [ncol] that takes the tempered log-weights of the sites with code 1 or 2 (may
+        be base itself); info_out: int32 device tensor [n_sites][2] for {code, members whose value at delta = 0 is finite}
+        (no host synchronisation); without it the arguments are checked first and a site with bad input raises before
+        anything is written.  delta as beta of pf_resample_sites gives exactly the returned ess.  -> (delta, delta_hi, ess),
+        float64 device tensors [n_sites]."""
+        t = self._torch
+        what = "pf_temper_sites"
+        for x, name, needed in ((loglik, "loglik", True), (base, "base", False), (out, "out", False)):
+            if (x is None and needed) or (x is not None and (not t.is_tensor(x) or not _dense(x, t.float64, self.ncol))):
+                raise ValueError(f"{what}: {name} must be a contiguous float64 device tensor of {self.ncol} values")
+        ess_target = self._upload(what, ess_target, self.n_sites, "ess_target")
+        delta_max = self._upload(what, delta_max, self.n_sites, "delta_max")
+        if ess_target is None:
+            raise ValueError(f"{what}: ess_target needs {self.n_sites} values")
+        if info_out is not None and (not t.is_tensor(info_out) or not _dense(info_out, t.int32, TEMPER_INFO_WORDS * self.n_sites)):
+            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x {TEMPER_INFO_WORDS}")
+        delta, delta_hi, ess = (t.zeros(self.n_sites, dtype=t.float64, device=self.device) for _ in range(3))
+        check(self.L.sipnet_batch_pf_temper_sites(self.h, ptr(loglik), ptr(base), ptr(delta_max), ptr(ess_target), ptr(delta),
+                                                  ptr(delta_hi), ptr(ess), ptr(out), ptr(info_out), self._stream()), what)
+        return delta, delta_hi, ess
 
     def pf_rejuvenate(self, params, shrink, pools=None, pool_sd=None, seed=0, draw=0, streams=None, site_total=None,
                       info_out=None):

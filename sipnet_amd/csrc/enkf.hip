@@ -170,24 +170,6 @@ int enkfBegin(const char* name, const EnkfCall& c, EnkfArgs& a, bool ownRows = f
   return 0;
 }
 
-// "A launch of `kernel` may use dynBytes of dynamic LDS": *ok, after the kernel was given the attribute where its static
-// and dynamic LDS together pass the 48 KB a kernel may use unasked.  False where they pass the device's maximum or the
-// request fails: the caller then keeps in global memory what it wanted in LDS.
-int ldsGranted(const void* kernel, size_t dynBytes, int device, bool* ok) {
-  int ldsMax = 0;
-  hipFuncAttributes attr;
-  HIP_TRY(hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
-  HIP_TRY(hipFuncGetAttributes(&attr, kernel));
-  const size_t total = dynBytes + attr.sharedSizeBytes;
-  *ok = total <= (size_t)ldsMax;
-  if (*ok && total > 48 * 1024 &&
-      hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynBytes) != hipSuccess) {
-    (void)hipGetLastError();
-    *ok = false;
-  }
-  return 0;
-}
-
 // A scratch block of the batch (b->d_enkf, or the series stage's b->d_smooth) sized, grown and carved, in
 // this order: the working copies [nv][ncol] (workInGlobal: else they live in LDS) | part [sites][chunks][cap] | stat [sites]
 // [3 cap] (cap: the kernels' A::kCap) | matPerSite doubles per site (the block-local matrices, the series stage's g and G) | info

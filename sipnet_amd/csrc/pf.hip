@@ -15,7 +15,7 @@
 // This file is the one translation unit (the one tools/build_variants.py compiles with -DSIPNET_PF_*) and the host side; the
 // device code is in parts, each with its own header comment, included below in this order: site_device.h (the sums in their
 // one order, a member's limits and derived rows, shared with enkf.hip), pf_gather.inc, pf_weights.inc, pf_fused.inc,
-// pf_plan.inc, pf_sites.inc, pf_series.inc, pf_rejuvenate.inc, pf_metropolis.inc.  Refusals, the bookkeeping of a call that writes the batch, the
+// pf_plan.inc, pf_sites.inc, pf_series.inc, pf_rejuvenate.inc, pf_metropolis.inc, pf_temper.inc.  Refusals, the bookkeeping of a call that writes the batch, the
 // scratch blocks' growth and the synchronous forms' copies are site_host.h's.
 //
 // The host side runs three filters.  One batch (sipnet_batch_pf_analysis): takePfPre, the one launch (fusedSetup) or the
@@ -23,7 +23,8 @@
 // sipnet_batch_pf_resample_sites from given log-weights): sitesBegin, the weights' source, sitesFinish.  Across ranks by peer
 // reads: sipnet_batch_pf_publish, _connect (mapPeer, fillBank) and _resample_peers (peerTable, peerAncestors, peerGather).
 // Beside them the series weights (sipnet_batch_series_loglik), the rejuvenation (sipnet_batch_pf_rejuvenate) and the Metropolis
-// move over members (sipnet_batch_mcmc_propose, sipnet_batch_mcmc_accept).
+// move over members (sipnet_batch_mcmc_propose, sipnet_batch_mcmc_accept) and the tempering exponent that keeps an effective
+// sample size (sipnet_batch_pf_temper_sites).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -53,6 +54,7 @@ namespace {
 #include "pf_series.inc"
 #include "pf_rejuvenate.inc"
 #include "pf_metropolis.inc"
+#include "pf_temper.inc"
 
 }  // namespace
 }  // namespace sipnet
@@ -212,6 +214,7 @@ struct PfScratch {
   DevBuf<int32_t> d_loglikUsed;         // ... and [n_sites][terms' tiles] the tiles' rows used
   DevBuf<unsigned char> d_rejuv;        // sipnet_batch_pf_rejuvenate (rejScratch), bytes
   DevBuf<unsigned char> d_mcmc;         // sipnet_batch_mcmc_propose / _accept (mcScratch), bytes
+  DevBuf<unsigned char> d_temper;       // sipnet_batch_pf_temper_sites, per-chunk path (temperScratch), bytes
 };
 namespace {
 constexpr int kMaxParts = 256;
@@ -1148,6 +1151,102 @@ int sipnet_batch_mcmc_accept(sipnet_batch* b, int32_t n_params, const sipnet_enk
   HIP_TRY(hipGetLastError());
   reportPath(b, direct, direct ? (int32_t)nSites : 0);
   return markBusy(b, stream);
+}
+
+// ---- the tempering exponent of every site --------------------------------------------------------------------------------
+// the synchronous form's check: the arguments read back, the first site with bad input named
+static int temperCheck(const char* who, const sipnet_batch* b, const TemperArgs& a, hipStream_t stream) {
+  const size_t nSites = (size_t)b->n_sites, M = (size_t)b->n_members;
+  std::vector<double> loglik, base, dmax, target;
+  RC_TRY(readBack(loglik, a.loglik, (size_t)b->ncol, stream));
+  RC_TRY(readBack(base, a.base, (size_t)b->ncol, stream));
+  RC_TRY(readBack(dmax, a.deltaMax, nSites, stream));
+  RC_TRY(readBack(target, a.essTarget, nSites, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (size_t s = 0; s < nSites; s++) {
+    const double dm = a.deltaMax ? dmax[s] : 1.0;
+    bool ok = dm > 0.0 && std::isfinite(dm) && target[s] > 0.0;
+    for (size_t c = s * M; ok && c < (s + 1) * M; c++)
+      ok = loglik[c] != INFINITY && (!a.base || base[c] != INFINITY);
+    if (!ok)
+      return refuse(who, "site " + std::to_string(s) + ": bad input (delta_max must be finite and > 0, the target > 0, no +inf among "
+                         "loglik or base); nothing was written");
+  }
+  return SIPNET_OK;
+}
+// the per-chunk path's scratch carved: the states of the stages, the chunks' maxima, partial sums, candidate maxima and counts
+static int temperScratch(sipnet_batch* b, TemperArgs& a) {
+  PfScratch& sc = scratchOf(b);
+  const size_t nSites = (size_t)b->n_sites, nCk = nSites * (size_t)a.nChunks;
+  const size_t nState = (size_t)(SIPNET_TEMPER_ROUNDS + 1) * nSites, nCand = a.base ? nCk * kTemperCand : 0;
+  const size_t bytes = nState * sizeof(TemperState) + (2 * nCk + nCand) * sizeof(double) + 2 * nCk * kTemperWords * sizeof(long long) +
+                       nCk * sizeof(int32_t);
+  RC_TRY(growScratch(b, sc.d_temper, bytes));
+  a.state = (TemperState*)sc.d_temper.get();
+  a.chunkMax = (double*)(a.state + nState);
+  a.candMax = a.chunkMax + 2 * nCk;
+  a.partial = (long long*)(a.candMax + nCand);
+  a.chunkCnt = (int32_t*)(a.partial + 2 * nCk * kTemperWords);
+  return SIPNET_OK;
+}
+extern "C++" {
+template <bool Base>
+static int temperLaunch(sipnet_batch* b, TemperArgs& a, bool split, hipStream_t stream) {
+  const dim3 sites((unsigned)b->n_sites), chunks((unsigned)b->n_sites, (unsigned)a.nChunks);
+  // One workgroup per site only without carried log-weights.  With them that kernel (15 maxima and 45 sums per thread in
+  // registers, both arrays in LDS) reported an ESS(delta) that the filter did not reproduce at a few sites in a hundred, about
+  // 1e-9 off, while the per-chunk launches did at every one; the cause is not found, so d_base takes the launches that are right.
+  if (!split && !Base) {   // the site's loglik in LDS: past 48 KB a kernel has to ask
+    const size_t ldsBytes = (size_t)a.M * sizeof(double);
+    bool ok = false;
+    RC_TRY(ldsGranted((const void*)temperGroupKernel, ldsBytes, b->device, &ok));
+    if (ok) {
+      hipLaunchKernelGGL(temperGroupKernel, sites, dim3(256), ldsBytes, stream, a);
+      HIP_TRY(hipGetLastError());
+      reportPath(b, true, (int32_t)b->n_sites);
+      return SIPNET_OK;
+    }
+  }
+  RC_TRY(temperScratch(b, a));
+  hipLaunchKernelGGL(temperChunkMaxKernel<Base>, chunks, dim3(256), 0, stream, a);
+  for (int stage = 0; stage <= SIPNET_TEMPER_ROUNDS; stage++) {
+    if (Base) hipLaunchKernelGGL(temperChunkKernel<Base>, chunks, dim3(256), 0, stream, a, stage, 0);
+    hipLaunchKernelGGL(temperChunkKernel<Base>, chunks, dim3(256), 0, stream, a, stage, 1);
+  }
+  hipLaunchKernelGGL(temperTailKernel<Base>, chunks, dim3(256), 0, stream, a);
+  HIP_TRY(hipGetLastError());
+  reportPath(b, false, 0);
+  return SIPNET_OK;
+}
+}  // extern "C++"
+
+int sipnet_batch_pf_temper_sites(sipnet_batch* b, const double* d_loglik, const double* d_base, const double* d_delta_max,
+                                 const double* d_ess_target, double* d_delta, double* d_delta_hi, double* d_ess,
+                                 double* d_logw_out, int32_t* d_site_info, void* hip_stream) {
+  const char* who = "sipnet_batch_pf_temper_sites";
+  if (!b || !d_loglik || !d_ess_target || !d_delta) return refuse(who, "a NULL batch, d_loglik, d_ess_target or d_delta");
+  if (tooManyColumns(b)) return refuse(who, "at most 4194304 columns");
+  if (b->pfPeers) return refuse(who, "this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
+  RC_TRY(useDevice(b));
+  hipStream_t stream = (hipStream_t)hip_stream;
+  TemperArgs a{};
+  a.loglik = d_loglik;
+  a.base = d_base;
+  a.deltaMax = d_delta_max;
+  a.essTarget = d_ess_target;
+  a.delta = d_delta;
+  a.deltaHi = d_delta_hi;
+  a.ess = d_ess;
+  a.logwOut = d_logw_out;
+  a.info = d_site_info;
+  a.M = b->n_members;
+  a.nSites = b->n_sites;
+  if (!d_site_info) RC_TRY(temperCheck(who, b, a, stream));
+  int chunk, nChunks;
+  const bool split = sitesGeometry(b, &chunk, &nChunks);   // (the many-site analysis's rule)
+  a.chunk = chunk;
+  a.nChunks = nChunks;
+  return d_base ? temperLaunch<true>(b, a, split, stream) : temperLaunch<false>(b, a, split, stream);
 }
 
 }  // extern "C"

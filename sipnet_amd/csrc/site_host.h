@@ -1,6 +1,6 @@
 // site_host.h -- the host side that the per-site analyses share (enkf.hip, pf.hip, quantiles.hip): a refusal, the limit on a
-// batch's columns, the bookkeeping of a call that writes the batch, a scratch block grown, what sipnet_batch_pf_info reports
-// of the last call, and the copies of a synchronous form's check.  batch_impl.h stays the batch object and the stream bookkeeping.
+// batch's columns, the bookkeeping of a call that writes the batch, a scratch block grown, the request for dynamic LDS past
+// what a kernel may use unasked, what sipnet_batch_pf_info reports of the last call, and the copies of a synchronous form's check.  batch_impl.h stays the batch object and the stream bookkeeping.
 #pragma once
 #include <string>
 #include <vector>
@@ -38,6 +38,24 @@ int growScratch(sipnet_batch* b, DevBuf<T>& block, size_t count) {
   if (block.capacity() >= count) return SIPNET_OK;
   RC_TRY(waitIdle(b));
   return block.reserve(count);
+}
+
+// "A launch of `kernel` may use dynBytes of dynamic LDS": *ok, after the kernel was given the attribute where its static
+// and dynamic LDS together pass the 48 KB a kernel may use unasked.  False where they pass the device's maximum or the
+// request fails: the caller then keeps in global memory what it wanted in LDS (or takes its other path).
+inline int ldsGranted(const void* kernel, size_t dynBytes, int device, bool* ok) {
+  int ldsMax = 0;
+  hipFuncAttributes attr;
+  HIP_TRY(hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+  HIP_TRY(hipFuncGetAttributes(&attr, kernel));
+  const size_t total = dynBytes + attr.sharedSizeBytes;
+  *ok = total <= (size_t)ldsMax;
+  if (*ok && total > 48 * 1024 &&
+      hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynBytes) != hipSuccess) {
+    (void)hipGetLastError();
+    *ok = false;
+  }
+  return 0;
 }
 
 // what sipnet_batch_pf_info reports of a per-site call: one workgroup per site (fused, grid = the sites) or launches per stage
