@@ -1468,6 +1468,25 @@ int sipnet_debug_enkf_local_serial(sipnet_enkf_local *L, int32_t on);
  * the runtime -- what sipnet_dev_alloc hands out is the caller's and is not counted.  Either pointer may be NULL.  Back at
  * its earlier value once everything made since has been destroyed: a leak check that other users of the device do not disturb. */
 int sipnet_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
+/* sipnet_debug_fast_math: the arithmetic helpers of the throughput kernels (csrc/fast_math.h) on their own, compiled as
+ * those kernels compile them: out[i] = op(x[i], y[i]) for n elements, d_x, d_y and d_out DEVICE arrays of double; one
+ * launch on the null stream, finished when the call returns.  precision SIPNET_F32_MIXED: the kernel narrows the
+ * operands to float, runs the float overload and widens the result; SIPNET_FM_RECR instead reads the slot's low word as
+ * the float it holds (the narrow fields of an fp32-mixed site record).  d_y is read by SIPNET_FM_DIV (x / y) and
+ * SIPNET_FM_RMINV (min(x, y)) alone and may be NULL for the others.  info (may be NULL): the exp2 polynomial's degree
+ * and the Newton steps of the division this library was compiled with.  SIPNET_ERR_BAD_ARGUMENT: an unknown op or
+ * precision, n < 0 or n > 2^31 (one launch covers no more), a NULL array with n > 0; nothing is launched and info is
+ * left alone.  SIPNET_ERR_NO_DEVICE: the launch or the wait for it failed (sipnet_last_error has the runtime's text). */
+enum sipnet_fast_math_op {
+  SIPNET_FM_EXP2 = 0,   /* fexp2(x) */
+  SIPNET_FM_DIV = 1,    /* fdiv(x, y) */
+  SIPNET_FM_RMINV = 2,  /* rminv(x, y) */
+  SIPNET_FM_RMAX0 = 3,  /* rmax0(x) */
+  SIPNET_FM_CLIP01 = 4, /* clip01(x) */
+  SIPNET_FM_RECR = 5    /* recR<R>(x) */
+};
+int sipnet_debug_fast_math(int32_t op, int32_t precision, int64_t n, const double *d_x, const double *d_y, double *d_out,
+                           int32_t info[2]);
 
 /* Device buffer helpers for callers without their own allocator (the CLI). */
 void *sipnet_dev_alloc(size_t bytes);

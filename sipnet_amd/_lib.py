@@ -26,6 +26,7 @@ ERR_NO_DEVICE = 100
 ERR_BAD_ARGUMENT = 101
 
 F64, F32_MIXED = 0, 1
+FM_EXP2, FM_DIV, FM_RMINV, FM_RMAX0, FM_CLIP01, FM_RECR = range(6)   # enum sipnet_fast_math_op (sipnet_debug_fast_math)
 # enum sipnet_kernel / sipnet_kernel_option
 KERNEL_AUTO, KERNEL_ONE_WAVE, KERNEL_COOP_LDS, KERNEL_COOP_HBM, KERNEL_STRICT, KERNEL_COOP_PAIR, KERNEL_COOP_QUAD = range(7)
 KERNEL_COOP_NCYCLE = 7
@@ -326,6 +327,7 @@ SIGNATURES = {
     "sipnet_debug_set_num_cus": (C.c_int, [_P, C.c_int32]),
     "sipnet_debug_pf_barrier": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "sipnet_debug_live_bytes": (C.c_int, [_P, _P]),
+    "sipnet_debug_fast_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     "sipnet_batch_set_device_share": (C.c_int, [_P, C.c_int32]),
     "sipnet_batch_pf_info": (C.c_int, [_P, _P, _P]),
     "sipnet_stream_sync": (C.c_int, [_P]),

@@ -989,3 +989,27 @@ def debug_live_bytes():
     dev, pin = C.c_int64(0), C.c_int64(0)
     check(lib().sipnet_debug_live_bytes(C.byref(dev), C.byref(pin)), "debug_live_bytes")
     return dev.value, pin.value
+
+
+def debug_fast_math(op, x, y=None, prec=F64, info=None):
+    """test hook (sipnet_debug_fast_math): the throughput kernels' arithmetic helper `op` (_lib.FM_EXP2, FM_DIV, FM_RMINV,
+    FM_RMAX0, FM_CLIP01, FM_RECR) on every element of the float64 tensor x (and y, for FM_DIV and FM_RMINV), as those kernels
+    compile it; prec F32_MIXED: the float overload on the narrowed operands (FM_RECR: on the slot's low word), widened.
+    info: a list that receives the exp2 polynomial's degree and the division's Newton steps of the loaded library.
+    -> the results, a float64 tensor of x's shape on x's device"""
+    import torch
+    x = x.to(dtype=torch.float64).contiguous()
+    assert x.is_cuda, "debug_fast_math: x must be on the device"
+    if y is not None:
+        y = y.to(device=x.device, dtype=torch.float64).contiguous()
+        assert y.numel() == x.numel()
+    out = torch.empty_like(x)
+    words = (C.c_int32 * 2)()
+    with torch.cuda.device(x.device):
+        torch.cuda.current_stream().synchronize()       # (the hook launches on the null stream)
+        check(lib().sipnet_debug_fast_math(int(op), int(prec), x.numel(), ptr(x) if x.numel() else None,
+                                           ptr(y) if y is not None and y.numel() else None,
+                                           ptr(out) if x.numel() else None, words), "debug_fast_math")
+    if info is not None:
+        info[:] = [words[0], words[1]]
+    return out

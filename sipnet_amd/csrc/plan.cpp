@@ -76,7 +76,7 @@ void fillFastRec(const StepRec& s, const RingOp* ops, bool tsoilSame, int phenMo
   f.tair = s.tair;
   f.tsoil = s.tsoil;
   f.negPar = -s.par;
-  f.vpd = s.vpd;
+  f.vpd = (s.vpd > 0.0 && s.vpd < kVpdFloor) ? kVpdFloor : s.vpd;   // (plan.h: the divisor of moisture() stays in fdiv's range)
   f.rainRate = s.rainRate;
   f.sublW = s.sublNum * s.wspd;
   f.evapNum = s.evapNum;
@@ -129,6 +129,7 @@ double narrowSlot(double v) {
 void narrowFastRec(FastRec& f) {
   double* const slots[] = {&f.tair,  &f.tsoil,   &f.negPar,  &f.vpd,    &f.tillP1,  &f.rainRate,
                            &f.sublW, &f.evapNum, &f.invWspd, &f.tair10, &f.tsoil10, &f.log2vpd};
+  if (f.vpd > 0.0 && f.vpd < kVpdFloorNarrow) f.vpd = kVpdFloorNarrow;   // (plan.h)
   for (double* p : slots) *p = narrowSlot(*p);
 }
 

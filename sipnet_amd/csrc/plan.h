@@ -73,6 +73,12 @@ static_assert(sizeof(EvRec) == 40, "EvRec layout");
 // time loop; the rest is read only when a flag bit says so.  It carries the step's ring
 // evictions and the NEXT step's eviction slots, so that the ring values of step t+1 are
 // requested during step t.
+// FastRec::vpd has a floor: a positive VPD below kVpdFloor (fp32-mixed records: kVpdFloorNarrow) is stored as the floor.
+// moisture() divides by potTrans = potGrossPsn * vpd * K_tr through a reciprocal (fast_math.h, fdiv), whose range ends at
+// 2^-1024 (float: 2^-126); with potGrossPsn >= 1e-6 and K_tr >= 1e-3 the floors keep potTrans inside it, and a transpiration
+// of 1e-280 instead of 1e-309 changes no result.  Only an array handed over by a caller can hold such a VPD (a reader floors a
+// file's 0 at 1e-6); 0 itself stays 0 (potTrans = 0 is selected away).  Both plan builders apply it (plan.cpp, plan_device.hip).
+constexpr double kVpdFloor = 0x1p-900, kVpdFloorNarrow = 0x1p-90;
 // NARROW fields (marked [n]): climate values the step only uses at the precision of its flux arithmetic.  In the
 // records of an fp32-mixed batch (buildSitePlan(..., narrowFast = true)) such a slot holds the correctly rounded
 // FLOAT in its low four bytes and a quiet-NaN tag in the high four; the fp32 kernels take the low word (fast_math.h,

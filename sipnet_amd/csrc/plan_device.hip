@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void planExpandKernel(DevPlanArgs a) {
   f.tair = tair;
   f.tsoil = tsoil;
   f.negPar = -par;
-  f.vpd = vpd;
+  f.vpd = (vpd > 0.0 && vpd < kVpdFloor) ? kVpdFloor : vpd;   // (plan.h)
   f.tillP1 = 1.0 + dTill;
   f.rainRate = precip / len;
   f.sublW = (a.convS * (kEStarSnow - vPress)) * wspd;
@@ -384,6 +384,7 @@ __global__ __launch_bounds__(256) void planExpandKernel(DevPlanArgs a) {
   f.tileEndDayTime = maxDay;
   for (int k = 0; k < 6; k++) f.pad[k] = 0;
   if (a.narrow) {
+    if (f.vpd > 0.0 && f.vpd < kVpdFloorNarrow) f.vpd = kVpdFloorNarrow;   // (plan.h)
     f.tair = narrowSlotDev(f.tair); f.tsoil = narrowSlotDev(f.tsoil); f.negPar = narrowSlotDev(f.negPar); f.vpd = narrowSlotDev(f.vpd);
     f.tillP1 = narrowSlotDev(f.tillP1); f.rainRate = narrowSlotDev(f.rainRate); f.sublW = narrowSlotDev(f.sublW);
     f.evapNum = narrowSlotDev(f.evapNum); f.invWspd = narrowSlotDev(f.invWspd); f.tair10 = narrowSlotDev(f.tair10);

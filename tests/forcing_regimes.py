@@ -17,6 +17,8 @@ synth.half_hourly_year_raw, so synth.round_like_file, synth.convert_raw and synt
              sixty days of 12-hour steps in its middle, both switches off a 16-step tile boundary
   tiny       `threshold` converted, with some of its exact zeros replaced by +-1e-300 and +-5e-324 (in memory only:
              a file cannot print them): positive or negative in fp64, zero once narrowed to fp32
+  tiny_vpd   three summer days of `threshold` from first light with a VPD of 1e-307 (in memory only), for dry_members(): a
+             potential transpiration below 2^-1024 that divides a removable water of exactly 0
 
 Everything is generated here from seeds; nothing is copied from any input file.  tests/test_forcing_regimes.py asserts
 the properties above (a regime that degenerates into the temperate climate fails there) and holds the conditioning
@@ -212,6 +214,32 @@ def tiny(site=0, seed=SEED, gdd=1):
     if gdd:
         d[:, 9] = np.maximum(d[:, 1] * d[:, 0], 0.0)            # convert_raw's growing degree days of the new tair
     return ClimTable(d, clim.year, clim.day)
+
+
+VPD_TINY = (1e-307, 2e-307)
+
+
+def tiny_vpd(site=0, seed=SEED, gdd=1, days=3):
+    """`days` summer days of `threshold`, from the first light of day 171, with the VPD of three steps in four at 1e-307 or
+    2e-307 (in memory only: a reader floors a file's 0 at 1e-6; below about 6e-308 the reference's own wueConst / vpd overflows
+    and its GPP is NaN).  Potential transpiration, the product of the potential photosynthesis, the VPD and 1 / wueConst, is
+    then positive and, in the weak light of the first step, below 2^-1024 for most members: a soil with no water at all has
+    removable = 0 < potTrans, and the reference divides 0 by it (GPP 0) where a reciprocal overflows."""
+    whole = synth.convert_raw(raw("threshold", site, seed), gdd)
+    first = 170 * 48 + 9
+    c = whole.slice(first, first + days * 48)
+    d = c.data.copy()
+    k = np.arange(d.shape[0])
+    d[:, 5] = np.where(k % 4 == 3, d[:, 5], np.asarray(VPD_TINY)[k % 2])
+    return ClimTable(d, c.year, c.day)
+
+
+def dry_members(base, n=130):
+    """hard_members with no soil water at the start in every second member (soilWFracInit 0)"""
+    from sipnet_amd.config import param_index as pi
+    members = hard_members(base, n)
+    members[::2, pi("soilWFracInit")] = 0.0
+    return members
 
 
 def clim(name, site=0, seed=SEED, gdd=1):

@@ -166,6 +166,28 @@ def test_tiny():
     assert np.array_equal(np.delete(t.data, [1, 2, 3, 9], axis=1), np.delete(c.data, [1, 2, 3, 9], axis=1))
 
 
+def test_tiny_vpd_reaches_a_potential_transpiration_below_the_reciprocals_range(oracle):
+    """the divisor of moisture()'s removable / potTrans: with a VPD of 1e-307 in the first light it is positive and below 2^-1024
+    for most members (the GPP plane of a member with water is potGrossPsn * length; potTrans = potGrossPsn * vpd / wueConst, and
+    wueConst is above 1), and a member with no soil water divides 0 by it: the oracle's GPP is exactly 0 there, positive next door"""
+    c = fr.tiny_vpd()
+    m = fr.dry_members(sa.read_params(BASE, FLAGS)[0])
+    assert c.n_steps == 144 and c.data[0, 3] > 0.1                            # starts by day
+    v = c.data[:, 5]
+    assert set(np.unique(v[np.arange(144) % 4 != 3])) == set(fr.VPD_TINY) and (v[3::4] >= TINY).all()
+    assert (m[::2, pi("soilWFracInit")] == 0.0).all() and (m[1::2, pi("soilWFracInit")] > 0.0).sum() >= 55
+    planes, final, st = oracle.run_block(FLAGS, m, c)
+    ok = st == 0
+    assert ok.sum() >= 125 and np.isfinite(planes[:, :, ok]).all()
+    gpp0 = planes[1, 0, :]
+    dry, wet = ok & (np.arange(133) % 2 == 0), ok & (np.arange(133) % 2 == 1)
+    assert (m[:, pi("wueConst")] > 1.0).all()
+    pot = gpp0[wet] / c.data[0, 0]                                           # potential photosynthesis of the members with water
+    assert (gpp0[dry] == 0.0).all() and (pot >= 1e-6).sum() >= 40
+    pot_trans = pot * c.data[0, 5] / m[wet, pi("wueConst")]
+    assert ((pot >= 1e-6) & (pot_trans < 2.0 ** -1024)).sum() >= 30          # ... in the window, and their dry neighbours alike
+
+
 @pytest.mark.parametrize("name", fr.FILE_REGIMES)
 def test_file_round_trip_is_bit_for_bit(name, tmp_path):
     raw = fr.raw(name)

@@ -185,6 +185,48 @@ def test_three_sites_three_regimes_three_lengths(family, kernel, prec, ref):
         judge(f"site {s} {r} {name}", prec, got[:, :clims[s].n_steps, cols], state[cols], status[cols], want, final, st)
 
 
+@pytest.mark.parametrize("family,prec", FAMILIES, ids=[f + ("_f64" if p == sa.F64 else "_f32") for f, p in FAMILIES])
+def test_a_dry_soil_under_a_vanishing_vpd_divides_zero_by_a_denormal(family, prec, ref, oracle):
+    """what the test of fdiv on its own found (tests/test_gpu_fast_math.py): moisture()'s removable / potTrans is taken by a
+    reciprocal, which overflows for 0 < potTrans < 2^-1024 (fp32-mixed: for a denormal float), and with removable = 0 the
+    quotient came back NaN where the reference's is 0 -- and was not selected away, because removable < potTrans holds.
+    fr.tiny_vpd() with fr.dry_members() reaches it at the first step; the plan builders now floor the record's VPD (plan.h,
+    kVpdFloor), which keeps the divisor in the range and changes no result."""
+    flags = ref.flags("default")
+    members = fr.dry_members(sa.read_params(os.path.join(DATA, "base_forest.param"), flags)[0])
+    clim = fr.tiny_vpd()
+    want, final, st = oracle.run_block(flags, members, clim)
+    kernel = {"strict": sa.KERNEL_AUTO, "one_wave": sa.KERNEL_ONE_WAVE, **COOP}[family]
+    b = batch(flags, [clim], members, prec, kernel, strict=family == "strict")
+    planes, _ = b.run()
+    name = b.last_launch()["kernel"]
+    got, state, status = planes.double().cpu().numpy(), b.get_state(), b.get_status()
+    b.close()
+    assert family_ok(family, "default", name), name
+    ok = st == 0
+    assert np.isfinite(got[:, :, ok]).all(), f"{name}: {int((~np.isfinite(got[:, :, ok])).any(axis=(0, 1)).sum())} members not finite"
+    judge(f"tiny_vpd, dry members, {name}", prec, got, state, status, want, final, st)
+
+
+@pytest.mark.parametrize("prec", [sa.F64, sa.F32_MIXED], ids=["f64", "f32"])
+@pytest.mark.parametrize("plan", [sa.KOPT_HOST_PLAN, sa.KOPT_DEVICE_PLAN], ids=["host_plan", "device_plan"])
+def test_both_plan_builders_floor_a_vanishing_vpd(plan, prec, oracle, ref):
+    """the same input through the host's and the device's plan builder: the same bits, and the regime bounds"""
+    flags = ref.flags("default")
+    members = fr.dry_members(sa.read_params(os.path.join(DATA, "base_forest.param"), flags)[0])
+    clim = fr.tiny_vpd()
+    want, final, st = oracle.run_block(flags, members, clim)
+    b = batch(flags, [clim], members, prec, sa.KERNEL_COOP_LDS, plan)
+    planes, _ = b.run()
+    li = b.last_launch()
+    got, state, status = planes.double().cpu().numpy(), b.get_state(), b.get_status()
+    b.close()
+    assert li["plan_device_sites"] == (1 if plan == sa.KOPT_DEVICE_PLAN else 0), li
+    judge(f"tiny_vpd, plan option {plan}, {li['kernel']}", prec, got, state, status, want, final, st)
+    other = outputs(batch(flags, [clim], members, prec, sa.KERNEL_COOP_LDS, sa.KOPT_HOST_PLAN + sa.KOPT_DEVICE_PLAN - plan))
+    same(outputs(batch(flags, [clim], members, prec, sa.KERNEL_COOP_LDS, plan)), other, "one plan builder against the other")
+
+
 @pytest.mark.parametrize("plan", [sa.KOPT_HOST_PLAN, sa.KOPT_DEVICE_PLAN], ids=["host_plan", "device_plan"])
 @pytest.mark.parametrize("family", ["one_wave", "coop_lds", "coop_quad"])
 def test_a_soil_just_below_a_frozen_threshold_of_zero_is_frozen_in_fp32_mixed(family, plan, ref, oracle):

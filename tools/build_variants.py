@@ -16,7 +16,7 @@ CSRC = os.path.join(REPO, "sipnet_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall",
         "-Wno-unused-function"]
-FAST_SRCS = ["step_fast.hip", "step_coop.hip"]                      # -ffp-contract=fast
+FAST_SRCS = ["step_fast.hip", "step_coop.hip", "fast_math_probe.hip"]   # -ffp-contract=fast (the probe: the variant's SIPNET_EXP2_DEGREE / SIPNET_FDIV_NEWTON, for tests/test_gpu_fast_math.py)
 OTHER_OBJS = ["engine.o", "engine_plan.o", "engine_run.o", "engine_state.o", "engine_mem.o", "step_kernel.o", "step_coop_bounded.o", "step_coop_sums.o", "step_fast_sums.o", "pf.o", "enkf.o", "quantiles.o", "plan_device.o", "plan.o", "host_io.o", "restart_io.o", "ensemble_io.o", "node.o"]
 
 
