@@ -17,6 +17,7 @@
   // =============================================================================================
   // ---- C: carbon fluxes, pools, trackers, running mean (sipnet.c:756-842, 1051-1196, 1420-1806)
   COOP_CODE_PHASE(0);
+  constexpr bool Carried = kCoopCarriedTile<R, PlainExp, RingLds, Full, NP, NCyc, Ext, Sums>;
   const R K_invLcsw = (R)(1.0 / PRM(leafCSpWt));
   const R K_wtr = (R)PRM(woodTurnoverRate), K_ltr = (R)PRM(leafTurnoverRate);
   const R K_frt = (R)PRM(fineRootTurnoverRate), K_crt = (R)PRM(coarseRootTurnoverRate);
@@ -179,6 +180,7 @@
     }
   };
 
+  if constexpr (Carried) COOP_CARRIED_PAD(0);
   for (int tileStart = curTile * kFastTile; tileStart < tEnd; tileStart += kFastTile, curTile++) {
     // the DMA of this tile was issued a tile ago; only the last step's two stores may still be
     // in flight behind it
@@ -233,6 +235,9 @@
         double vPrev = 0.0;
         if (nOps == 2) {
           const int s0 = slots0 & 255;
+          if constexpr (Carried)   // (read and awaited by hand, like every DS access of the step: the compiler counts none of its own there)
+            asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(vPrev) : "v"(ldsAddr(&ringL[s0 * 64 + lane])) : "memory");
+          else
           vPrev = RingLds ? ringL[s0 * 64 + lane] : (s0 == lastIns ? lastNpp : (double)ringp[(uint32_t)s0 * ncu]);
         }
         // The rest of a step, written once and instantiated twice: the common case (nobody dies: no
@@ -240,6 +245,35 @@
         // member of the wavefront dies AFTER the loop, which that step leaves (the wavefront takes the
         // general step from then on) -- the loop body stays one straight run of code.  What the
         // tail needs from the step lives outside the loop for that.
+        // Carried (kCoopCarriedTile, step_coop.hip: c10k's instantiation alone): what a step needs of t's parity and of the ring
+        // slots is CARRIED from step to step as per-lane LDS byte addresses instead of being derived from t and the slot numbers
+        // -- a two-slot mailbox's address flips with one subtraction from the sum of both slots' addresses, a ring address
+        // advances by a slot's 512 bytes, the posted sequence number by one -- and re-seeded at the top of every regular tile.
+        // The ring's wrap is a wave-uniform test against the step on which it falls (wrapNext), corrected out of line.
+        [[maybe_unused]] unsigned cFac = 0, cLai = 0, cAlive = 0, cRead = 0, cIns = 0;   // mailFac[t & 1], mailLai / mailAlive[(t + 1) & 1], ringL[readSlot / insSlot]
+        [[maybe_unused]] unsigned sumFac = 0, sumLai = 0, sumAlive = 0, sumPsnLai = 0;
+        [[maybe_unused]] int cSeq = 0;                                                   // t + 1
+        [[maybe_unused]] int wrapRead = 0, wrapIns = 0, wrapNext = 0;                    // the steps that use the ring's last slot
+        [[maybe_unused]] uint64_t allLanes = 0;
+        if constexpr (Carried) {
+          cFac = ldsAddr(&mailFac[t & 1][0][lane]);
+          sumFac = ldsAddr(&mailFac[0][0][lane]) + ldsAddr(&mailFac[1][0][lane]);
+          cLai = ldsAddr(&mailLai[(t + 1) & 1][lane]);
+          sumLai = ldsAddr(&mailLai[0][lane]) + ldsAddr(&mailLai[1][lane]);
+          cAlive = ldsAddr(&mailAlive[(t + 1) & 1][lane]);
+          sumAlive = ldsAddr(&mailAlive[0][lane]) + ldsAddr(&mailAlive[1][lane]);
+          // mailPsn[t & 1] is the OTHER slot of the two (same stride as mailLai): this sum less cLai, on the day path only
+          static_assert(sizeof(mailPsn[0]) == sizeof(mailLai[0]), "mailPsn[t & 1] from mailLai[(t + 1) & 1]: the same slot stride");
+          sumPsnLai = ldsAddr(&mailPsn[1][lane]) + ldsAddr(&mailLai[0][lane]);
+          cSeq = t + 1;
+          asm volatile("" : "+v"(cSeq));   // (a vector register of its own: not t + 1 moved over every step)
+          cRead = ldsAddr(&ringL[readSlot * 64 + lane]);
+          cIns = ldsAddr(&ringL[insSlot * 64 + lane]);
+          wrapRead = t + (SIPNET_RING_SLOTS - 1 - readSlot);
+          wrapIns = t + (SIPNET_RING_SLOTS - 1 - insSlot);
+          wrapNext = wrapRead < wrapIns ? wrapRead : wrapIns;
+          allLanes = __builtin_amdgcn_ballot_w64(true);
+        }
         R photosynthesis = 0, rSoil = 0, rVeg = 0, rCoarseRoot = 0, rFineRoot = 0, rHet = 0;
         [[maybe_unused]] R methaneReg = 0;
         double soilGain = 0.0, litterGain = 0.0, ringNew = 0.0;
@@ -280,7 +314,8 @@
           const R tGpp = photosynthesis * len;
           const R tRa = ffma(rVeg, len, (rCoarseRoot + rFineRoot) * len);
           if (NCyc) postD(&mailPend[t & 1][0][lane], 0, (double)(tGpp - tRa));   // S forms NEE (it has R_h); before the verdict word
-          postAlive(&mailAlive[(t + 1) & 1][lane], t + 1, diedNow);
+          if constexpr (Carried) postAlive(ldsPtr<int>(cAlive), cSeq, diedNow);
+          else postAlive(&mailAlive[(t + 1) & 1][lane], t + 1, diedNow);
           if (!NCyc) {
             soilC += soilGain;
             if (Opt) litterC += litterGain;
@@ -307,7 +342,8 @@
           }
           vPrev = vNew;
           if (RingLds) {
-            ringL[insSlot * 64 + lane] = npp;
+            if constexpr (Carried) postRaw(ldsPtr<double>(cIns), npp);   // (like the posts around it: no wait of the compiler's in the step)
+            else ringL[insSlot * 64 + lane] = npp;
           } else {
             ringp[(uint32_t)insSlot * ncu] = (R)npp;   // (npp is an R-typed difference: nothing is lost)
             lastIns = insSlot;
@@ -329,8 +365,10 @@
           }
           if (__builtin_expect(stageOn, 0)) postRaw(&stage[0][(t - tBegin) & (2 * kStageR - 1)][lane], tNee);
         };
-        unsigned dayMask = ((unsigned)tileBits >> 16) >> (t - tileStart);
-        for (; t < tLast; t++, dayMask >>= 1) {
+        if constexpr (Carried) COOP_CARRIED_PAD(1);
+        // (Carried: the mask stays where it is, step t's bit at position t & 31 -- nothing to shift along from step to step)
+        unsigned dayMask = Carried ? ((unsigned)tileBits >> 16) << (tileStart & 16) : ((unsigned)tileBits >> 16) >> (t - tileStart);
+        for (; t < tLast; t++, dayMask >>= Carried ? 0 : 1) {
           // The carbon wave's arithmetic is written out with explicit fused multiply-adds and
           // compiled with contraction off (here and in the general step below): which of the two
           // paths a wavefront takes depends on its 63 neighbours, so they must not differ by what
@@ -354,12 +392,37 @@
                                g2, qSoilT, gFine, gCoarse, moistEff, mK, ringNew);
             else if (Opt)
               takeFactors7(&mailFac[t & 1][0][lane], seqFacMoist, t, g1, g2, qSoilT, gFine, gCoarse, moistEff, mK);
-            else if (RingLds)
+            else if (RingLds) {
+              if constexpr (Carried)
+                takeFactorsRing(ldsPtr<const R>(cFac), seqFacMoist, cRead, t, g1, g2, qSoilT, gFine, gCoarse, moistEff, ringNew);
+              else
               takeFactorsRing(&mailFac[t & 1][0][lane], seqFacMoist, ldsAddr(&ringL[readSlot * 64 + lane]), t, g1,
                               g2, qSoilT, gFine, gCoarse, moistEff, ringNew);
-            else
+            } else
               takeFactors(&mailFac[t & 1][0][lane], seqFacMoist, t, g1, g2, qSoilT, gFine, gCoarse, moistEff);
             WAIT_END(0)
+          }
+          // (Carried: each carried value is advanced once its last use of the step is behind it, in place -- the empty asm keeps
+          // the compiler from deriving anything from the old value -- and WHERE among the step's three stretches of straight code
+          // each one stands is what holds the loop heads at their measured offsets: tests/test_code_placement.py)
+          // (Carried) lai(t + 1) FIRST: waves L and W start on step t + 1 with it, and by night their answer (the factors of
+          // t + 1) and this wave's own step are nearly as long as each other -- left to the scheduler the post stood behind 36
+          // instructions of the other pools' arithmetic.  The leaf pool's share of the step is computed HERE, once -- its litter,
+          // its creation, the leaf part of checkNegativeCreation(), the pool of t + 1 -- then the post and a fence nothing is
+          // moved across; the statements below take these values where the other instantiations compute them in place.
+          [[maybe_unused]] R leafLitterFirst = 0, leafCreationFirst = 0, leafDeficitFirst = 0;
+          [[maybe_unused]] double leafNextFirst = 0.0;
+          if constexpr (Carried) {
+            cRead += 512;
+            asm volatile("" : "+v"(cRead));
+            const R leafNow = (R)plantLeafC;
+            leafLitterFirst = leafNow * K_ltr;
+            leafCreationFirst = (R)(ringSum * 0.2) * K_la;
+            leafDeficitFirst = rminv(ffma(leafNow, invLen, leafCreationFirst) - leafLitterFirst, R(0));
+            leafNextFirst = plantLeafC;
+            accum(leafNextFirst, (leafCreationFirst - leafDeficitFirst) - leafLitterFirst, len);
+            post(ldsPtr<R>(cLai), &seqLai, (R)rmax0(leafNextFirst) * K_invLcsw, cSeq);
+            __builtin_amdgcn_sched_barrier(0);
           }
           const R fSoil = NCyc ? R(0) : qSoilT * moistEff;
           rvN = 0;
@@ -370,7 +433,7 @@
               asm volatile("global_load_dword %0, %1, off" : "=&v"(rvN) : "v"(ringp + (uint32_t)readSlot * ncu) : "memory");
           }
           useLast = readSlot == lastIns;
-          const bool isDay = (dayMask & 1u) != 0;
+          const bool isDay = Carried ? (dayMask & (1u << (t & 31))) != 0 : (dayMask & 1u) != 0;
 
           const R eLeaf = (R)plantLeafC, eSoilC = (R)soilC;
           const R eCoarse = (R)coarseRootC, eFine = (R)fineRootC;
@@ -383,13 +446,13 @@
           rFineRoot = eFine * gFine;
           if (!Opt) rSoil = eSoilC * fSoil;
           const R woodLitter = totalWoodC * K_wtr;
-          const R leafLitter = eLeaf * K_ltr;
-          R leafCreation = meanNpp * K_la, woodCreation = meanNpp * K_wa;
+          const R leafLitter = Carried ? leafLitterFirst : eLeaf * K_ltr;
+          R leafCreation = Carried ? leafCreationFirst : meanNpp * K_la, woodCreation = meanNpp * K_wa;
           const R coarseRootLoss = K_crt * eCoarse, fineRootLoss = K_frt * eFine;
           R coarseRootCreation = K_ca * meanNpp, fineRootCreation = K_fa * meanNpp;
           {  // checkNegativeCreation(), limitations.c:146-182, as selects
             const R leafDeficit = ffma(eLeaf, invLen, leafCreation) - leafLitter;
-            const R ld = rminv(leafDeficit, R(0));
+            const R ld = Carried ? leafDeficitFirst : rminv(leafDeficit, R(0));
             woodCreation += ld;
             leafCreation -= ld;
             const R fineDef = ffma(eFine, invLen, fineRootCreation) - fineRootLoss;
@@ -402,8 +465,9 @@
           if (NCyc)   // the plants' side of the step for wave S, and checkNitrogenLimitation() (see the general step)
             plantSideN(t, len, invLen, minNStep, minNSeq, (double)moistEff, (double)h0.x, leafLitter, woodLitter, fineRootLoss,
                        coarseRootLoss, R(0), R(0), leafCreation, woodCreation, fineRootCreation, coarseRootCreation);
-          accum(plantLeafC, leafCreation - leafLitter, len);
-          post(&mailLai[(t + 1) & 1][lane], &seqLai, (R)rmax0(plantLeafC) * K_invLcsw, t + 1);
+          if constexpr (Carried) plantLeafC = leafNextFirst;   // (the pool of t + 1, as posted)
+          else accum(plantLeafC, leafCreation - leafLitter, len);
+          if constexpr (!Carried) post(&mailLai[(t + 1) & 1][lane], &seqLai, (R)rmax0(plantLeafC) * K_invLcsw, t + 1);   // (Carried: posted above)
           accum(plantWoodC, woodCreation - woodLitter, len);
           accum(coarseRootC, coarseRootCreation - coarseRootLoss, len);
           accum(fineRootC, fineRootCreation - fineRootLoss, len);
@@ -413,29 +477,67 @@
           else if (!NCyc) soilGain = (double)((coarseRootLoss + fineRootLoss + woodLitter + leafLitter - rSoil) * len);
           const R r_a = rVeg + rFineRoot + rCoarseRoot;
           const R alloc = leafCreation + woodCreation + fineRootCreation + coarseRootCreation;
-          rootsOk = (plantWoodC > kTiny) && (fineRootC + coarseRootC > kTiny);
+          // (Carried: the mortality test as lane masks straight from the compares -- one scalar test against the full wave)
+          [[maybe_unused]] uint64_t okMask = 0;
+          if constexpr (Carried)
+            okMask = __builtin_amdgcn_ballot_w64(plantWoodC > kTiny) & __builtin_amdgcn_ballot_w64(fineRootC + coarseRootC > kTiny);
+          else rootsOk = (plantWoodC > kTiny) && (fineRootC + coarseRootC > kTiny);
           photosynthesis = 0;
           if (__builtin_expect(isDay, 0)) {  // laid out for the night step: by night this wave is the critical one
             WAIT_BEGIN()
-            photosynthesis = take(&mailPsn[t & 1][lane], &seqPsn, t);
+            if constexpr (Carried) COOP_CARRIED_PAD(2);   // (day steps only: the carbon wave has slack then)
+            if constexpr (Carried) photosynthesis = take(ldsPtr<const R>(sumPsnLai - cLai), &seqPsn, t);
+            else photosynthesis = take(&mailPsn[t & 1][lane], &seqPsn, t);
             WAIT_END(1)
           }
           accum(delta, (photosynthesis - r_a) - alloc, len);
-          const bool dies = !(rootsOk && (plantWoodC + delta > kTiny));
+          if constexpr (Carried) {
+            okMask &= __builtin_amdgcn_ballot_w64(plantWoodC + delta > kTiny);
+            if (__builtin_expect(okMask != allLanes, 0)) {
+              dyingStep = true;
+              break;
+            }
+          }
+          const bool dies = !Carried && !(rootsOk && (plantWoodC + delta > kTiny));
           if (__builtin_expect(__builtin_amdgcn_ballot_w64(dies) != 0, 0)) {
             dyingStep = true;
             break;
           }
           finishStep(std::false_type{});
+          if constexpr (Carried) {
+            // (the 8-byte encoding: four bytes of padding in this stretch that no instruction slot pays for)
+            asm volatile("v_sub_u32_e64 %0, %1, %0" : "+v"(cFac) : "v"(sumFac));
+            cLai = sumLai - cLai;
+            asm volatile("" : "+v"(cLai));
+            if (__builtin_expect(t == wrapNext, 0)) {   // the next step uses slot 0
+              if (t == wrapRead) cRead -= SIPNET_RING_SLOTS * 512;
+              if (t == wrapIns) cIns -= SIPNET_RING_SLOTS * 512;
+              wrapNext = wrapRead > wrapIns ? wrapRead : wrapIns;
+            }
+            cSeq++;
+            cAlive = sumAlive - cAlive;
+            cIns += 512;
+            asm volatile("" : "+v"(cSeq), "+v"(cAlive), "+v"(cIns));
+          } else {
           readSlot = nextSlot(readSlot);
           insSlot = nextSlot(insSlot);
+          }
           MARK("C regular step end")
         }
+        // (Carried: both ways out of the loop meet HERE, at an opaque copy of the flag: with one exit block the compiler keeps
+        // fewer flag tests inside the loop than when it threads the dying exit into the divergent mortality code below)
+        if constexpr (Carried) {
+          int dying = uni((int)dyingStep);
+          asm volatile("" : "+s"(dying));
+          dyingStep = dying != 0;
+        }
         if (dyingStep) {  // finish that step with the mortality code; the general step from the next one on
+          if constexpr (Carried) rootsOk = (plantWoodC > kTiny) && (fineRootC + coarseRootC > kTiny);
           finishStep(std::true_type{});
           t++;
         }
         recB += (int)(t - tFirst) * (int)sizeof(FastRec);
+        if constexpr (Carried) COOP_CARRIED_PAD(3);
       }
     }
   for (; t < tLast; t++, recB += sizeof(FastRec)) {
@@ -540,6 +642,7 @@
       } WAIT_WHILE(uni(facSeq) < t || uni(moistSeq) < t, 27, t);
       WAIT_END(0)
     }
+    if constexpr (Carried) COOP_CARRIED_PAD(4);
     const R fSoil = qSoilT * moistEff;
     const double* rare = (const double*)(recB + 144);
     const int32_t* rareI = (const int32_t*)(recB + 184);
@@ -963,6 +1066,7 @@
       // see the regular-tile path); with one eviction w1 is 0 and its term an exact no-op
       if (__builtin_expect(ringClean && insSlot >= 0 && nOps <= 2, 1)) {
         const double v1 = RingLds ? ringL[evSlot1 * 64 + lane] : (useLast1 ? lastNpp : (double)rv1);
+        if constexpr (Carried) COOP_CARRIED_PAD(5);
         ringSum = ffma(-q7.y, v0, ringSum);
         ringSum = ffma(-rare[0], v1, ringSum);
         ringSum = ffma(npp, (double)len, ringSum);
@@ -1067,6 +1171,7 @@
 
   CSTAMP_STORE()
   WAIT_STORE(8)
+  if constexpr (Carried) COOP_CARRIED_PAD(6);
   if (a.statsPart) {  // every NEE store of the launch has reached L2 (see wave L's statistics)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("ds_write_b32 %0, %1" :: "v"(ldsAddr(&seqDone[0])), "v"(1) : "memory");

@@ -18,6 +18,7 @@
     // written out below
 #pragma clang fp contract(off)
     COOP_CODE_PHASE(2);
+    if constexpr (kCoopCarriedTile<R, PlainExp, RingLds, Full, NP, NCyc, Ext, Sums>) COOP_CARRIED_PAD(7);   // (see coopCarriedPad)
     // ---- L: potPsn() + calcLightEff(), sipnet.c:517-641 -------------------------------------
     const double leafCSpWt = PRM(leafCSpWt);
     const double convK = kCWeight * (1.0 / kTen9) * (leafCSpWt / PRM(cFracLeaf)) * kSecPerDay;

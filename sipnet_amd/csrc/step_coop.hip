@@ -151,6 +151,9 @@ __device__ __forceinline__ float take(const float* slot, const int* flag, int st
 typedef double d2_t __attribute__((ext_vector_type(2)));
 typedef int i4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned ldsAddr(const void* p) { return (unsigned)(size_t)p; }
+// (the way back, for the hand-over primitives below, which take pointers and use their low words alone)
+template <class T>
+__device__ __forceinline__ T* ldsPtr(unsigned addr) { return (T*)(size_t)addr; }
 // Q10 exponent (temperature / 10) x log2(Q10), rounded as a product of its own: the factor block runs
 // on the light wave in some layouts and on a wave of its own (uniform temperature operand) in
 // others, and the compiler must not fuse the product into exp2's range reduction in one of them only
@@ -578,6 +581,32 @@ __device__ constexpr int coopCodePhase(int role) {
   return (Full || f64) ? 3 : 4;                // LDS ring f64 8.51 -> 8.32, its full-state build 14.71 -> 14.21, f32 8.15 -> 8.08
 #endif
 }
+
+// The regular-tile step of the carbon wave with carried addresses (coop_wave_carbon.inc, `Carried`): the one-chunk LDS-ring
+// kernel of fp64 batches with the default physics -- c10k's, c2's and c2x16's launch -- and no other instantiation: the
+// coop wave sources are shared, and every other measured kernel's code (tests/test_code_placement.py) stays what it is.
+// (Not the bounded-wait build of the same instantiation either, step_coop_bounded.hip: a test-only kernel with other
+// poll loops, for which the pads below were not counted -- it keeps the step it had.)
+#ifdef SIPNET_COOP_BOUNDED
+constexpr bool kCoopBoundedBuild = true;
+#else
+constexpr bool kCoopBoundedBuild = false;
+#endif
+template <class R, bool PlainExp, bool RingLds, bool Full, int NP, bool NCyc, bool Ext, bool Sums>
+constexpr bool kCoopCarriedTile =
+    !kCoopBoundedBuild && sizeof(R) == 8 && PlainExp && RingLds && !Full && NP == 1 && !NCyc && !Ext && !Sums;
+// Its step is shorter than the one the code phases were swept for (coopCodePhase), and the kernel is ONE function: its register
+// allocation -- a spill reload here, a compiler-placed wait there -- moves with the carbon wave's code.  The loop heads
+// behind the edit are put back on their measured offsets (tests/golden/code_placement.json) with counted s_nop where they cost
+// nothing:  0 once per launch, in front of the tile loop   1 once per tile, in front of the step loop   2 on the day step, in
+// front of the photosynthesis poll   3 once per tile, behind the regular-tile block   4 / 5 in the general step (15 tiles of
+// c10k's 1 095), behind its take and in its ring update   6 once per launch, behind the tile loop   7 once per launch, at the
+// top of the light wave.  (An edit to this kernel's code in front of a head means counting the table again.)
+__device__ constexpr int coopCarriedPad(int where) {
+  constexpr int pad[8] = {1, 3, 2, 2, 1, 1, 4, 4};
+  return pad[where];
+}
+#define COOP_CARRIED_PAD(WHERE) asm volatile(".rept %0\n s_nop 0\n .endr" ::"n"(coopCarriedPad(WHERE)))
 
 // ---- coopBody by role (round 6) ------------------------------------------------------------------------------------------
 // coopBody is ONE function -- a wavefront takes one of its branches by its index in the workgroup -- but it is written in
