@@ -80,20 +80,21 @@ def per_site(x, n_sites):
     return None if x is None else np.full(n_sites, x)
 
 
-def snapshot(b):
-    return b.get_state(), b.get_params(), b.get_rings()
+def snapshot(b, rings=True):
+    """rings=False: a site of very many columns, whose rings would be gigabytes -- None stands for them"""
+    return b.get_state(), b.get_params(), b.get_rings() if rings else None
 
 
-def propose_and_compare(b, n_sites, params, gamma, jitter, half, seed, draw, streams=None, total=None, site_total=None):
+def propose_and_compare(b, n_sites, params, gamma, jitter, half, seed, draw, streams=None, total=None, site_total=None, rings=True):
     """one proposal against the reference from the state the batch holds -> (worst ratio, saved, moved, info, prm before)"""
-    st0, prm0, rings0 = snapshot(b)
+    st0, prm0, rings0 = snapshot(b, rings)
     ncol = st0.shape[0]
     info = torch.full((n_sites, 4), -9, dtype=torch.int32, device=DEV)
     saved = torch.full((len(params), ncol), np.nan, dtype=torch.float64, device=DEV)
     moved = torch.full((ncol,), -7, dtype=torch.int32, device=DEV)
     b.mcmc_propose(params, gamma, jitter, half=half, seed=seed, draw=draw, streams=streams, site_total=site_total, saved=saved,
                    moved=moved, info_out=info)
-    st1, prm1, rings1 = snapshot(b)
+    st1, prm1, rings1 = snapshot(b, rings)
     want_prm, want_saved, want_moved, want_info, tol, margin = mr.propose(
         st0, prm0, np.zeros(n_sites), n_sites, tuples(params), gamma, jitter, half, seed, draw, streams, total)
     assert margin.min() > 1.0, margin.min()          # no decision within the bound of its threshold: no member is excused
@@ -110,7 +111,8 @@ def propose_and_compare(b, n_sites, params, gamma, jitter, half, seed, draw, str
     # what must stay: state, rings and status; the rows neither listed nor derived; every column no proposal was made for
     # (the other half, the dead, the sites whose code is not 1)
     np.testing.assert_array_equal(bits(st1), bits(st0))
-    np.testing.assert_array_equal(bits(rings1), bits(rings0))
+    if rings:
+        np.testing.assert_array_equal(bits(rings1), bits(rings0))
     rows = [p.index for p in params]
     derived = ([rr.PSN_TMAX] if rr.PSN_TOPT in rows or rr.PSN_TMIN in rows else []) + (
         [rr.COARSE_ALLOC] if set(mr.ALLOC) & set(rows) else [])
@@ -123,15 +125,15 @@ def propose_and_compare(b, n_sites, params, gamma, jitter, half, seed, draw, str
     return worst, saved, moved, want_info, prm0
 
 
-def accept_and_compare(b, n_sites, params, saved, moved, logp_new, logp_cur, beta, seed, draw, prm_before, streams=None):
+def accept_and_compare(b, n_sites, params, saved, moved, logp_new, logp_cur, beta, seed, draw, prm_before, streams=None, rings=True):
     """the accept step against the reference -> (accepted mask, info); prm_before: the rows before the proposal"""
-    st0, prm0, rings0 = snapshot(b)
+    st0, prm0, rings0 = snapshot(b, rings)
     moved0, saved0 = moved.cpu().numpy(), saved.cpu().numpy()
     new_t = torch.tensor(logp_new, dtype=torch.float64, device=DEV)
     cur_t = torch.tensor(logp_cur, dtype=torch.float64, device=DEV)
     info = torch.full((n_sites, 4), -9, dtype=torch.int32, device=DEV)
     b.mcmc_accept(params, saved, moved, new_t, cur_t, beta, seed=seed, draw=draw, streams=streams, info_out=info)
-    st1, prm1, rings1 = snapshot(b)
+    st1, prm1, rings1 = snapshot(b, rings)
     want_prm, want_moved, want_cur, want_info, margin, acc = mr.accept(
         st0, prm0, np.zeros(n_sites), n_sites, tuples(params), saved0, moved0, logp_new, logp_cur, beta, seed, draw, streams)
     assert margin.min() > 1.0, margin.min()
@@ -145,7 +147,8 @@ def accept_and_compare(b, n_sites, params, saved, moved, logp_new, logp_cur, bet
     np.testing.assert_array_equal(bits(prm1[rejected]), bits(prm_before[rejected]))      # all 80 rows as before the proposal
     np.testing.assert_array_equal(bits(prm1[~rejected]), bits(prm0[~rejected]))          # accepted, or not handled: as they were
     np.testing.assert_array_equal(bits(st1), bits(st0))
-    np.testing.assert_array_equal(bits(rings1), bits(rings0))
+    if rings:
+        np.testing.assert_array_equal(bits(rings1), bits(rings0))
     return acc, want_info
 
 
