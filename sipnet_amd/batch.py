@@ -592,8 +592,7 @@ class Batch:
         delta_max = self._upload(what, delta_max, self.n_sites, "delta_max")
         if ess_target is None:
             raise ValueError(f"{what}: ess_target needs {self.n_sites} values")
-        if info_out is not None and (not t.is_tensor(info_out) or not _dense(info_out, t.int32, TEMPER_INFO_WORDS * self.n_sites)):
-            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x {TEMPER_INFO_WORDS}")
+        self._info_out(what, info_out, TEMPER_INFO_WORDS)
         delta, delta_hi, ess = (t.zeros(self.n_sites, dtype=t.float64, device=self.device) for _ in range(3))
         check(self.L.sipnet_batch_pf_temper_sites(self.h, ptr(loglik), ptr(base), ptr(delta_max), ptr(ess_target), ptr(delta),
                                                   ptr(delta_hi), ptr(ess), ptr(out), ptr(info_out), self._stream()), what)
@@ -612,36 +611,38 @@ class Batch:
         touched (None: every site); info_out: int32 device tensor [n_sites][4] for {code, rows + slots perturbed, live
         members, members kept} (no host synchronisation); without it the call checks shrink and pool_sd first and raises
         before anything is written."""
-        t = self._torch
         what = "pf_rejuvenate"
         prm = list(params)
         mask = pool_mask(pools) if pools else 0
         shrink = self._upload(what, shrink, self.n_sites, "shrink")
         pool_sd = self._upload(what, pool_sd, self.n_sites * 13, "pool_sd")
-        if streams is not None:
-            streams = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
-            if streams.size != self.n_sites:
-                raise ValueError(f"{what}: streams needs {self.n_sites} values, got {streams.size}")
-            streams = t.from_numpy(streams.view(np.int32)).to(self.device)
-        if site_total is not None and not _dense(site_total, t.int64, self.n_sites):
-            raise ValueError(f"{what}: site_total must be a contiguous int64 device tensor of {self.n_sites} values")
-        if info_out is not None and not _dense(info_out, t.int32, REJUVENATE_INFO_WORDS * self.n_sites):
-            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x {REJUVENATE_INFO_WORDS}")
+        streams = self._streams(what, streams)
+        self._site_total(what, site_total)
+        self._info_out(what, info_out, REJUVENATE_INFO_WORDS)
         check(self.L.sipnet_batch_pf_rejuvenate(self.h, len(prm), c_array(EnkfParam, prm), ptr(shrink), mask, ptr(pool_sd),
                                                 int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff, ptr(streams), ptr(site_total),
                                                 ptr(info_out), self._stream()), what)
 
-    def _mcmc_common(self, what, streams, info_out):
-        """the uint32 streams on the device (None stays None); info_out checked"""
+    def _streams(self, what, streams):
+        """the sites' uint32 random streams on the device (None stays None)"""
+        if streams is None:
+            return None
+        streams = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
+        if streams.size != self.n_sites:
+            raise ValueError(f"{what}: streams needs {self.n_sites} values, got {streams.size}")
+        return self._torch.from_numpy(streams.view(np.int32)).to(self.device)
+
+    def _info_out(self, what, info_out, words):
+        """info_out (None: the synchronous form) checked: `words` int32 per site"""
         t = self._torch
-        if streams is not None:
-            streams = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
-            if streams.size != self.n_sites:
-                raise ValueError(f"{what}: streams needs {self.n_sites} values, got {streams.size}")
-            streams = t.from_numpy(streams.view(np.int32)).to(self.device)
-        if info_out is not None and not _dense(info_out, t.int32, MCMC_INFO_WORDS * self.n_sites):
-            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x {MCMC_INFO_WORDS}")
-        return streams
+        if info_out is not None and (not t.is_tensor(info_out) or not _dense(info_out, t.int32, words * self.n_sites)):
+            raise ValueError(f"{what}: info_out must be a contiguous int32 device tensor of n_sites x {words}")
+
+    def _site_total(self, what, site_total):
+        """site_total (None: every site) checked: pf_resample_sites' total_out"""
+        t = self._torch
+        if site_total is not None and (not t.is_tensor(site_total) or not _dense(site_total, t.int64, self.n_sites)):
+            raise ValueError(f"{what}: site_total must be a contiguous int64 device tensor of {self.n_sites} values")
 
     def mcmc_propose(self, params, gamma, jitter=None, half=0, seed=0, draw=0, streams=None, site_total=None, saved=None,
                      moved=None, info_out=None):
@@ -661,9 +662,9 @@ class Batch:
         jitter = self._upload(what, jitter, self.n_sites, "jitter")
         if gamma is None:
             raise ValueError(f"{what}: gamma needs {self.n_sites} values")
-        streams = self._mcmc_common(what, streams, info_out)
-        if site_total is not None and not _dense(site_total, t.int64, self.n_sites):
-            raise ValueError(f"{what}: site_total must be a contiguous int64 device tensor of {self.n_sites} values")
+        streams = self._streams(what, streams)
+        self._info_out(what, info_out, MCMC_INFO_WORDS)
+        self._site_total(what, site_total)
         if saved is None:
             saved = t.zeros((max(len(prm), 1), self.ncol), dtype=t.float64, device=self.device)
         if moved is None:
@@ -685,7 +686,8 @@ class Batch:
         what = "mcmc_accept"
         prm = list(params)
         beta = self._upload(what, beta, self.n_sites, "beta")
-        streams = self._mcmc_common(what, streams, info_out)
+        streams = self._streams(what, streams)
+        self._info_out(what, info_out, MCMC_INFO_WORDS)
         for x, dtype, n, name in ((saved, t.float64, max(len(prm), 1) * self.ncol, "saved"), (moved, t.int32, self.ncol, "moved"),
                                   (logp_new, t.float64, self.ncol, "logp_new"), (logp_cur, t.float64, self.ncol, "logp_cur")):
             if not t.is_tensor(x) or not _dense(x, dtype, n):

@@ -54,9 +54,7 @@ struct JointArgs : EnkfArgs {
   DerivedRows rows;                        // where leafAllocation .. psnTMin are among the analysed parameters
 };
 
-__device__ __forceinline__ bool liveAt(const EnkfArgs& a, int s, int64_t j) {
-  return j < a.M && a.siteStatus[s] == 0 && a.state[(int64_t)ST_status * a.ncol + (int64_t)s * a.M + j] == 0.0;
-}
+__device__ __forceinline__ bool liveAt(const EnkfArgs& a, int s, int64_t j) { return liveIn(a, s, j); }
 
 // the site's inputs: kBadInput, kNoObs, or kAnalysed (before the live count); *used = observations that are not NaN
 __host__ __device__ inline int siteInputs(const double* obs, const double* sd, const double* infl, int nObs, int s, int* used) {

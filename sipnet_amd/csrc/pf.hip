@@ -14,17 +14,18 @@
 //
 // This file is the one translation unit (the one tools/build_variants.py compiles with -DSIPNET_PF_*) and the host side; the
 // device code is in parts, each with its own header comment, included below in this order: site_device.h (the sums in their
-// one order, a member's limits and derived rows, shared with enkf.hip), pf_gather.inc, pf_weights.inc, pf_fused.inc,
-// pf_plan.inc, pf_sites.inc, pf_series.inc, pf_rejuvenate.inc, pf_metropolis.inc, pf_temper.inc.  Refusals, the bookkeeping of a call that writes the batch, the
-// scratch blocks' growth and the synchronous forms' copies are site_host.h's.
+// one order, a member's limits, the listed and derived rows, shared with enkf.hip), pf_gather.inc, pf_weights.inc,
+// pf_fused.inc, pf_plan.inc, pf_sites.inc, pf_series.inc, pf_random.inc, pf_rejuvenate.inc, pf_metropolis.inc, pf_temper.inc.
+// Refusals, the bookkeeping of a call that writes the batch, the scratch blocks' growth and carving and the synchronous forms'
+// copies are site_host.h's.
 //
 // The host side runs three filters.  One batch (sipnet_batch_pf_analysis): takePfPre, the one launch (fusedSetup) or the
 // launches of their own, checkTotal, the resampling gather (resampleColumns).  Many sites (sipnet_batch_pf_analysis_sites, and
 // sipnet_batch_pf_resample_sites from given log-weights): sitesBegin, the weights' source, sitesFinish.  Across ranks by peer
 // reads: sipnet_batch_pf_publish, _connect (mapPeer, fillBank) and _resample_peers (peerTable, peerAncestors, peerGather).
-// Beside them the series weights (sipnet_batch_series_loglik), the rejuvenation (sipnet_batch_pf_rejuvenate) and the Metropolis
-// move over members (sipnet_batch_mcmc_propose, sipnet_batch_mcmc_accept) and the tempering exponent that keeps an effective
-// sample size (sipnet_batch_pf_temper_sites).
+// Beside them the series weights (sipnet_batch_series_loglik) and, their host side in pf_moves.inc (included behind it), the
+// rejuvenation (sipnet_batch_pf_rejuvenate), the Metropolis move over members (sipnet_batch_mcmc_propose, sipnet_batch_mcmc_accept)
+// and the tempering exponent that keeps an effective sample size (sipnet_batch_pf_temper_sites).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -52,6 +53,7 @@ namespace {
 #include "pf_plan.inc"
 #include "pf_sites.inc"
 #include "pf_series.inc"
+#include "pf_random.inc"
 #include "pf_rejuvenate.inc"
 #include "pf_metropolis.inc"
 #include "pf_temper.inc"
@@ -663,10 +665,17 @@ int sipnet_batch_pf_analysis(sipnet_batch* b, const void* d_plane, int32_t elem_
   return sipnet_batch_resample(b, d_ancestors, nullptr, 0, nullptr, with_params, hip_stream);
 }
 
-// scratch of the many-site analysis: the sites' totals, and for the split path the chunks' maxima, sums and threads' sums
-// (and, behind them, the chunks' sums of squares that given weights' effective sample size needs)
-static int sitesScratchFor(sipnet_batch* b, PfScratch& sc, int64_t nSites, int64_t nChunks) {
-  return growScratch(b, sc.d_sites, (size_t)(nSites + nChunks * (2 + 256 + 2)) * sizeof(int64_t));
+// scratch of the many-site analysis carved into sa: the sites' totals, and for the split path the chunks' maxima, sums and
+// threads' sums and the chunks' sums of squares that given weights' effective sample size needs
+static int sitesScratchFor(sipnet_batch* b, PfScratch& sc, SitesArgs& sa, bool split) {
+  const size_t nSites = (size_t)b->n_sites, nCk = split ? nSites * (size_t)sa.nChunks : 0;
+  return carveScratch(b, sc.d_sites, [&](Carver& c) {
+    sa.total = c.take<int64_t>(nSites);
+    sa.chunkMax = c.take<double>(nCk);
+    sa.chunkSum = c.take<int64_t>(nCk);
+    sa.threadIncl = c.take<int64_t>(nCk * 256);
+    sa.chunkSq = c.take<int64_t>(2 * nCk);
+  });
 }
 
 // the many-site analysis on the device: one workgroup per site in one launch, or (split) chunks of sa.chunk columns in three
@@ -679,10 +688,6 @@ static void sitesLaunch(SitesArgs& sa, PfScratch& sc, int64_t nSites, bool split
     else hipLaunchKernelGGL(pfSitesKernel<double>, sites, dim3(256), 0, stream, sa);
     return;
   }
-  sa.chunkMax = (double*)(sa.total + nSites);
-  sa.chunkSum = sa.total + nSites + nSites * sa.nChunks;
-  sa.threadIncl = sa.chunkSum + nSites * sa.nChunks;
-  sa.chunkSq = sa.threadIncl + nSites * sa.nChunks * 256;
   if (!sa.w) sa.w = sc.d_w;
   const dim3 chunks((unsigned)nSites, (unsigned)sa.nChunks);
   const dim3 tiles((unsigned)nSites, (unsigned)((sa.M + 255) / 256));
@@ -735,16 +740,15 @@ static int sitesBegin(const char* who, sipnet_batch* b, const double* d_u0, doub
   RC_TRY(pfScratchFor(sc, b->ncol, stream));
   int chunk, nChunks;
   *split = sitesGeometry(b, &chunk, &nChunks);
-  RC_TRY(sitesScratchFor(b, sc, b->n_sites, *split ? (int64_t)b->n_sites * nChunks : 0));
   sa = SitesArgs{};
   sa.M = b->n_members;
   sa.nChunks = nChunks;
   sa.chunk = chunk;
+  RC_TRY(sitesScratchFor(b, sc, sa, *split));
   sa.u0 = d_u0;
   sa.logw = d_logw;
   sa.w = d_fixed_weights;
   sa.anc = d_ancestors;
-  sa.total = (int64_t*)sc.d_sites.get();
   sa.totalOut = d_site_total;
   return SIPNET_OK;
 }
@@ -896,360 +900,9 @@ int sipnet_batch_series_loglik(sipnet_batch* b, int32_t n_terms, const sipnet_lo
   return SIPNET_OK;
 }
 
-// ---- rejuvenation ----------------------------------------------------------------------------------------------------
-void sipnet_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
-  philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out);
-}
-
-void sipnet_rejuvenate_normals(uint64_t seed, uint32_t draw, uint32_t stream, uint32_t member, uint32_t block, double z[4]) {
-  rejNormals((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, stream, member, block, true, z);
-}
-
-static int rejRefuse(const std::string& why) { return refuse("sipnet_batch_pf_rejuvenate", why); }
-// the synchronous form's check: shrink, pool_sd and the totals read back, the first selected site with bad input named
-static int rejCheck(const sipnet_batch* b, const RejArgs& a, hipStream_t stream) {
-  const size_t nSites = (size_t)b->n_sites;
-  std::vector<double> shrink, sd;
-  std::vector<int64_t> total;
-  RC_TRY(readBack(shrink, a.nPrm > 0 ? a.shrink : nullptr, nSites, stream));
-  RC_TRY(readBack(sd, a.mask ? a.poolSd : nullptr, nSites * kRejPools, stream));
-  RC_TRY(readBack(total, a.siteTotal, nSites, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  for (size_t s = 0; s < nSites; s++)
-    if (rejSiteInputs(shrink.data(), sd.data(), a.siteTotal ? total.data() : nullptr, a.nPrm, a.mask, (int64_t)s) == kRejBadInput)
-      return rejRefuse("site " + std::to_string(s) + ": bad input (the shrink factor must lie in (0, 1]; a masked pool sd must be "
-                       "finite and >= 0); nothing was written");
-  return SIPNET_OK;
-}
-// the batch's scratch block carved: the split path's chunk sums and site statistics, the info (a.info is d_site_info where
-// given), the split path's counts and codes
-static int rejScratch(sipnet_batch* b, PfScratch& sc, RejArgs& a, int32_t* d_site_info, bool split) {
-  const size_t nSites = (size_t)b->n_sites, nCnt = split ? nSites * (size_t)a.nCh : 0;
-  const size_t nPart = nCnt * kRejPrm, nStat = split ? nSites * 2 * kRejPrm : 0;
-  const size_t nInt = nSites * 4 + 2 * nCnt + (split ? 2 * nSites : 0);
-  const size_t bytes = (nPart + nStat) * sizeof(double) + nInt * sizeof(int32_t);
-  RC_TRY(growScratch(b, sc.d_rejuv, bytes));
-  a.part = (double*)sc.d_rejuv.get();
-  a.stat = a.part + nPart;
-  int32_t* ints = (int32_t*)(a.stat + nStat);
-  a.info = d_site_info ? d_site_info : ints;
-  a.cnt = ints + nSites * 4;
-  a.kept = a.cnt + nCnt;
-  a.site = a.kept + nCnt;
-  return SIPNET_OK;
-}
-
-int sipnet_batch_pf_rejuvenate(sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, const double* d_shrink,
-                               int32_t pool_mask, const double* d_pool_sd, uint64_t seed, uint32_t draw,
-                               const uint32_t* d_stream, const int64_t* d_site_total, int32_t* d_site_info, void* hip_stream) {
-  RejArgs a{};
-  if (sipnet_enkf_params_check(n_params, params, a.lo, a.hi) != SIPNET_OK) {   // (the joint analysis's rows and bounds)
-    const std::string why = sipnet_last_error(), from = "sipnet_enkf_params_check: ";
-    return rejRefuse(why.compare(0, from.size(), from) == 0 ? why.substr(from.size()) : why);
-  }
-  if (n_params > 0 && !d_shrink) return rejRefuse("n_params > 0 needs d_shrink");
-  if (pool_mask & ~((1 << kRejPools) - 1)) return rejRefuse("pool_mask must name pools 0..12");
-  if (pool_mask && !d_pool_sd) return rejRefuse("a pool_mask needs d_pool_sd");
-  if (n_params == 0 && pool_mask == 0) return rejRefuse("nothing to do (n_params == 0 and pool_mask == 0)");
-  if (!b) return rejRefuse("a NULL batch");
-  if (tooManyColumns(b)) return rejRefuse("at most 4194304 columns");
-  if (b->planDirty) return rejRefuse("needs a batch that was set up (sipnet_batch_setup): the members' status is read");
-  if (b->pfPeers) return rejRefuse("this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
-  int rc = useDevice(b);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const int64_t M = b->n_members, nSites = b->n_sites;
-  a.nPrm = n_params;
-  a.mask = pool_mask;
-  a.rows = derivedRowsOf(n_params, params, a.prmRow);
-  a.shrink = d_shrink;
-  a.poolSd = d_pool_sd;
-  a.key0 = (uint32_t)(seed & 0xffffffffu);
-  a.key1 = (uint32_t)(seed >> 32);
-  a.draw = draw;
-  a.stream = d_stream;
-  a.siteTotal = d_site_total;
-  a.ncol = b->ncol;
-  a.M = M;
-  a.nCh = (int32_t)((M + 255) / 256);
-  if (!d_site_info) {
-    rc = rejCheck(b, a, stream);
-    if (rc) return rc;
-  }
-  rc = beginWrite(b, stream, /*ownRows=*/n_params > 0);   // (every column its own rows: the move writes them)
-  if (rc) return rc;
-  a.state = b->d_state;
-  a.prm = b->d_prm;
-  a.siteStatus = b->d_siteStatus;
-  // one workgroup per site when the sites are one chunk each, else the per-chunk launches (pf_rejuvenate.inc says why)
-  const bool split = a.nCh > 1 || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
-  rc = rejScratch(b, scratchOf(b), a, d_site_info, split);
-  if (rc) return rc;
-  const dim3 sites((unsigned)nSites), chunks((unsigned)nSites, (unsigned)a.nCh);
-  if (!split) {
-    hipLaunchKernelGGL(rejGroupKernel, sites, dim3(256), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(rejChunkKernel, chunks, dim3(256), 0, stream, a, 0);
-    hipLaunchKernelGGL(rejSiteKernel, sites, dim3(256), 0, stream, a, 0);
-    if (n_params > 0) {
-      hipLaunchKernelGGL(rejChunkKernel, chunks, dim3(256), 0, stream, a, 1);
-      hipLaunchKernelGGL(rejSiteKernel, sites, dim3(256), 0, stream, a, 1);
-    }
-    hipLaunchKernelGGL(rejApplyKernel, chunks, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(rejInfoKernel, sites, dim3(256), 0, stream, a);
-  }
-  HIP_TRY(hipGetLastError());
-  reportPath(b, !split, split ? 0 : (int32_t)nSites);
-  return markBusy(b, stream);
-}
-
-// ---- the Metropolis move over members ------------------------------------------------------------------------------------
-int sipnet_mcmc_draws(uint64_t seed, uint32_t draw, uint32_t stream, uint32_t member, int32_t n_other, int32_t idx[2], double* u) {
-  if (n_other < 2 || !idx || !u) return refuse("sipnet_mcmc_draws", "n_other must be at least 2; idx and u must not be NULL");
-  uint32_t x2;
-  mcDraws((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), draw, stream, member, (uint32_t)n_other, &idx[0], &idx[1], &x2);
-  *u = ((double)x2 + 0.5) * 0x1p-32;
-  return SIPNET_OK;
-}
-
-// What both calls of the move refuse before any launch, in this order: the listed rows (the joint analysis's checks; the
-// bounds converted into a), the half, a NULL required array (named by `missing`), then the batch.
-static int mcBegin(const char* who, sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, int32_t half,
-                   const char* missing, McArgs& a) {
-  if (n_params < 1 || n_params > kRejPrm) return refuse(who, "n_params must be 1.." + std::to_string(kRejPrm));
-  if (sipnet_enkf_params_check(n_params, params, a.lo, a.hi) != SIPNET_OK) {   // (the joint analysis's rows and bounds)
-    const std::string why = sipnet_last_error(), from = "sipnet_enkf_params_check: ";
-    return refuse(who, why.compare(0, from.size(), from) == 0 ? why.substr(from.size()) : why);
-  }
-  if (half != 0 && half != 1) return refuse(who, "half must be 0 or 1");
-  if (missing) return refuse(who, std::string("a NULL ") + missing);
-  if (!b) return refuse(who, "a NULL batch");
-  if (tooManyColumns(b)) return refuse(who, "at most 4194304 columns");
-  if (b->planDirty) return refuse(who, "needs a batch that was set up (sipnet_batch_setup): the members' status is read");
-  if (b->pfPeers) return refuse(who, "this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
-  a.nPrm = n_params;
-  a.half = half;
-  a.rows = derivedRowsOf(n_params, params, a.prmRow);
-  a.ncol = b->ncol;
-  a.M = b->n_members;
-  a.nCh = (int32_t)((b->n_members + 255) / 256);
-  return SIPNET_OK;
-}
-// the batch's scratch block carved: the chunks' masks, the fallback info (a.info is d_site_info where given), the chunks'
-// counts and the sites' codes
-static int mcScratch(sipnet_batch* b, McArgs& a, int32_t* d_site_info) {
-  PfScratch& sc = scratchOf(b);
-  const size_t nSites = (size_t)b->n_sites, nCnt = nSites * (size_t)a.nCh;
-  const size_t bytes = 4 * nCnt * sizeof(uint64_t) + (4 * nSites + 5 * nCnt + 3 * nSites) * sizeof(int32_t);
-  RC_TRY(growScratch(b, sc.d_mcmc, bytes));
-  a.masks = (uint64_t*)sc.d_mcmc.get();
-  int32_t* ints = (int32_t*)(a.masks + 4 * nCnt);
-  a.info = d_site_info ? d_site_info : ints;
-  a.cntB = ints + 4 * nSites;
-  a.off = a.cntB + nCnt;
-  a.cntA = a.off + nCnt;
-  a.made = a.cntA + nCnt;
-  a.taken = a.made + nCnt;
-  a.site = a.taken + nCnt;
-  return SIPNET_OK;
-}
-static void mcKey(McArgs& a, uint64_t seed, uint32_t draw, const uint32_t* d_stream) {
-  a.key0 = (uint32_t)(seed & 0xffffffffu);
-  a.key1 = (uint32_t)(seed >> 32);
-  a.draw = draw;
-  a.stream = d_stream;
-}
-
-int sipnet_batch_mcmc_propose(sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, const double* d_gamma,
-                              const double* d_jitter, int32_t half, uint64_t seed, uint32_t draw, const uint32_t* d_stream,
-                              const int64_t* d_site_total, double* d_saved, int32_t* d_moved, int32_t* d_site_info,
-                              void* hip_stream) {
-  const char* who = "sipnet_batch_mcmc_propose";
-  McArgs a{};
-  int rc = mcBegin(who, b, n_params, params, half, !d_gamma ? "d_gamma" : !d_saved ? "d_saved" : !d_moved ? "d_moved" : nullptr, a);
-  if (rc) return rc;
-  rc = useDevice(b);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const int64_t nSites = b->n_sites;
-  a.gamma = d_gamma;
-  a.jitter = d_jitter;
-  a.siteTotal = d_site_total;
-  a.saved = d_saved;
-  a.moved = d_moved;
-  mcKey(a, seed, draw, d_stream);
-  if (!d_site_info) {   // the synchronous form's check: gamma, jitter and the totals read back, the first bad selected site named
-    std::vector<double> gamma, jitter;
-    std::vector<int64_t> total;
-    RC_TRY(readBack(gamma, d_gamma, (size_t)nSites, stream));
-    RC_TRY(readBack(jitter, d_jitter, (size_t)nSites, stream));
-    RC_TRY(readBack(total, d_site_total, (size_t)nSites, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    for (int64_t s = 0; s < nSites; s++)
-      if (mcProposeInputs(gamma.data(), d_jitter ? jitter.data() : nullptr, d_site_total ? total.data() : nullptr, s) == kMcBadInput)
-        return refuse(who, "site " + std::to_string(s) + ": bad input (gamma must be finite; a jitter must be finite and >= 0); nothing was written");
-  }
-  rc = beginWrite(b, stream, /*ownRows=*/true);   // (every column its own rows: the move writes them)
-  if (rc) return rc;
-  a.state = b->d_state;
-  a.prm = b->d_prm;
-  a.siteStatus = b->d_siteStatus;
-  rc = mcScratch(b, a, d_site_info);
-  if (rc) return rc;
-  // one workgroup per site when the sites are one chunk each, else the per-chunk launches (pf_metropolis.inc)
-  const bool split = a.nCh > 1 || (b->kernelOptions & SIPNET_KOPT_PF_MULTI_LAUNCH);
-  const dim3 sites((unsigned)nSites), chunks((unsigned)nSites, (unsigned)a.nCh);
-  if (!split) {
-    hipLaunchKernelGGL(mcGroupKernel, sites, dim3(256), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(mcMaskKernel, chunks, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(mcSiteKernel, sites, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(mcProposeKernel, chunks, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(mcInfoKernel, sites, dim3(256), 0, stream, a);
-  }
-  HIP_TRY(hipGetLastError());
-  reportPath(b, !split, split ? 0 : (int32_t)nSites);
-  return markBusy(b, stream);
-}
-
-int sipnet_batch_mcmc_accept(sipnet_batch* b, int32_t n_params, const sipnet_enkf_param* params, const double* d_saved,
-                             int32_t* d_moved, const double* d_logp_new, double* d_logp_cur, const double* d_beta, uint64_t seed,
-                             uint32_t draw, const uint32_t* d_stream, int32_t* d_site_info, void* hip_stream) {
-  const char* who = "sipnet_batch_mcmc_accept";
-  McArgs a{};
-  int rc = mcBegin(who, b, n_params, params, 0,
-                   !d_saved ? "d_saved" : !d_moved ? "d_moved" : !d_logp_new ? "d_logp_new" : !d_logp_cur ? "d_logp_cur" : nullptr, a);
-  if (rc) return rc;
-  rc = useDevice(b);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const int64_t nSites = b->n_sites;
-  a.beta = d_beta;
-  a.saved = const_cast<double*>(d_saved);
-  a.moved = d_moved;
-  a.logpNew = d_logp_new;
-  a.logpCur = d_logp_cur;
-  mcKey(a, seed, draw, d_stream);
-  if (!d_site_info && d_beta) {   // the synchronous form's check: beta read back, the first bad site named
-    std::vector<double> beta;
-    RC_TRY(readBack(beta, d_beta, (size_t)nSites, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    for (int64_t s = 0; s < nSites; s++)
-      if (mcAcceptInputs(beta.data(), s) == kMcBadInput)
-        return refuse(who, "site " + std::to_string(s) + ": bad input (beta must be finite and > 0); nothing was written");
-  }
-  rc = beginWrite(b, stream, /*ownRows=*/true);
-  if (rc) return rc;
-  a.state = b->d_state;
-  a.prm = b->d_prm;
-  a.siteStatus = b->d_siteStatus;
-  rc = mcScratch(b, a, d_site_info);
-  if (rc) return rc;
-  const bool direct = a.nCh == 1;   // (a site of one chunk writes its info itself; the counts of more chunks meet in a launch of their own)
-  hipLaunchKernelGGL(mcAcceptKernel, dim3((unsigned)nSites, (unsigned)a.nCh), dim3(256), 0, stream, a, direct ? 1 : 0);
-  if (!direct) hipLaunchKernelGGL(mcAcceptInfoKernel, dim3((unsigned)nSites), dim3(256), 0, stream, a);
-  HIP_TRY(hipGetLastError());
-  reportPath(b, direct, direct ? (int32_t)nSites : 0);
-  return markBusy(b, stream);
-}
-
-// ---- the tempering exponent of every site --------------------------------------------------------------------------------
-// the synchronous form's check: the arguments read back, the first site with bad input named
-static int temperCheck(const char* who, const sipnet_batch* b, const TemperArgs& a, hipStream_t stream) {
-  const size_t nSites = (size_t)b->n_sites, M = (size_t)b->n_members;
-  std::vector<double> loglik, base, dmax, target;
-  RC_TRY(readBack(loglik, a.loglik, (size_t)b->ncol, stream));
-  RC_TRY(readBack(base, a.base, (size_t)b->ncol, stream));
-  RC_TRY(readBack(dmax, a.deltaMax, nSites, stream));
-  RC_TRY(readBack(target, a.essTarget, nSites, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  for (size_t s = 0; s < nSites; s++) {
-    const double dm = a.deltaMax ? dmax[s] : 1.0;
-    bool ok = dm > 0.0 && std::isfinite(dm) && target[s] > 0.0;
-    for (size_t c = s * M; ok && c < (s + 1) * M; c++)
-      ok = loglik[c] != INFINITY && (!a.base || base[c] != INFINITY);
-    if (!ok)
-      return refuse(who, "site " + std::to_string(s) + ": bad input (delta_max must be finite and > 0, the target > 0, no +inf among "
-                         "loglik or base); nothing was written");
-  }
-  return SIPNET_OK;
-}
-// the per-chunk path's scratch carved: the states of the stages, the chunks' maxima, partial sums, candidate maxima and counts
-static int temperScratch(sipnet_batch* b, TemperArgs& a) {
-  PfScratch& sc = scratchOf(b);
-  const size_t nSites = (size_t)b->n_sites, nCk = nSites * (size_t)a.nChunks;
-  const size_t nState = (size_t)(SIPNET_TEMPER_ROUNDS + 1) * nSites, nCand = a.base ? nCk * kTemperCand : 0;
-  const size_t bytes = nState * sizeof(TemperState) + (2 * nCk + nCand) * sizeof(double) + 2 * nCk * kTemperWords * sizeof(long long) +
-                       nCk * sizeof(int32_t);
-  RC_TRY(growScratch(b, sc.d_temper, bytes));
-  a.state = (TemperState*)sc.d_temper.get();
-  a.chunkMax = (double*)(a.state + nState);
-  a.candMax = a.chunkMax + 2 * nCk;
-  a.partial = (long long*)(a.candMax + nCand);
-  a.chunkCnt = (int32_t*)(a.partial + 2 * nCk * kTemperWords);
-  return SIPNET_OK;
-}
-extern "C++" {
-template <bool Base>
-static int temperLaunch(sipnet_batch* b, TemperArgs& a, bool split, hipStream_t stream) {
-  const dim3 sites((unsigned)b->n_sites), chunks((unsigned)b->n_sites, (unsigned)a.nChunks);
-  // One workgroup per site only without carried log-weights.  With them that kernel (15 maxima and 45 sums per thread in
-  // registers, both arrays in LDS) reported an ESS(delta) that the filter did not reproduce at a few sites in a hundred, about
-  // 1e-9 off, while the per-chunk launches did at every one; the cause is not found, so d_base takes the launches that are right.
-  if (!split && !Base) {   // the site's loglik in LDS: past 48 KB a kernel has to ask
-    const size_t ldsBytes = (size_t)a.M * sizeof(double);
-    bool ok = false;
-    RC_TRY(ldsGranted((const void*)temperGroupKernel, ldsBytes, b->device, &ok));
-    if (ok) {
-      hipLaunchKernelGGL(temperGroupKernel, sites, dim3(256), ldsBytes, stream, a);
-      HIP_TRY(hipGetLastError());
-      reportPath(b, true, (int32_t)b->n_sites);
-      return SIPNET_OK;
-    }
-  }
-  RC_TRY(temperScratch(b, a));
-  hipLaunchKernelGGL(temperChunkMaxKernel<Base>, chunks, dim3(256), 0, stream, a);
-  for (int stage = 0; stage <= SIPNET_TEMPER_ROUNDS; stage++) {
-    if (Base) hipLaunchKernelGGL(temperChunkKernel<Base>, chunks, dim3(256), 0, stream, a, stage, 0);
-    hipLaunchKernelGGL(temperChunkKernel<Base>, chunks, dim3(256), 0, stream, a, stage, 1);
-  }
-  hipLaunchKernelGGL(temperTailKernel<Base>, chunks, dim3(256), 0, stream, a);
-  HIP_TRY(hipGetLastError());
-  reportPath(b, false, 0);
-  return SIPNET_OK;
-}
-}  // extern "C++"
-
-int sipnet_batch_pf_temper_sites(sipnet_batch* b, const double* d_loglik, const double* d_base, const double* d_delta_max,
-                                 const double* d_ess_target, double* d_delta, double* d_delta_hi, double* d_ess,
-                                 double* d_logw_out, int32_t* d_site_info, void* hip_stream) {
-  const char* who = "sipnet_batch_pf_temper_sites";
-  if (!b || !d_loglik || !d_ess_target || !d_delta) return refuse(who, "a NULL batch, d_loglik, d_ess_target or d_delta");
-  if (tooManyColumns(b)) return refuse(who, "at most 4194304 columns");
-  if (b->pfPeers) return refuse(who, "this batch is connected to a filter across ranks (sipnet_batch_pf_connect)");
-  RC_TRY(useDevice(b));
-  hipStream_t stream = (hipStream_t)hip_stream;
-  TemperArgs a{};
-  a.loglik = d_loglik;
-  a.base = d_base;
-  a.deltaMax = d_delta_max;
-  a.essTarget = d_ess_target;
-  a.delta = d_delta;
-  a.deltaHi = d_delta_hi;
-  a.ess = d_ess;
-  a.logwOut = d_logw_out;
-  a.info = d_site_info;
-  a.M = b->n_members;
-  a.nSites = b->n_sites;
-  if (!d_site_info) RC_TRY(temperCheck(who, b, a, stream));
-  int chunk, nChunks;
-  const bool split = sitesGeometry(b, &chunk, &nChunks);   // (the many-site analysis's rule)
-  a.chunk = chunk;
-  a.nChunks = nChunks;
-  return d_base ? temperLaunch<true>(b, a, split, stream) : temperLaunch<false>(b, a, split, stream);
-}
-
 }  // extern "C"
+
+#include "pf_moves.inc"
 
 // ---- the filter across ranks by peer reads --------------------------------------------------------------------
 void pfRelease(sipnet_batch* b) {

@@ -4,8 +4,9 @@
 // of Foreman-Mackey et al. 2013), and the accept / restore step.  Given the other half the moving chains are independent and
 // the proposal is symmetric, so a whole half moves at once and detailed balance holds exactly.
 //
-// The draw is pf_rejuvenate.inc's counter-based Philox: one call per member, ctr = {member, stream, 8, draw}, gives the two
-// partner ranks (words 0 and 1) and the accept step's uniform (word 2); the jitter's normals are blocks 12..15.  A partner is
+// The draw is pf_random.inc's counter-based Philox: one call per member, block kMcBlock, gives the two partner ranks (words 0
+// and 1, mcDraws) and the accept step's uniform (word 2); the jitter's normals are blocks kMcJitterBlock ...  The listed rows and
+// the write of a member's rows are site_device.h's (ListedRows, MemberRows), the host side is pf_moves.inc.  A partner is
 // a RANK among the live members of the other half in ascending member index; a rank becomes a member by popcounts over the
 // waves' __ballot masks of live lanes (the other half's lanes are the even or the odd bits) and a select of the n-th set bit
 // in six halvings -- no loop over lanes, no list of live members in memory.
@@ -19,21 +20,15 @@
 // paths: it reads no other column.  No atomic, no grid barrier, no spin.
 constexpr int kMcDone = SIPNET_MCMC_DONE, kMcTooFew = SIPNET_MCMC_TOO_FEW, kMcBadInput = SIPNET_MCMC_BAD_INPUT,
               kMcNotSelected = SIPNET_MCMC_NOT_SELECTED;
-constexpr uint32_t kMcBlock = 8;          // the Philox block of a member's partner ranks and accept uniform (0..7: the rejuvenation's)
-constexpr uint32_t kMcJitterBlock = 12;   // ... and the first of the four blocks of the jitter's normals
 constexpr int kMcOffCap = 2048;           // chunk offsets staged in LDS; a site of more chunks bisects the rest in global memory
 constexpr uint64_t kMcEvenLanes = 0x5555555555555555ull;
 
-struct McArgs {
-  int32_t nPrm, half;
-  int32_t prmRow[kRejPrm];                 // the listed rows of prm, in the caller's order
-  double lo[kRejPrm], hi[kRejPrm];         // their bounds, converted units
-  DerivedRows rows;
+struct McArgs : ListedRows {
+  int32_t half;
   const double* gamma;                     // [n_sites] (propose)
   const double* jitter;                    // [n_sites] or null (propose)
   const double* beta;                      // [n_sites] or null: 1 (accept)
-  uint32_t key0, key1, draw;
-  const uint32_t* stream;                  // [n_sites] or null: the site's index
+  DrawKey key;
   const int64_t* siteTotal;                // [n_sites] or null: every site (propose)
   int32_t* info;                           // [n_sites][4]
   const double* state;                     // [NSTATE][ncol]: the status row is read, nothing is written
@@ -55,9 +50,6 @@ struct McArgs {
   int32_t* site;                           // [n_sites][3] the site's code, nB and live members of the moving half
 };
 
-__device__ __forceinline__ bool mcLive(const McArgs& a, int s, int64_t j) {
-  return j < a.M && a.siteStatus[s] == 0 && a.state[(int64_t)ST_status * a.ncol + (int64_t)s * a.M + j] == 0.0;
-}
 // the bits of a wave's live mask that belong to the moving half (other == false) or to the other one
 __device__ __forceinline__ uint64_t mcHalfBits(const McArgs& a, uint64_t mask, bool other) {
   return mask & ((((a.half ^ (other ? 1 : 0)) & 1) == 0) ? kMcEvenLanes : ~kMcEvenLanes);
@@ -103,42 +95,27 @@ __device__ __forceinline__ int mcSelectLane(const uint64_t pm[4], int i) {
   const uint64_t m = wave == 0 ? pm[0] : wave == 1 ? pm[1] : wave == 2 ? pm[2] : pm[3];
   return 64 * wave + mcSelectBit(m, i);
 }
-// the member's Philox words: the two partner ranks among nB (0 <= i1, i2 < nB, i1 != i2) and the accept step's word
-__host__ __device__ inline void mcDraws(uint32_t key0, uint32_t key1, uint32_t draw, uint32_t stream, uint32_t member, uint32_t nB,
-                                        int32_t* i1, int32_t* i2, uint32_t* x2) {
-  uint32_t x[4];
-  philox4x32_10(member, stream, kMcBlock, draw, key0, key1, x);
-  const uint32_t a = (uint32_t)(((uint64_t)x[0] * nB) >> 32);
-  uint32_t b = (uint32_t)(((uint64_t)x[1] * (nB - 1u)) >> 32);
-  b += b >= a ? 1u : 0u;
-  *i1 = (int32_t)a;
-  *i2 = (int32_t)b;
-  *x2 = x[2];
-}
 
 // One live member of the moving half of a code-1 site: its proposal (x(k): its row k now; px(k, r): row k of member r of the
 // site; memberOf(i): the member at rank i of the other half), the tests, and -- if the proposal is made -- the old rows saved,
 // the new ones and the derived rows written.  false: not made, nothing written.
 template <class X, class PX, class R>
-__device__ __forceinline__ bool mcMember(const McArgs& a, int s, int64_t j, double gamma, double w, int nB, X x, PX px, R memberOf) {
+__device__ __forceinline__ bool mcMember(const McArgs& a, int s, int64_t j, int nB, X x, PX px, R memberOf) {
   const int64_t col = (int64_t)s * a.M + j;
-  const uint32_t stream = a.stream ? a.stream[s] : (uint32_t)s, member = (uint32_t)j;
+  const double gamma = a.gamma[s], w = a.jitter ? a.jitter[s] : 0.0;
+  const uint32_t stream = a.key.streamOf(s), member = (uint32_t)j;
   int32_t i1, i2;
   uint32_t x2;
-  mcDraws(a.key0, a.key1, a.draw, stream, member, (uint32_t)nB, &i1, &i2, &x2);
+  mcDraws(a.key, stream, member, (uint32_t)nB, &i1, &i2, &x2);
   const int64_t r1 = memberOf(i1), r2 = memberOf(i2);
   bool ok = true;
   double nv[kRejPrm], old[kRejPrm];
-  double leaf = 0.0, wood = 0.0, fine = 0.0, opt = 0.0, tmin = 0.0;
-  const auto now = [&](int k, int row) {
-    if (k < 0) return a.prm[(int64_t)row * a.ncol + col];
-    return row == SP_leafAllocation ? leaf : row == SP_woodAllocation ? wood : row == SP_fineRootAllocation ? fine : row == SP_psnTOpt ? opt : tmin;
-  };
+  MemberRows mine{a, a.prm, a.ncol, col};
 #pragma unroll
   for (int blk = 0; blk < kRejPrm / 4; blk++) {
     if (4 * blk >= a.nPrm) break;
     double z[4] = {0.0, 0.0, 0.0, 0.0};
-    if (w > 0.0) rejNormals(a.key0, a.key1, a.draw, stream, member, kMcJitterBlock + (uint32_t)blk, 4 * blk + 2 < a.nPrm, z);
+    if (w > 0.0) memberNormals(a.key, stream, member, kMcJitterBlock + (uint32_t)blk, 4 * blk + 2 < a.nPrm, z);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const int k = 4 * blk + i;
@@ -149,23 +126,18 @@ __device__ __forceinline__ bool mcMember(const McArgs& a, int s, int64_t j, doub
       ok = ok && fabs(v) < INFINITY && v >= a.lo[k] && v <= a.hi[k];
       nv[k] = v;
       old[k] = xj;
-      if (k == a.rows.leaf) leaf = v;
-      if (k == a.rows.wood) wood = v;
-      if (k == a.rows.fineRoot) fine = v;
-      if (k == a.rows.opt) opt = v;
-      if (k == a.rows.tmin) tmin = v;
+      mine.set(k, v);
     }
   }
-  ok = allocationsOk(a.rows, now) && ok;
+  ok = mine.allocOk() && ok;
   if (!ok) return false;
   // (no unroll pragma: with the loop above unrolled the compiler already knows nPrm's range on every way here and takes this
   // loop apart itself -- asked to unroll what is left, it warns; the kernels' scratch size stays 0)
   for (int k = 0; k < kRejPrm; k++) {
     if (k >= a.nPrm) break;
     a.saved[(int64_t)k * a.ncol + col] = old[k];
-    a.prm[(int64_t)a.prmRow[k] * a.ncol + col] = nv[k];
   }
-  writeDerivedRows(a.prm, a.ncol, col, a.rows, now);
+  mine.commit(a.prm, nv);
   return true;
 }
 
@@ -181,7 +153,7 @@ __global__ __launch_bounds__(256) void mcGroupKernel(McArgs a) {
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int64_t j = tid, col = (int64_t)s * a.M + j;
   int code = mcProposeInputs(a.gamma, a.jitter, a.siteTotal, s);
-  const bool live = mcLive(a, s, j);
+  const bool live = liveIn(a, s, j);
   const uint64_t ballot = __ballot(live);
   if ((tid & 63) == 0) g.mask[tid >> 6] = ballot;
   __syncthreads();
@@ -196,27 +168,20 @@ __global__ __launch_bounds__(256) void mcGroupKernel(McArgs a) {
   if (code == kMcDone && nB < 2) code = kMcTooFew;
   if (code != kMcDone) {
     if (j < a.M) a.moved[col] = 0;
-    if (tid == 0) {
-      int32_t* o = a.info + 4 * (int64_t)s;
-      o[0] = code, o[1] = 0, o[2] = nA, o[3] = nB;
-    }
+    if (tid == 0) writeInfo4(a.info, s, code, 0, nA, nB);
     return;
   }
   for (int q = 0; q < a.nPrm; q++) g.rows[q][tid] = live ? a.prm[(int64_t)a.prmRow[q] * a.ncol + col] : 0.0;
   __syncthreads();
   int made = 0;
   if (live && (tid & 1) == a.half) {
-    const double w = a.jitter ? a.jitter[s] : 0.0;
-    made = mcMember(a, s, j, a.gamma[s], w, nB, [&](int k) { return g.rows[k][tid]; },
+    made = mcMember(a, s, j, nB, [&](int k) { return g.rows[k][tid]; },
                     [&](int k, int64_t r) { return g.rows[k][r]; }, [&](int i) { return (int64_t)mcSelectLane(pm, i); })
                ? 1 : 0;
   }
   if (j < a.M) a.moved[col] = made;
   const int nMade = blockSum(g.smI, made);
-  if (tid == 0) {
-    int32_t* o = a.info + 4 * (int64_t)s;
-    o[0] = kMcDone, o[1] = nMade, o[2] = nA, o[3] = nB;
-  }
+  if (tid == 0) writeInfo4(a.info, s, kMcDone, nMade, nA, nB);
 }
 
 // ---- the split path: (site, chunk) launches ----------------------------------------------------------------------------
@@ -225,7 +190,7 @@ __global__ __launch_bounds__(256) void mcMaskKernel(McArgs a) {
   __shared__ uint64_t sm[4];
   const int s = (int)blockIdx.x, c = (int)blockIdx.y, tid = (int)threadIdx.x;
   const int64_t j = (int64_t)c * 256 + tid, at = (int64_t)s * a.nCh + c;
-  const uint64_t ballot = __ballot(mcLive(a, s, j));
+  const uint64_t ballot = __ballot(liveIn(a, s, j));
   if ((tid & 63) == 0) {
     sm[tid >> 6] = ballot;
     a.masks[4 * at + (tid >> 6)] = ballot;
@@ -284,8 +249,7 @@ __global__ __launch_bounds__(256) void mcProposeKernel(McArgs a) {
   for (int i = tid; i < staged; i += 256) smOff[i] = a.off[base + i];
   __syncthreads();
   int made = 0;
-  if (mcLive(a, s, j) && (tid & 1) == a.half) {
-    const double w = a.jitter ? a.jitter[s] : 0.0;
+  if (liveIn(a, s, j) && (tid & 1) == a.half) {
     // the member at rank i of the other half: the last chunk whose offset is <= i, then the lane from that chunk's masks
     const auto memberOf = [&](int i) {
       int lo = 0, hi = a.nCh;
@@ -301,7 +265,7 @@ __global__ __launch_bounds__(256) void mcProposeKernel(McArgs a) {
       for (int q = 0; q < 4; q++) pm[q] = mcHalfBits(a, a.masks[4 * (base + lo) + q], true);
       return (int64_t)lo * 256 + mcSelectLane(pm, i - o);
     };
-    made = mcMember(a, s, j, a.gamma[s], w, nB, [&](int k) { return a.prm[(int64_t)a.prmRow[k] * a.ncol + col]; },
+    made = mcMember(a, s, j, nB, [&](int k) { return a.prm[(int64_t)a.prmRow[k] * a.ncol + col]; },
                     [&](int k, int64_t r) { return a.prm[(int64_t)a.prmRow[k] * a.ncol + (int64_t)s * a.M + r]; }, memberOf)
                ? 1 : 0;
   }
@@ -313,14 +277,8 @@ __global__ __launch_bounds__(256) void mcInfoKernel(McArgs a) {
   __shared__ int smI[4];
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int code = a.site[3 * (int64_t)s];
-  int made = 0;
-  if (code == kMcDone)
-    for (int c = tid; c < a.nCh; c += 256) made += a.made[(int64_t)s * a.nCh + c];
-  const int nMade = blockSum(smI, made);
-  if (tid == 0) {
-    int32_t* o = a.info + 4 * (int64_t)s;
-    o[0] = code, o[1] = nMade, o[2] = a.site[3 * (int64_t)s + 2], o[3] = a.site[3 * (int64_t)s + 1];
-  }
+  const int nMade = chunkCounts(smI, a.made, s, a.nCh, code == kMcDone);
+  if (tid == 0) writeInfo4(a.info, s, code, nMade, a.site[3 * (int64_t)s + 2], a.site[3 * (int64_t)s + 1]);
 }
 
 // ---- accept or restore --------------------------------------------------------------------------------------------------
@@ -335,10 +293,9 @@ __global__ __launch_bounds__(256) void mcAcceptKernel(McArgs a, int direct) {
   int handled = 0, taken = 0;
   if (code == kMcDone && j < a.M && a.moved[col] == 1) {
     handled = 1;
-    const uint32_t stream = a.stream ? a.stream[s] : (uint32_t)s;
     uint32_t x[4];
-    philox4x32_10((uint32_t)j, stream, kMcBlock, a.draw, a.key0, a.key1, x);
-    const double u = ((double)x[2] + 0.5) * 0x1p-32;
+    philox4x32_10((uint32_t)j, a.key.streamOf(s), kMcBlock, a.key.draw, a.key.key0, a.key.key1, x);
+    const double u = uniformOf(x[2]);
     const double lpNew = a.logpNew[col], lpCur = a.logpCur[col];
     const double d = lpNew - lpCur;
     const double scaled = a.beta ? a.beta[s] * d : d;
@@ -356,13 +313,12 @@ __global__ __launch_bounds__(256) void mcAcceptKernel(McArgs a, int direct) {
     }
     a.moved[col] = 0;
   }
-  const int nLive = blockSum(smI[0], mcLive(a, s, j) ? 1 : 0);
+  const int nLive = blockSum(smI[0], liveIn(a, s, j) ? 1 : 0);
   const int nHandled = blockSum(smI[1], handled);
   const int nTaken = blockSum(smI[2], taken);
   if (tid != 0) return;
   if (direct) {
-    int32_t* o = a.info + 4 * (int64_t)s;
-    o[0] = code, o[1] = nHandled, o[2] = nTaken, o[3] = nLive;
+    writeInfo4(a.info, s, code, nHandled, nTaken, nLive);
   } else {
     a.cntA[at] = nLive, a.made[at] = nHandled, a.taken[at] = nTaken;
   }
@@ -370,14 +326,7 @@ __global__ __launch_bounds__(256) void mcAcceptKernel(McArgs a, int direct) {
 __global__ __launch_bounds__(256) void mcAcceptInfoKernel(McArgs a) {
   __shared__ int smI[3][4];
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
-  int live = 0, handled = 0, taken = 0;
-  for (int c = tid; c < a.nCh; c += 256) {
-    const int64_t at = (int64_t)s * a.nCh + c;
-    live += a.cntA[at], handled += a.made[at], taken += a.taken[at];
-  }
-  const int nLive = blockSum(smI[0], live), nHandled = blockSum(smI[1], handled), nTaken = blockSum(smI[2], taken);
-  if (tid == 0) {
-    int32_t* o = a.info + 4 * (int64_t)s;
-    o[0] = mcAcceptInputs(a.beta, s), o[1] = nHandled, o[2] = nTaken, o[3] = nLive;
-  }
+  const int nLive = chunkCounts(smI[0], a.cntA, s, a.nCh), nHandled = chunkCounts(smI[1], a.made, s, a.nCh),
+            nTaken = chunkCounts(smI[2], a.taken, s, a.nCh);
+  if (tid == 0) writeInfo4(a.info, s, mcAcceptInputs(a.beta, s), nHandled, nTaken, nLive);
 }

@@ -2,11 +2,8 @@
 // shrinkage move of some of a site's parameter rows, and additive noise on pools.  SIPNET is deterministic, so two copies of
 // a resampled particle stay identical for ever; this pass gives every copy its own draw again.
 //
-// The draw is COUNTER-BASED (Philox4x32-10, Salmon et al. 2011): no generator state anywhere, nothing drawn on the host.  A
-// normal is a function of (seed, draw, the site's stream, the member's index inside its site, a block number) alone, so the
-// result depends neither on the number of sites, nor on the path, nor on the launch geometry.  One Philox call gives four
-// words, two Box-Muller pairs, four normals: the four rows of one block of a member.
-//
+// The draw is pf_random.inc's counter-based Philox (blocks kRejRowBlock .. and kRejPoolBlock ..), the listed rows and the write
+// of a member's rows are site_device.h's (ListedRows, MemberRows), the host side is pf_moves.inc.
 // Two paths with the same bits.  rejGroupKernel: one workgroup per site, for sites of one chunk (at most 256 members) -- the
 // moments of the listed rows over the site's live members (the means, then the centred sums), then the draw and the limits
 // in a second sweep; the rows are staged in LDS, so HBM is read once.  The split path for larger sites (and under
@@ -21,61 +18,12 @@ constexpr int kRejPools = 13;                     // state slots 0..12
 constexpr int kRejDone = SIPNET_REJUVENATE_DONE, kRejTooFew = SIPNET_REJUVENATE_TOO_FEW, kRejBadInput = SIPNET_REJUVENATE_BAD_INPUT,
               kRejNotSelected = SIPNET_REJUVENATE_NOT_SELECTED;
 
-// Philox4x32-10: ten rounds of two 32 x 32 -> 64 bit products, the key bumped by the Weyl constants between rounds
-__host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0;
-  out[1] = c1;
-  out[2] = c2;
-  out[3] = c3;
-}
-// two normals from two words: u = (xa + 0.5) 2^-32 and v = (xb + 0.5) 2^-32 (exact), r = sqrt(-2 ln u), r cos(2 pi v) and
-// r sin(2 pi v).  The angle is reduced exactly -- 2 v = k / 2 + f, |f| <= 1/4 -- before pi enters, so its rounding costs a
-// fraction of an ulp instead of 2 pi of them.
-__host__ __device__ inline void boxMuller(uint32_t xa, uint32_t xb, double* za, double* zb) {
-  const double u = ((double)xa + 0.5) * 0x1p-32, v = ((double)xb + 0.5) * 0x1p-32;
-  const double r = sqrt(-2.0 * log(u));
-  const int k = (int)rint(4.0 * v);
-  const double f = 2.0 * v - 0.5 * (double)k;
-#ifdef __HIP_DEVICE_COMPILE__
-  const double sf = sinpi(f), cf = cospi(f);
-#else
-  const double sf = sin(3.14159265358979323846 * f), cf = cos(3.14159265358979323846 * f);
-#endif
-  const double c = (k & 1) ? ((k & 2) ? sf : -sf) : ((k & 2) ? -cf : cf);
-  const double s = (k & 1) ? ((k & 2) ? -cf : cf) : ((k & 2) ? -sf : sf);
-  *za = r * c;
-  *zb = r * s;
-}
-// the four normals of one block of one member: ctr = {member, stream, block, draw}
-__host__ __device__ inline void rejNormals(uint32_t k0, uint32_t k1, uint32_t draw, uint32_t stream, uint32_t member,
-                                           uint32_t block, bool second, double z[4]) {
-  uint32_t x[4];
-  philox4x32_10(member, stream, block, draw, k0, k1, x);
-  boxMuller(x[0], x[1], &z[0], &z[1]);
-  if (second) boxMuller(x[2], x[3], &z[2], &z[3]);
-}
-
-struct RejArgs {
-  int32_t nPrm, mask;
-  int32_t prmRow[kRejPrm];                 // the listed rows of prm, in the caller's order
-  double lo[kRejPrm], hi[kRejPrm];         // their bounds, converted units
-  DerivedRows rows;                        // where leafAllocation .. psnTMin are among the listed rows
+// (keep mask, shrink and poolSd in front: behind the fields McArgs has too, rejApplyKernel compiled a quarter longer and ran a tenth slower)
+struct RejArgs : ListedRows {
+  int32_t mask;
   const double* shrink;                    // [n_sites] a, or null (nPrm == 0)
   const double* poolSd;                    // [n_sites][13], or null (mask == 0)
-  uint32_t key0, key1, draw;
-  const uint32_t* stream;                  // [n_sites] or null: the site's index
+  DrawKey key;
   const int64_t* siteTotal;                // [n_sites] or null: every site
   int32_t* info;                           // [n_sites][4]
   double* state;                           // [NSTATE][ncol]
@@ -91,9 +39,6 @@ struct RejArgs {
   int32_t* site;                           // [n_sites][2] the site's code and live count
 };
 
-__device__ __forceinline__ bool rejLive(const RejArgs& a, int s, int64_t j) {
-  return j < a.M && a.siteStatus[s] == 0 && a.state[(int64_t)ST_status * a.ncol + (int64_t)s * a.M + j] == 0.0;
-}
 // the site's inputs: kRejNotSelected, kRejBadInput, or kRejDone (before the live count)
 __host__ __device__ inline int rejSiteInputs(const double* shrink, const double* poolSd, const int64_t* siteTotal, int nPrm,
                                              int mask, int64_t s) {
@@ -124,22 +69,17 @@ template <class X>
 __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, double shrinkA, const double* mean,
                                           const double* hsd, X x) {
   const int64_t col = (int64_t)s * a.M + j;
-  const uint32_t stream = a.stream ? a.stream[s] : (uint32_t)s, member = (uint32_t)j;
+  const uint32_t stream = a.key.streamOf(s), member = (uint32_t)j;
   const bool rows = a.nPrm > 0 && shrinkA != 1.0;
   bool ok = true;
   double nv[kRejPrm];
-  double leaf = 0.0, wood = 0.0, fine = 0.0, opt = 0.0, tmin = 0.0;
-  // the member's value of one of the five rows that the derived rows depend on: a listed one's from its register
-  const auto now = [&](int k, int row) {
-    if (k < 0) return a.prm[(int64_t)row * a.ncol + col];
-    return row == SP_leafAllocation ? leaf : row == SP_woodAllocation ? wood : row == SP_fineRootAllocation ? fine : row == SP_psnTOpt ? opt : tmin;
-  };
+  MemberRows mine{a, a.prm, a.ncol, col};
   if (rows) {
 #pragma unroll
     for (int blk = 0; blk < kRejPrm / 4; blk++) {
       if (4 * blk >= a.nPrm) break;
       double z[4] = {0.0, 0.0, 0.0, 0.0};
-      rejNormals(a.key0, a.key1, a.draw, stream, member, (uint32_t)blk, 4 * blk + 2 < a.nPrm, z);
+      memberNormals(a.key, stream, member, kRejRowBlock + (uint32_t)blk, 4 * blk + 2 < a.nPrm, z);
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int k = 4 * blk + i;
@@ -151,14 +91,10 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
         v = v < a.lo[k] ? a.lo[k] : (v > a.hi[k] ? a.hi[k] : v);
         ok = ok && fabs(v) < INFINITY;
         nv[k] = v;
-        if (k == a.rows.leaf) leaf = v;
-        if (k == a.rows.wood) wood = v;
-        if (k == a.rows.fineRoot) fine = v;
-        if (k == a.rows.opt) opt = v;
-        if (k == a.rows.tmin) tmin = v;
+        mine.set(k, v);
       }
     }
-    ok = allocationsOk(a.rows, now) && ok;
+    ok = mine.allocOk() && ok;
   }
   // the pools: the masked slots with an sd above 0 perturbed and clipped; hasSufficientBiomass (sipnet.c:1530-1536) of the result
   double f[kRejPools];
@@ -168,7 +104,7 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
   for (int blk = 0; blk < 4; blk++) {
     const int bits = (a.mask >> (4 * blk)) & 15;
     double z[4] = {0.0, 0.0, 0.0, 0.0};
-    if (bits) rejNormals(a.key0, a.key1, a.draw, stream, member, (uint32_t)(4 + blk), (bits & 12) != 0, z);
+    if (bits) memberNormals(a.key, stream, member, kRejPoolBlock + (uint32_t)blk, (bits & 12) != 0, z);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const int p = 4 * blk + i;
@@ -189,14 +125,7 @@ __device__ __forceinline__ bool rejMember(const RejArgs& a, int s, int64_t j, do
 #pragma unroll
   for (int p = 0; p < kRejPools; p++)
     if (moved[p]) a.state[(int64_t)p * a.ncol + col] = f[p];
-  if (rows) {
-#pragma unroll
-    for (int k = 0; k < kRejPrm; k++) {
-      if (k >= a.nPrm) break;
-      a.prm[(int64_t)a.prmRow[k] * a.ncol + col] = nv[k];
-    }
-    writeDerivedRows(a.prm, a.ncol, col, a.rows, now);
-  }
+  if (rows) mine.commit(a.prm, nv);
   return true;
 }
 
@@ -217,14 +146,11 @@ __global__ __launch_bounds__(256) void rejGroupKernel(RejArgs a) {
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int64_t j = tid, col = (int64_t)s * a.M + j;
   int code = rejSiteInputs(a.shrink, a.poolSd, a.siteTotal, a.nPrm, a.mask, s);
-  const bool live = rejLive(a, s, j);
+  const bool live = liveIn(a, s, j);
   const int n = blockCount(g, live ? 1 : 0);
   if (code == kRejDone && n < 2) code = kRejTooFew;
   if (code != kRejDone) {
-    if (tid == 0) {
-      int32_t* o = a.info + 4 * (int64_t)s;
-      o[0] = code, o[1] = 0, o[2] = n, o[3] = 0;
-    }
+    if (tid == 0) writeInfo4(a.info, s, code, 0, n, 0);
     return;
   }
   const double shrinkA = a.nPrm > 0 ? a.shrink[s] : 1.0;
@@ -243,10 +169,7 @@ __global__ __launch_bounds__(256) void rejGroupKernel(RejArgs a) {
   int kept = 0;
   if (live) kept = rejMember(a, s, j, shrinkA, g.mean, g.hsd, [&](int k) { return g.rows[k][tid]; }) ? 0 : 1;
   const int nKept = blockSum(g.smI, kept);
-  if (tid == 0) {
-    int32_t* o = a.info + 4 * (int64_t)s;
-    o[0] = kRejDone, o[1] = rejPerturbed(a, s), o[2] = n, o[3] = nKept;
-  }
+  if (tid == 0) writeInfo4(a.info, s, kRejDone, rejPerturbed(a, s), n, nKept);
 }
 
 // ---- the split path: (site, chunk) launches ----------------------------------------------------------------------------
@@ -257,7 +180,7 @@ __global__ __launch_bounds__(256) void rejChunkKernel(RejArgs a, int pass) {
   __shared__ int smI[4];
   const int s = (int)blockIdx.x, c = (int)blockIdx.y, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t j = (int64_t)c * 256 + tid, col = (int64_t)s * a.M + j;
-  const bool live = rejLive(a, s, j);
+  const bool live = liveIn(a, s, j);
   if (pass == 0) {
     const int n = blockSum(smI, live ? 1 : 0);
     if (tid == 0) a.cnt[(int64_t)s * a.nCh + c] = n;
@@ -288,9 +211,7 @@ __global__ __launch_bounds__(256) void rejSiteKernel(RejArgs a, int pass) {
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   int n;
   if (pass == 0) {
-    int live = 0;
-    for (int c = tid; c < a.nCh; c += 256) live += a.cnt[(int64_t)s * a.nCh + c];
-    n = blockSum(smI, live);
+    n = chunkCounts(smI, a.cnt, s, a.nCh);
     int code = rejSiteInputs(a.shrink, a.poolSd, a.siteTotal, a.nPrm, a.mask, s);
     if (code == kRejDone && n < 2) code = kRejTooFew;
     if (tid == 0) a.site[2 * (int64_t)s] = code, a.site[2 * (int64_t)s + 1] = n;
@@ -330,7 +251,7 @@ __global__ __launch_bounds__(256) void rejApplyKernel(RejArgs a) {
   const double* stat = a.stat + (int64_t)s * 2 * kRejPrm;
   const double shrinkA = a.nPrm > 0 ? a.shrink[s] : 1.0;
   int kept = 0;
-  if (rejLive(a, s, j))
+  if (liveIn(a, s, j))
     kept = rejMember(a, s, j, shrinkA, stat, stat + kRejPrm, [&](int k) { return a.prm[(int64_t)a.prmRow[k] * a.ncol + col]; }) ? 0 : 1;
   const int nKept = blockSum(smI, kept);
   if (tid == 0) a.kept[(int64_t)s * a.nCh + c] = nKept;
@@ -339,12 +260,6 @@ __global__ __launch_bounds__(256) void rejInfoKernel(RejArgs a) {
   __shared__ int smI[4];
   const int s = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int code = a.site[2 * (int64_t)s];
-  int kept = 0;
-  if (code == kRejDone)
-    for (int c = tid; c < a.nCh; c += 256) kept += a.kept[(int64_t)s * a.nCh + c];
-  const int nKept = blockSum(smI, kept);
-  if (tid == 0) {
-    int32_t* o = a.info + 4 * (int64_t)s;
-    o[0] = code, o[1] = code == kRejDone ? rejPerturbed(a, s) : 0, o[2] = a.site[2 * (int64_t)s + 1], o[3] = nKept;
-  }
+  const int nKept = chunkCounts(smI, a.kept, s, a.nCh, code == kRejDone);
+  if (tid == 0) writeInfo4(a.info, s, code, code == kRejDone ? rejPerturbed(a, s) : 0, a.site[2 * (int64_t)s + 1], nKept);
 }

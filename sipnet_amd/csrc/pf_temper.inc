@@ -10,7 +10,8 @@
 // leaves every chunk's exact partial triples in scratch, the next launch's workgroups each sum the site's partials and derive
 // the new bracket -- every workgroup of a site decides alike, as in sitesAncestorKernel.  No atomic, no grid barrier, no spin.
 // All sums are integers, so no reduction order shows; the only floating-point values a path could disturb are the candidates
-// (temperCandidate) and the tempered log-weights (temperV), which are written with explicit operations.
+// (temperCandidate) and the tempered log-weights (temperV), which are written with explicit operations.  The wave sums are
+// site_device.h's (waveSum, blockSum); the host side, with the note on why d_base takes the launches, is pf_moves.inc.
 constexpr int kTemperCand = SIPNET_TEMPER_SECTIONS - 1;   // candidates of a round
 constexpr int kTemperWords = 3 * kTemperCand;             // a round's sums: S | squares, low word | squares, the rest
 constexpr int32_t kTemperSearching = 3;                   // a site's state between the stages (never reported)
@@ -127,9 +128,7 @@ __device__ __forceinline__ void temperBlockSum(long long (&v)[kTemperWords], lon
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
 #pragma unroll
   for (int q = 0; q < kTemperWords; q++) {
-    long long x = v[q];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    const long long x = waveSum(v[q]);
     if (lane == 0) smSum[wave * kTemperWords + q] = x;
   }
   __syncthreads();
@@ -196,7 +195,7 @@ __device__ __forceinline__ void temperWrite(const TemperArgs& a, int s, const Te
 }
 
 // One workgroup = one site (blockIdx.x), M <= kSitesLds, no carried log-weights (with them the call takes the per-chunk
-// launches: pf.hip says why).  Dynamic LDS: loglik [M].
+// launches: pf_moves.inc says why).  Dynamic LDS: loglik [M].
 __global__ __launch_bounds__(256) void temperGroupKernel(TemperArgs a) {
   extern __shared__ double temperLds[];
   __shared__ long long smSum[4 * kTemperWords];
@@ -284,10 +283,7 @@ __device__ __forceinline__ TemperState temperStateBefore(const TemperArgs& a, in
   *maxLl = blockMax256(pl, smD);
   if (stage == 0) {
     const double maxBase = blockMax256(pb, smD);
-    int cnt = 0;
-    for (int q = tid; q < nCh; q += 256) cnt += a.chunkCnt[(int64_t)s * nCh + q];
-    cnt = blockSum(smI, cnt);
-    return temperBegin(scalarsOk, dmax, *maxLl, maxBase, cnt);
+    return temperBegin(scalarsOk, dmax, *maxLl, maxBase, chunkCounts(smI, a.chunkCnt, s, nCh));
   }
   TemperState st = a.state[(int64_t)(stage - 1) * a.nSites + s];
   if (st.code != kTemperSearching) return st;   // (the same in every thread)

@@ -1,5 +1,6 @@
 // site_device.h -- the device side that the per-site analyses share (enkf.hip, pf.hip, quantiles.hip and their .inc parts):
-// the sums in their one order, a member's physical limits, and the parameter rows that are derived from listed ones.  Plain
+// which members are live, the sums in their one order, a member's physical limits, and a call's listed parameter rows with the
+// rows that are derived from them (ListedRows, MemberRows: what the particle moves of pf.hip write a member's rows through).  Plain
 // functions and templates, included INSIDE each unit's anonymous namespace like the .inc parts (so no include guard: once per
 // unit).  fast_math.h has a kTiny of its own for the step kernels; no unit sees both.
 //
@@ -7,12 +8,14 @@
 // (waveSum), the four waves in order (combine4: ((w0 + w1) + w2) + w3), the chunks in order from 0.0 (siteSums).
 constexpr double kTiny = 0.000001;   // TINY, common/util.h
 
-__device__ __forceinline__ double waveSum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
+// member j of site s takes part: it is inside the site, the site ran, and so did the member (status row 0)
+__device__ __forceinline__ bool memberLive(const int32_t* siteStatus, const double* state, int64_t ncol, int64_t M, int s, int64_t j) {
+  return j < M && siteStatus[s] == 0 && state[(int64_t)ST_status * ncol + (int64_t)s * M + j] == 0.0;
 }
-__device__ __forceinline__ int waveSum(int v) {
+template <class A>   // ... by a kernel's arguments
+__device__ __forceinline__ bool liveIn(const A& a, int s, int64_t j) { return memberLive(a.siteStatus, a.state, a.ncol, a.M, s, j); }
+template <class T>   // double, int, long long
+__device__ __forceinline__ T waveSum(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
@@ -33,6 +36,18 @@ __device__ int blockCount(G& g, int v) {
   const int n = blockSum(g.smI, v);
   __syncthreads();
   return n;
+}
+// the sum of a site's per-chunk counts cnt[s][0 .. nCh), to every thread (counted == false: 0); blockSum's barrier and smI
+__device__ __forceinline__ int chunkCounts(int* smI, const int32_t* cnt, int s, int nCh, bool counted = true) {
+  int v = 0;
+  if (counted)
+    for (int c = (int)threadIdx.x; c < nCh; c += 256) v += cnt[(int64_t)s * nCh + c];
+  return blockSum(smI, v);
+}
+// a site's four info words (one thread)
+__device__ __forceinline__ void writeInfo4(int32_t* info, int s, int w0, int w1, int w2, int w3) {
+  int32_t* o = info + 4 * (int64_t)s;
+  o[0] = w0, o[1] = w1, o[2] = w2, o[3] = w3;
 }
 template <int kCap>
 __device__ __forceinline__ double combine4(const double* smW, int q) {   // smW [4][kCap]: the waves in order
@@ -126,3 +141,41 @@ __device__ __forceinline__ void writeDerivedRows(double* prm, int64_t ncol, int6
     prm[(int64_t)SP_coarseRootAllocation * ncol + col] = 1 - leaf - wood - fine;
   }
 }
+
+// The parameter rows a call lists (sipnet_enkf_params_check's), as a kernel's arguments carry them
+struct ListedRows {
+  int32_t nPrm;
+  int32_t prmRow[SIPNET_ENKF_MAX_PARAMS];                            // the listed rows of prm, in the caller's order
+  double lo[SIPNET_ENKF_MAX_PARAMS], hi[SIPNET_ENKF_MAX_PARAMS];     // their bounds, converted units
+  DerivedRows rows;                                                  // where leafAllocation .. psnTMin are among them
+};
+// One member's listed rows while a move gives them new values: those of the five rows that the derived rows depend on stay in
+// registers as they are set, so allocOk and commit read a listed row's new value (now) and any other row as it stands in prm.
+struct MemberRows {
+  const ListedRows& l;
+  const double* prm;   // [NPARAMS][ncol]
+  int64_t ncol, col;
+  double leaf = 0.0, wood = 0.0, fine = 0.0, opt = 0.0, tmin = 0.0;
+  __device__ __forceinline__ void set(int k, double v) {
+    if (k == l.rows.leaf) leaf = v;
+    if (k == l.rows.wood) wood = v;
+    if (k == l.rows.fineRoot) fine = v;
+    if (k == l.rows.opt) opt = v;
+    if (k == l.rows.tmin) tmin = v;
+  }
+  // the member's value of one of the five rows: a listed one's (k >= 0) from its register
+  __device__ __forceinline__ double now(int k, int row) const {
+    if (k < 0) return prm[(int64_t)row * ncol + col];
+    return row == SP_leafAllocation ? leaf : row == SP_woodAllocation ? wood : row == SP_fineRootAllocation ? fine : row == SP_psnTOpt ? opt : tmin;
+  }
+  __device__ __forceinline__ bool allocOk() const { return allocationsOk(l.rows, [&](int k, int row) { return now(k, row); }); }
+  // the listed rows' new values nv[k], then the derived rows, into column col of out (unrolled: nv stays in registers)
+  __device__ __forceinline__ void commit(double* out, const double* nv) const {
+#pragma unroll
+    for (int k = 0; k < SIPNET_ENKF_MAX_PARAMS; k++) {
+      if (k >= l.nPrm) break;
+      out[(int64_t)l.prmRow[k] * ncol + col] = nv[k];
+    }
+    writeDerivedRows(out, ncol, col, l.rows, [&](int k, int row) { return now(k, row); });
+  }
+};

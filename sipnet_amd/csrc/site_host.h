@@ -1,6 +1,7 @@
 // site_host.h -- the host side that the per-site analyses share (enkf.hip, pf.hip, quantiles.hip): a refusal, the limit on a
-// batch's columns, the bookkeeping of a call that writes the batch, a scratch block grown, the request for dynamic LDS past
-// what a kernel may use unasked, what sipnet_batch_pf_info reports of the last call, and the copies of a synchronous form's check.  batch_impl.h stays the batch object and the stream bookkeeping.
+// batch's columns, the bookkeeping of a call that writes the batch, a scratch block grown and carved into arrays from one
+// description of its layout, the request for dynamic LDS past what a kernel may use unasked, what sipnet_batch_pf_info reports
+// of the last call, and the copies of a synchronous form's check.  batch_impl.h stays the batch object and the stream bookkeeping.
 #pragma once
 #include <string>
 #include <vector>
@@ -38,6 +39,28 @@ int growScratch(sipnet_batch* b, DevBuf<T>& block, size_t count) {
   if (block.capacity() >= count) return SIPNET_OK;
   RC_TRY(waitIdle(b));
   return block.reserve(count);
+}
+
+// A byte block carved into typed arrays: the layout is written ONCE, as a function that takes its arrays from a Carver in order
+// (wider element types first), and carveScratch runs it twice -- to measure, then over the block grown to that size.
+struct Carver {
+  unsigned char* base;   // null: measure only
+  size_t bytes = 0;
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + bytes) : nullptr;
+    bytes += count * sizeof(T);
+    return p;
+  }
+};
+template <class F>
+int carveScratch(sipnet_batch* b, DevBuf<unsigned char>& block, F layout) {
+  Carver measure{nullptr}, assign{nullptr};
+  layout(measure);
+  RC_TRY(growScratch(b, block, measure.bytes));
+  assign.base = block.get();
+  layout(assign);
+  return SIPNET_OK;
 }
 
 // "A launch of `kernel` may use dynBytes of dynamic LDS": *ok, after the kernel was given the attribute where its static

@@ -544,6 +544,35 @@ def test_synchronous_form_and_refusals(base):
         c.mcmc_propose(params, [0.3])
     assert e.value.code == BAD and "set up" in str(e.value)
     c.close()
+    # two things wrong at once, at the smallest shape and with no launch: n_params, the listed rows, the half and a NULL
+    # array answer in that order, and all of them before the batch's
+    c = sa.Batch(sa.flags_from(), 1, 2, sa.F64, fast_math=True)
+    c.set_climate(0, site_clim(0))
+    c.set_params(0, synth.perturbed_params(base, 2, seed=1))
+    L, twice = sa.lib(), listed(NAMES[:1]) * 2
+    sv, mv2, lp = saved[:, :2].contiguous(), moved[:2].contiguous(), new[:2].contiguous()
+    P = _lib.ptr
+
+    def raw_propose(prm, half, gamma, sv_, mv_):
+        return L.sipnet_batch_mcmc_propose(c.h, len(prm), (_lib.EnkfParam * len(prm))(*prm), P(gamma), None, half, 1, 0, None, None,
+                                           P(sv_), P(mv_), None, None)
+
+    def raw_accept(prm, sv_, mv_, new_, cur_):
+        return L.sipnet_batch_mcmc_accept(c.h, len(prm), (_lib.EnkfParam * len(prm))(*prm), P(sv_), P(mv_), P(new_), P(cur_), None,
+                                          1, 0, None, None, None)
+
+    for call, word in ((lambda: raw_propose(twice, 2, None, sv, mv2), "twice"),            # ... a bad half, no d_gamma, not set up
+                       (lambda: raw_propose(params, 2, None, sv, mv2), "half"),            # ... no d_gamma, not set up
+                       (lambda: raw_propose(params, 2, lp, sv, mv2), "half"),              # ... not set up
+                       (lambda: raw_propose(params, 1, lp, None, None), "NULL d_saved"),   # ... no d_moved, not set up
+                       (lambda: raw_propose(params, 0, lp, sv, None), "NULL d_moved"),     # ... not set up
+                       (lambda: raw_accept(twice, None, mv2, lp, lp), "twice"),            # ... no d_saved, not set up
+                       (lambda: raw_accept(params, sv, mv2, None, None), "NULL d_logp_new"),
+                       (lambda: raw_accept(params, sv, mv2, lp, None), "NULL d_logp_cur")):
+        assert call() == BAD
+        why = L.sipnet_last_error().decode()
+        assert word in why and "set up" not in why, why
+    c.close()
     # a batch connected across ranks
     c, _ = forecast(base, 1, 64, sa.F64, steps=48)
     c.pf_connect([c.pf_publish(with_params=True)], 0)

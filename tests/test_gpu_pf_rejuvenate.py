@@ -485,6 +485,22 @@ def test_refusals(base):
         c.pf_rejuvenate(listed(NAMES[:2]), [0.9])
     assert e.value.code == BAD and "set up" in str(e.value)
     c.close()
+    # two things wrong at once, at the smallest shape and with no launch: the arguments' refusals answer in their order,
+    # and all of them before the batch's
+    c = sa.Batch(sa.flags_from(), 1, 2, sa.F64, fast_math=True)
+    c.set_climate(0, site_clim(0))
+    c.set_params(0, synth.perturbed_params(base, 2, seed=1))
+    twice = listed(NAMES[:1]) * 2
+    for call, word in ((lambda: c.pf_rejuvenate(twice, None), "twice"),                                  # ... and no d_shrink
+                       (lambda: c.pf_rejuvenate(twice, [0.9], ["plantWoodC"], None), "twice"),           # ... and no d_pool_sd
+                       (lambda: c.pf_rejuvenate(listed(NAMES[:2]), None, ["plantWoodC"], None), "d_shrink"),
+                       (lambda: c.pf_rejuvenate(listed(NAMES[:2]), None), "d_shrink"),                   # ... and not set up
+                       (lambda: c.pf_rejuvenate((), None, ["plantWoodC"], None), "d_pool_sd"),
+                       (lambda: c.pf_rejuvenate((), None), "nothing to do")):
+        with pytest.raises(sa.SipnetError) as e:
+            call()
+        assert e.value.code == BAD and word in str(e.value) and "set up" not in str(e.value), str(e.value)
+    c.close()
     # a batch connected across ranks
     c, _ = forecast(base, 1, 64, sa.F64, steps=48)
     c.pf_connect([c.pf_publish(with_params=True)], 0)

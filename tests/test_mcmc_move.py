@@ -157,6 +157,15 @@ def test_refusals_that_need_no_device():
         assert call(good, moved=False) == BAD and b"NULL d_moved" in why()
         # well-formed arguments get as far as the batch
         assert call(good) == BAD and b"NULL batch" in why() and name in why()
+        # two things wrong at once: the earlier check answers -- n_params, the listed rows, (the half,) a NULL array, the batch
+        assert call([(a, 20.0, 20.0)], n_params=0, saved=False) == BAD and b"1..16" in why()
+        assert call(good + [(a, 1.0, 20.0)], saved=False) == BAD and b"twice" in why()
+        assert call(good, saved=False, moved=False) == BAD and b"NULL d_saved" in why()
+    assert propose(good + [(a, 1.0, 20.0)], half=2) == BAD and b"twice" in why()
+    assert propose(good, half=2, gamma=False) == BAD and b"half" in why()
+    assert propose(good, gamma=False, saved=False) == BAD and b"NULL d_gamma" in why()
+    assert accept(good, moved=False, new=False) == BAD and b"NULL d_moved" in why()
+    assert accept(good, new=False, cur=False) == BAD and b"NULL d_logp_new" in why()
     assert propose(good, half=2) == BAD and b"half" in why()
     assert propose(good, half=-1) == BAD and b"half" in why()
     assert propose(good, gamma=False) == BAD and b"NULL d_gamma" in why()

@@ -122,6 +122,12 @@ def test_refusals_that_need_no_device():
     # well-formed arguments get as far as the batch
     assert call([(a, 1.0, 20.0)], mask=0x10FF, pool_sd=True) == BAD and b"NULL batch" in why()
     assert call([], mask=1, pool_sd=True, shrink=False) == BAD and b"NULL batch" in why()
+    # two things wrong at once: the earlier check answers -- the listed rows, d_shrink, the mask, d_pool_sd, nothing to do
+    assert call([(a, 20.0, 20.0)], shrink=False) == BAD and b"d_shrink" not in why() and b"NULL batch" not in why()
+    assert call([(a, 1.0, 20.0), (a, 1.0, 20.0)], mask=1 << 13) == BAD and b"twice" in why()
+    assert call([(a, 1.0, 20.0)], shrink=False, mask=1 << 13) == BAD and b"d_shrink" in why()
+    assert call([(a, 1.0, 20.0)], mask=(1 << 13) | 1) == BAD and b"pools 0..12" in why()
+    assert call([], mask=1) == BAD and b"d_pool_sd" in why()
 
 
 @pytest.mark.parametrize("n", [4096, 65536])
