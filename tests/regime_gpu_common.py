@@ -29,10 +29,13 @@ def family_ok(family, flagset, name):
                     "coop_ncycle": "stepCoopNKernel", "coop_ncycle_pair": "stepCoopNPairKernel"}[family]
 
 
-def batch(flags, clims, members, prec, kernel, options=0, strict=False, diagnostics=False):
+def batch(flags, clims, members, prec, kernel, options=0, strict=False, diagnostics=False, events=None):
+    """events: None, or every site's list of sa.Event"""
     b = sa.Batch(flags, len(clims), members.shape[0], prec, fast_math=(not strict) if prec == sa.F64 else None,
                  kernel=kernel, kernel_options=options)
     for s, c in enumerate(clims):
+        if events is not None:
+            b.set_events(s, events[s])
         b.set_climate(s, c)
     b.set_params(None, members)
     if diagnostics:

@@ -99,7 +99,7 @@ np.save(out_path, out)
     return out
 
 
-def ref_warning_counts(flags, param_file, clim_file, raw_members, first_steps=None):
+def ref_warning_counts(flags, param_file, clim_file, raw_members, first_steps=None, events_file="/nonexistent/events.in"):
     """The reference's OWN per-step self-check warnings, counted per member: the real reference (not
     quiet) runs every member in a child process whose stdout is parsed for
       "[WARNING] ... Non-negative stock constraint applied for ..."   ensureNonNegative(), sipnet.c:1346-1356
@@ -107,10 +107,10 @@ def ref_warning_counts(flags, param_file, clim_file, raw_members, first_steps=No
     -> (n_clamp_warn[n_members], n_balance_warn[n_members])"""
     code = r"""
 import ctypes as C, numpy as np, sys, pickle, os
-flags, param_file, clim_file, raw_path, so = pickle.load(open(sys.argv[1],'rb'))
+flags, param_file, clim_file, events_file, raw_path, so = pickle.load(open(sys.argv[1],'rb'))
 ref = C.CDLL(so); libc = C.CDLL(None)
 fl = (C.c_int*12)(*flags)
-n = ref.ref_init(fl, param_file.encode(), clim_file.encode(), b"/nonexistent/events.in", b"/dev/null")
+n = ref.ref_init(fl, param_file.encode(), clim_file.encode(), events_file.encode(), b"/dev/null")
 ref.ref_set_quiet(0)
 raw = np.load(raw_path)
 for m in range(raw.shape[0]):
@@ -124,7 +124,7 @@ libc.fflush(None)
     raw_path = os.path.join(tmp, "raw.npy")
     np.save(raw_path, raw_members)
     job = os.path.join(tmp, "job.pkl")
-    pickle.dump((list(flags), param_file, clim_file, raw_path, REF_SO), open(job, "wb"))
+    pickle.dump((list(flags), param_file, clim_file, events_file, raw_path, REF_SO), open(job, "wb"))
     out = subprocess.run([sys.executable, "-c", code, job], check=True, capture_output=True).stdout.decode(errors="replace")
     shutil.rmtree(tmp)
     clamp, bal = np.zeros(len(raw_members), dtype=np.int64), np.zeros(len(raw_members), dtype=np.int64)
@@ -274,6 +274,52 @@ def edit_records():
         assert rec_reset[steps[0], 32] == 0.0 and rec[steps[0], 32] != 0.0 and not np.array_equal(rec_reset[-1], rec[-1])
         print("edit records", case, steps, "kept", len(idx), "wood after each edit", rec[list(steps), 14])
     np.savez_compressed(os.path.join(GOLD, "ref_edit_records.npz"), **out)
+
+
+EVENT_MEMBERS = (0, 7)          # of tests/forcing_regimes.hard_members: the base member and a perturbed one
+
+
+def event_index(n, event_records, every=7):
+    """the records within three of any event, every seventh record and the last"""
+    near = {t + k for t in event_records for k in range(-3, 4) if 0 <= t + k < n}
+    return np.array(sorted(near | set(range(0, n, every)) | {n - 1}), dtype=np.int32)
+
+
+def event_records():
+    """tests/golden/ref_event_records.npz: the real reference's step loop on the schedules of tests/event_regimes.py -- the
+    one-record-a-day forcing written as a `.clim`, each schedule as an `events.in` -- under the three flag sets of the regime
+    tests, for two members, for tests/test_event_regimes.py to hold the oracle against bit for bit.  The reference's reader
+    refuses leaf-on / leaf-off events next to a computed phenology (events.c:251-261; all three flag sets compute it), so
+    the files carry the five other types.  Stored per schedule: the record indices, and per flag set the two members'
+    records there and the warning lines the reference printed for them (ref_warning_counts: clamp, balance)."""
+    from sipnet_amd import synth
+    from tests import event_regimes as er
+    data = os.path.join(REPO, "sipnet_amd", "data")
+    tmp = tempfile.mkdtemp(prefix="mkgold_events_")
+    clim_path = os.path.join(tmp, "daily2y.clim")
+    synth.write_clim(clim_path, er.daily2y_raw())
+    clim = er.clim("daily2y")
+    out = {"members": np.array(EVENT_MEMBERS, dtype=np.int32)}
+    for name, schedule in er.SCHEDULES.items():
+        events = [e for e in schedule(clim) if e.type not in (er.LEAFON, er.LEAFOFF)]
+        ev_path = os.path.join(tmp, name + ".in")
+        open(ev_path, "w").write(er.events_in_text(events))
+        idx = event_index(clim.n_steps, er.records_of(clim, events))
+        out[f"{name}_idx"] = idx
+        for flagset in er.FLAG_SETS:
+            flags = er.flags(flagset)
+            param_file = os.path.join(data, "base_forest.param" if flagset == "default" else "allflags_forest.param")
+            members = er.members(flagset)[list(EVENT_MEMBERS)]
+            rec = ref_run(flags, param_file, clim_path, ev_path, members)
+            assert rec.shape == (len(EVENT_MEMBERS), clim.n_steps, NREC) and np.isfinite(rec).all()
+            out[f"{name}_{flagset}"] = rec[:, idx]
+            clamp, balance = ref_warning_counts(flags, param_file, clim_path, members, events_file=ev_path)
+            out[f"{name}_{flagset}_warnings"] = np.stack([clamp, balance])
+        print("event records", name, len(events), "events, kept", len(idx), "records")
+    shutil.rmtree(tmp)
+    path = os.path.join(GOLD, "ref_event_records.npz")
+    np.savez_compressed(path, **out)
+    print("event records:", os.path.getsize(path), "bytes")
 
 
 def special_members(base):
@@ -560,6 +606,7 @@ if __name__ == "__main__":
     copy_smoke()
     smoke_records()
     edit_records()
+    event_records()
     synthetic()
     warning_counts()
     restart_cases()
