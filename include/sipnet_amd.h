@@ -1154,7 +1154,8 @@ int sipnet_batch_enkf_analysis_sharded(sipnet_batch *b, int32_t n_obs, const sip
  * parameter is read).  Everything is enqueued on hip_stream; nothing is synchronised.  No grid barrier, no spin, no
  * floating-point atomic.
  * Out of scope: the CLI and the node object; quantiles across ranks (order statistics do not merge from moments); the
- * CRPS beyond the sort path's capacity; weighted samples; quantiles inside the step kernels' launches. */
+ * CRPS beyond the sort path's capacity; quantiles inside the step kernels' launches.  Weighted samples are
+ * sipnet_batch_plane_quantiles_weighted's, below. */
 #define SIPNET_QUANTILES_MAX 16
 int32_t sipnet_quantile_lds_members(int32_t elem_is_f32);          /* host only: largest n the one-pass path sorts */
 int32_t sipnet_quantile_path(int32_t n_members, int32_t elem_is_f32, int32_t path); /* host only: 1 sort, 2 selection, -1 refused */
@@ -1167,6 +1168,63 @@ int sipnet_batch_plane_quantiles(sipnet_batch *b, const void *d_series, int32_t 
                                  const double *d_obs /* DEVICE [rows][n_sites], may be NULL */,
                                  double *d_crps    /* DEVICE [rows][n_sites], may be NULL */,
                                  int32_t *d_rank   /* DEVICE [rows][n_sites][2], may be NULL */,
+                                 void *hip_stream);
+
+/* ---- the same under per-member log-weights: weighted quantiles, moments, rank sums and CRPS -------------------------------
+ * For the sites that keep their particles in the importance-sampling cycle (total -3 of sipnet_batch_pf_resample_sites: the
+ * ensemble is a WEIGHTED sample, its log-weights carried in d_add of sipnet_batch_series_loglik / d_base of
+ * sipnet_batch_pf_temper_sites).  Series, cells, rows, ld, elem_is_f32, q and path as sipnet_batch_plane_quantiles.
+ * Weights: the used members are those of sipnet_batch_plane_quantiles (live_only has the same meaning).  m is the maximum of
+ * the site's used members' log-weights d_logw[s M + j] that are not NaN; w_j = rint(2^30 exp(logw_j - m)), the filter's own
+ * fixed-point weight (0 below exp(-21.5); <= 2^30).  A member that is not used, or whose log-weight is NaN or -inf, weighs 0.
+ * The SAMPLE of a cell is the used members with w_j > 0: n is their number, S = sum w_j, exact in int64 (S <= 2^52 by the
+ * limit on ncol, so exact as a double too).  A zero-weight member's value never enters a result and may be NaN.  With
+ * live_only = 0 the integers are sipnet_batch_pf_resample_sites' d_fixed_weights (beta NULL) and S is its total, bit for bit.
+ * d_site_weight[s] = {S, n, code}; d_fixed_weights[c] = the integer the call used for column c (0 for a member not used).
+ * Site code, which goes before everything of the site's cells: 0 analysed.  1: S == 0, no member weighs anything -- every
+ * floating-point output of the site's cells is NaN, rank {0, 0}, n = 0.  -2: a +inf log-weight among the used members -- as
+ * code 1 (S = n = 0, every integer 0), but rank {-2, -2}.
+ * Quantile: the inverse of the weighted distribution function, NOT interpolated.  T = sipnet_wquantile_target(S, q) =
+ * max(1, (int64) ceil(q * (double) S)), one rounded product, the same expression on host and device; Q = x_(i*), i* the first
+ * index in ascending order of value whose cumulative weight C_i >= T, compared as integers.  At equal weights this is
+ * Hyndman & Fan's type 1 (numpy's "inverted_cdf"), not the type 7 of the unweighted call; at q = 0 and q = 1 it is the
+ * minimum and the maximum of the positively weighted values.  Order of the keys, -0.0 == +0.0 (which zero a result carries is
+ * unspecified), a NaN among the sample's values (every floating-point output of the cell NaN, rank {-1, -1}) and the rules
+ * for y = d_obs[r][s] NaN (not scored: crps NaN, rank {-1, -1}, quantiles and moments as without it) or otherwise not finite
+ * (quantiles, moments and crps NaN, rank {-2, -2}) are the unweighted call's.
+ * rank[r][s] = {sum of w over x < y, sum of w over x == y}, exact; the PIT value is (rank[0] + u rank[1]) / S.
+ * moments[r][s] = {mean, m2}: mean = (sum (double) w_j x_j) / (double) S, m2 = (sum (double) w_j (x_j - mean)^2) / (double) S,
+ * two passes, every sum in one fixed order (a thread its elements in order, the threads by a fixed tree): a repeated call
+ * gives the same bits; the two paths add in different orders and may differ by rounding.
+ * crps[r][s] (sort path only) = (1/S) sum w_i |d_(i)| - (1/S^2) sum w_i (C_(i-1) + C_i - S) d_(i), d = x - y in sorted order:
+ * the weighted energy form; with w = 1 the unweighted call's (C_(i-1) + C_i - n = 2 i - n - 1).  The coefficient is
+ * (double) w_i * (double)(C_(i-1) + C_i - S): both factors exact, the product rounded once.
+ * Paths: a site pre-pass (one workgroup per site: m, the integers, S, n, code; into a scratch block of the batch), then one
+ * 256-thread workgroup per cell.  SORT: keys and 32-bit weights in LDS, 12 bytes a member, at most
+ * sipnet_wquantile_lds_members(elem_is_f32) = 8 192 members (96 KiB).  SELECTION: any M, the radix select over 64-bit sums of
+ * weights, eight reads of the row.  Quantiles, n, S, codes and ranks are the same bits on both.  sipnet_wquantile_path: the
+ * path a call runs (1 or 2), -1 where it would refuse.  sipnet_wquantile_target returns -1 for S outside 1..2^52 or a q that
+ * is not in [0, 1].  fused and grid of sipnet_batch_pf_info are set as by the unweighted call.
+ * Refused with SIPNET_ERR_BAD_ARGUMENT before any launch (sipnet_last_error says why): everything
+ * sipnet_batch_plane_quantiles refuses (the capacity is this call's); a NULL d_logw; ncol > 4 194 304.
+ * The batch's state, rings and parameters are left bit-identical; pending set_params rows are not flushed.  Everything is
+ * enqueued on hip_stream, behind the batch's last launch; the scratch block is the batch's, so two such calls on one batch go
+ * one behind the other.  No grid barrier, no spin, no floating-point atomic (the integer atomics are LDS bins of weights).
+ * Out of scope: the CLI and the node object; across ranks; a beta argument (the caller tempers d_logw); interpolated
+ * weighted quantiles; the CRPS beyond the sort path's capacity. */
+int64_t sipnet_wquantile_target(int64_t S, double q);                 /* host only */
+int32_t sipnet_wquantile_lds_members(int32_t elem_is_f32);            /* host only */
+int32_t sipnet_wquantile_path(int32_t n_members, int32_t elem_is_f32, int32_t path); /* host only: 1, 2 or -1 */
+int sipnet_batch_plane_quantiles_weighted(sipnet_batch *b, const void *d_series, int32_t elem_is_f32, int32_t rows, int64_t ld,
+                                 const double *d_logw /* DEVICE [ncol] */, int32_t n_q, const double *q /* HOST */,
+                                 int32_t live_only, int32_t path,
+                                 double  *d_quant         /* DEVICE [n_q][rows][n_sites] */,
+                                 int64_t *d_site_weight   /* DEVICE [n_sites][3] = {S, n, code}, may be NULL */,
+                                 int64_t *d_fixed_weights /* DEVICE [ncol], may be NULL: the integers the call used */,
+                                 double  *d_moments       /* DEVICE [rows][n_sites][2] = {mean, m2}, may be NULL */,
+                                 const double *d_obs      /* DEVICE [rows][n_sites], may be NULL */,
+                                 double  *d_crps          /* DEVICE [rows][n_sites], may be NULL */,
+                                 int64_t *d_rank          /* DEVICE [rows][n_sites][2], may be NULL */,
                                  void *hip_stream);
 
 /* ---- the filter across ranks WITHOUT an all-to-all: peer reads over xGMI -----------------------------

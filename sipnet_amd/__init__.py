@@ -17,7 +17,7 @@ from .config import (DEFAULT_FLAGS, FLAG_NAMES, PARAM_NAMES, POOLS, enkf_param, 
 from .io import (ClimTable, format_out_header, format_out_row, read_clim, read_events,
                  read_params, read_restart, check_restart, write_debug_logs, write_events_out, write_out,
                  write_restart)
-from .batch import (Batch, PlaneQuantiles, debug_fast_math, debug_live_bytes, liu_west_shrink, loglik_term, philox4x32_10, quantile_lds_members,
+from .batch import (Batch, PlaneQuantiles, WeightedQuantiles, wquantile_lds_members, wquantile_target, debug_fast_math, debug_live_bytes, liu_west_shrink, loglik_term, philox4x32_10, quantile_lds_members,
                     quantile_positions, rejuvenate_normals, demc_gamma, mcmc_draws)
 from ._lib import (REJUVENATE_BAD_INPUT, REJUVENATE_DONE, REJUVENATE_INFO_WORDS, REJUVENATE_NOT_SELECTED, REJUVENATE_TOO_FEW)
 from ._lib import (MCMC_BAD_INPUT, MCMC_DONE, MCMC_INFO_WORDS, MCMC_NOT_SELECTED, MCMC_TOO_FEW)
@@ -26,7 +26,7 @@ from ._lib import (TEMPER_BAD_INPUT, TEMPER_END, TEMPER_FOUND, TEMPER_INFO_WORDS
 from .enkf_local import ENKF_BLOCK_MAX_ROWS, EnkfLocalization, enkf_local_rows, enkf_local_schedule, gaspari_cohn
 
 __all__ = [
-    "Batch", "PlaneQuantiles", "debug_live_bytes", "debug_fast_math", "quantile_positions", "quantile_lds_members", "EnkfLocalization", "enkf_local_schedule", "enkf_local_rows", "ENKF_BLOCK_MAX_ROWS", "gaspari_cohn", "ClimTable", "Event", "Restart", "SipnetError", "read_restart", "write_restart",
+    "Batch", "PlaneQuantiles", "debug_live_bytes", "debug_fast_math", "quantile_positions", "quantile_lds_members", "WeightedQuantiles", "wquantile_target", "wquantile_lds_members", "EnkfLocalization", "enkf_local_schedule", "enkf_local_rows", "ENKF_BLOCK_MAX_ROWS", "gaspari_cohn", "ClimTable", "Event", "Restart", "SipnetError", "read_restart", "write_restart",
     "check_restart", "lib", "read_clim", "read_params",
     "read_events", "write_out", "write_events_out", "write_debug_logs", "format_out_header", "format_out_row", "read_config",
     "flags_from", "FLAG_NAMES", "POOLS", "enkf_pools", "enkf_plane", "enkf_param", "ENKF_MAX_PARAMS", "ENKF_MAX_SERIES", "DEFAULT_FLAGS", "PARAM_NAMES", "F64", "F32_MIXED",

@@ -257,6 +257,11 @@ SIGNATURES = {
     "sipnet_quantile_positions": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P]),
     "sipnet_batch_plane_quantiles": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32,
                                                _P, _P, _P, _P, _P, _P]),
+    "sipnet_wquantile_target": (C.c_int64, [C.c_int64, C.c_double]),
+    "sipnet_wquantile_lds_members": (C.c_int32, [C.c_int32]),
+    "sipnet_wquantile_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "sipnet_batch_plane_quantiles_weighted": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int32, _P, C.c_int32,
+                                                        C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sipnet_batch_pf_publish": (C.c_int, [_P, C.c_int32, _P]),
     "sipnet_batch_pf_connect": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "sipnet_batch_pf_block_len": (C.c_int64, [_P]),

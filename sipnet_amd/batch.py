@@ -19,6 +19,8 @@ from .enkf_local import EnkfLocalization
 
 PlaneQuantiles = collections.namedtuple("PlaneQuantiles", "quant count crps rank path")
 
+WeightedQuantiles = collections.namedtuple("WeightedQuantiles", "quant site_weight crps rank moments fixed path")
+
 # the EnKF analyses' arguments in the groups their C signatures have: ops (n_obs, operators, analysed mask), planes (pointers,
 # elements are floats, n_steps, ld), obs (obs, sd, inflation), info (d_site_info); held: what the pointers point into
 EnkfArgs = collections.namedtuple("EnkfArgs", "ops planes obs info held")
@@ -42,6 +44,20 @@ def quantile_positions(n, q):
     g = np.zeros(qs.size)
     check(lib().sipnet_quantile_positions(int(n), int(qs.size), ptr(qs), ptr(lo), ptr(g)), "quantile_positions")
     return lo, g
+
+
+def wquantile_lds_members(f32=False):
+    """the largest member count per site that Batch.plane_quantiles_weighted's sort path takes (sipnet_wquantile_lds_members)"""
+    return int(lib().sipnet_wquantile_lds_members(int(bool(f32))))
+
+
+def wquantile_target(S, q):
+    """the cumulative integer weight T = max(1, ceil(q S)) at which the weighted quantile q of a sample of total weight S is
+    read (sipnet_wquantile_target, host only: the expression the device uses)"""
+    T = int(lib().sipnet_wquantile_target(int(S), float(q)))
+    if T < 0:
+        raise ValueError("wquantile_target: S must be 1..2^52 and q a number in [0, 1]")
+    return T
 
 
 def philox4x32_10(ctr, key):
@@ -343,6 +359,54 @@ class Batch:
         check(self.L.sipnet_batch_plane_quantiles(self.h, *plane, n_q, ptr(qs), int(bool(live_only)), int(path), ptr(quant),
                                                   ptr(count), ptr(obs), ptr(crps), ptr(rank), self._stream()), what)
         return PlaneQuantiles(quant, count, crps, rank, ran)
+
+    def plane_quantiles_weighted(self, series, logw, q, live_only=True, obs=None, want_crps=None, want_rank=None, want_moments=False,
+                                 path=0, return_fixed=False):
+        """plane_quantiles under per-member log-weights (sipnet_batch_plane_quantiles_weighted): per (row, site) the
+        weighted quantiles q (the inverted weighted distribution function, not interpolated: type 1 at equal weights), the
+        weighted mean and centred second moment, and against obs[rows][n_sites] the rank sums {sum of w over x < y, over
+        x == y} and the weighted CRPS -- for the sites that keep their particles in the importance-sampling cycle.  logw:
+        float64 device tensor [ncol] (series_loglik's out, pf_temper_sites' out; NaN and -inf weigh nothing); the weights are
+        the filter's integers rint(2^30 exp(logw - the site's maximum)).  series, live_only, obs, want_crps / want_rank
+        (None: whenever obs is given; the CRPS: and the sort path runs) and path as plane_quantiles, the sort path taking at
+        most wquantile_lds_members() members per site.  -> WeightedQuantiles(quant[n_q][rows][n_sites] f64,
+        site_weight[n_sites][3] i64 = {S, n, code}, crps[rows][n_sites] f64 or None, rank[rows][n_sites][2] i64 or None,
+        moments[rows][n_sites][2] f64 or None, fixed[ncol] i64 or None (return_fixed: the integers the call used), path: the
+        one that ran), tensors on the device.  The batch is not changed."""
+        t = self._torch
+        what = "plane_quantiles_weighted"
+        if (not t.is_tensor(series) or not series.is_cuda or series.dim() != 2 or series.dtype not in (t.float32, t.float64)
+                or not series.is_contiguous() or series.shape[1] < self.ncol):
+            raise ValueError(f"{what}: series must be a contiguous 2-D float32 / float64 device tensor [rows][ld >= {self.ncol}]")
+        if not t.is_tensor(logw) or not _dense(logw, t.float64, self.ncol):
+            raise ValueError(f"{what}: logw must be a contiguous float64 device tensor of {self.ncol} values")
+        plane = _, f32, rows, _ = self._plane(series)
+        qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+        n_q = int(qs.size)
+        ran = int(self.L.sipnet_wquantile_path(self.n_members, f32, int(path)))     # (host only: the library's own rule; -1: the call refuses)
+        if want_crps is None:
+            want_crps = obs is not None and ran == 1
+        if want_rank is None:
+            want_rank = obs is not None
+        if obs is not None:
+            obs = t.as_tensor(obs, dtype=t.float64).to(self.device).contiguous()
+            if obs.numel() != rows * self.n_sites:
+                raise ValueError(f"{what}: obs needs rows x n_sites = {rows * self.n_sites} values, got {obs.numel()}")
+        cells = (rows, self.n_sites)
+
+        def new(wanted, shape, dtype):
+            return t.empty(shape, dtype=dtype, device=self.device) if wanted else None
+
+        quant = new(True, (n_q,) + cells, t.float64)
+        site_weight = new(True, (self.n_sites, 3), t.int64)
+        fixed = new(return_fixed, (self.ncol,), t.int64)
+        moments = new(want_moments, cells + (2,), t.float64)
+        crps = new(want_crps, cells, t.float64)
+        rank = new(want_rank, cells + (2,), t.int64)
+        check(self.L.sipnet_batch_plane_quantiles_weighted(self.h, *plane, ptr(logw), n_q, ptr(qs), int(bool(live_only)), int(path),
+                                                           ptr(quant), ptr(site_weight), ptr(fixed), ptr(moments), ptr(obs),
+                                                           ptr(crps), ptr(rank), self._stream()), what)
+        return WeightedQuantiles(quant, site_weight, crps, rank, moments, fixed, ran)
 
     def time_next_launch(self):
         """bracket the next run()'s step kernel with the timing events whatever its length (launches of 512 steps and

@@ -181,6 +181,8 @@ struct sipnet_batch {
   DevBuf<unsigned char> d_enkf;
   // sipnet_batch_enkf_analysis_smooth's series stage: a block of its own (the h, their anomalies, g and G), grow-only
   DevBuf<unsigned char> d_smooth;
+  // sipnet_batch_plane_quantiles_weighted's site pre-pass (quantiles.hip): the sites' maxima, totals and the members' integers
+  DevBuf<unsigned char> d_wquant;
 };
 int flushParams(sipnet_batch* b, hipStream_t stream);   // engine.hip: upload + convert what set_params left pending
 int materializeParams(sipnet_batch* b, hipStream_t stream);   // pf.hip: d_prm back into column order (no-op unless prmIndexed)

@@ -19,6 +19,8 @@
 //                      distinct order statistics wanted, and each of the seven passes that follow re-reads the row and counts the
 //                      next byte of the keys that share a target's prefix, a histogram per target.  Eight reads of the row.
 // Both form a quantile from its two order statistics by quantileOf, so their bits are the same.
+// quantiles_weighted.h: the same statistics and the moments under per-member log-weights
+// (sipnet_batch_plane_quantiles_weighted), with the filter's fixed-point weight of pf_weights.inc.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -399,6 +401,9 @@ __global__ __launch_bounds__(256) void quantSelectKernel(QuantArgs a) {
   }
 }
 
+#include "pf_weights.inc"
+#include "quantiles_weighted.h"
+
 // n_q and the q of a call: 0, or the refusal
 int checkQ(const char* name, int32_t n_q, const double* q) {
   if (!q) return refuse(name, "a NULL q");
@@ -406,6 +411,12 @@ int checkQ(const char* name, int32_t n_q, const double* q) {
   for (int i = 0; i < n_q; i++)
     if (!(q[i] >= 0.0 && q[i] <= 1.0)) return refuse(name, "q[" + std::to_string(i) + "] is not a number in [0, 1]");
   return 0;
+}
+
+// the path a call with this M and path argument runs under a sort capacity of cap members: 1 sort, 2 selection, -1 refused
+int32_t pathOf(int32_t n_members, int32_t path, int32_t cap) {
+  if (n_members < 1 || path < 0 || path > 2 || (path == 1 && n_members > cap)) return -1;
+  return path == 1 || (path == 0 && n_members <= cap) ? 1 : 2;
 }
 
 }  // namespace
@@ -418,9 +429,7 @@ int32_t sipnet_quantile_lds_members(int32_t elem_is_f32) {
 }
 
 int32_t sipnet_quantile_path(int32_t n_members, int32_t elem_is_f32, int32_t path) {
-  const int32_t cap = sipnet_quantile_lds_members(elem_is_f32);
-  if (n_members < 1 || path < 0 || path > 2 || (path == 1 && n_members > cap)) return -1;
-  return path == 1 || (path == 0 && n_members <= cap) ? 1 : 2;
+  return pathOf(n_members, path, sipnet_quantile_lds_members(elem_is_f32));
 }
 
 int sipnet_quantile_positions(int32_t n, int32_t n_q, const double* q, int32_t* lo, double* g) {
@@ -490,6 +499,94 @@ int sipnet_batch_plane_quantiles(sipnet_batch* b, const void* d_series, int32_t 
   b->pfInfo.fused = sort ? 1 : 0;   // (what sipnet_batch_pf_info reports of the last such call: which path ran)
   b->pfInfo.grid = (int32_t)std::min<int64_t>(a.cells, INT32_MAX);
   return live_only ? markBusy(b, stream) : SIPNET_OK;
+}
+
+int64_t sipnet_wquantile_target(int64_t S, double q) {
+  if (S < 1 || S > ((int64_t)1 << 52) || !(q >= 0.0 && q <= 1.0)) return -1;
+  return wTargetOf(S, q);
+}
+
+int32_t sipnet_wquantile_lds_members(int32_t elem_is_f32) {
+  (void)elem_is_f32;   // (floats are widened to 64-bit keys as well: one capacity)
+  return kWSortCap;
+}
+
+int32_t sipnet_wquantile_path(int32_t n_members, int32_t elem_is_f32, int32_t path) {
+  return pathOf(n_members, path, sipnet_wquantile_lds_members(elem_is_f32));
+}
+
+int sipnet_batch_plane_quantiles_weighted(sipnet_batch* b, const void* d_series, int32_t elem_is_f32, int32_t rows, int64_t ld,
+                                          const double* d_logw, int32_t n_q, const double* q, int32_t live_only, int32_t path,
+                                          double* d_quant, int64_t* d_site_weight, int64_t* d_fixed_weights, double* d_moments,
+                                          const double* d_obs, double* d_crps, int64_t* d_rank, void* hip_stream) {
+  const char* name = "sipnet_batch_plane_quantiles_weighted";
+  if (!b || !d_series || !d_quant) return refuse(name, "a NULL batch, series or d_quant");
+  if (!d_logw) return refuse(name, "a NULL d_logw");
+  int rc = checkQ(name, n_q, q);
+  if (rc) return rc;
+  if (rows < 1 || ld < b->ncol) return refuse(name, "needs rows >= 1 and ld >= ncol");
+  if (tooManyColumns(b)) return refuse(name, "more than 4194304 columns (the total weight must stay exact in a double)");
+  if ((d_crps || d_rank) && !d_obs) return refuse(name, "d_crps and d_rank need d_obs");
+  if (path < 0 || path > 2) return refuse(name, "path must be 0 (auto), 1 (sort) or 2 (selection)");
+  const int32_t M = b->n_members;
+  if (path == 1 && M > kWSortCap) return refuse(name, "the sort path holds at most 8192 members (sipnet_wquantile_lds_members)");
+  const bool sort = sipnet_wquantile_path(M, elem_is_f32, path) == 1;
+  if (d_crps && !sort)
+    return refuse(name, "the CRPS needs the sorted sample: the sort path only (at most 8192 members, path 0 or 1)");
+  if (live_only && b->planDirty) return refuse(name, "live_only needs a batch that was set up (sipnet_batch_setup)");
+  rc = useDevice(b);
+  if (rc) return rc;
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  // (the status row and the scratch are the batch's: behind whatever of the batch is writing or reading them)
+  rc = orderBehindBusy(b, stream);
+  if (rc) return rc;
+  WSiteArgs sa{};
+  rc = carveScratch(b, b->d_wquant, [&](Carver& c) {
+    sa.site = c.take<int64_t>((size_t)3 * b->n_sites);
+    sa.w = c.take<int32_t>((size_t)b->ncol);
+  });
+  if (rc) return rc;
+  sa.logw = d_logw;
+  sa.status = live_only ? b->d_state + (size_t)ST_status * b->ncol : nullptr;
+  sa.siteStatus = b->d_siteStatus;
+  sa.M = M;
+  sa.siteOut = d_site_weight;
+  sa.fixedOut = d_fixed_weights;
+  hipLaunchKernelGGL(wquantSiteKernel, dim3((unsigned)b->n_sites), dim3(256), 0, stream, sa);
+  HIP_TRY(hipGetLastError());
+  WQuantArgs a{};
+  a.series = d_series;
+  a.ld = ld;
+  a.nSites = b->n_sites;
+  a.cells = (int64_t)rows * b->n_sites;
+  a.M = M;
+  a.nq = n_q;
+  for (int i = 0; i < n_q; i++) a.q[i] = q[i];
+  a.w = sa.w;
+  a.site = sa.site;
+  a.quant = d_quant;
+  a.moments = d_moments;
+  a.obs = d_obs;
+  a.crps = d_crps;
+  a.rank = d_rank;
+  // a workgroup per cell: rows of at most 2^20 workgroups, as the unweighted call's
+  const unsigned gx = (unsigned)std::min<int64_t>(a.cells, (int64_t)1 << 20);
+  const dim3 grid(gx, (unsigned)((a.cells + gx - 1) / gx));
+  if (sort) {
+    int P = 256;
+    while (P < M) P <<= 1;
+    const size_t ldsBytes = (size_t)P * (sizeof(uint64_t) + sizeof(uint32_t));
+    const auto kernel = elem_is_f32 ? wquantSortKernel<float> : wquantSortKernel<double>;
+    if (ldsBytes > 32 * 1024)   // (beside its static LDS, past what a kernel may use unasked)
+      HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), ldsBytes, stream, a, P);
+  } else {
+    hipLaunchKernelGGL((elem_is_f32 ? wquantSelectKernel<float> : wquantSelectKernel<double>), grid, dim3(256), 0, stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  b->pfInfo.fused = sort ? 1 : 0;   // (what sipnet_batch_pf_info reports of the last such call: which path ran)
+  b->pfInfo.grid = (int32_t)std::min<int64_t>(a.cells, INT32_MAX);
+  return markBusy(b, stream);   // (the scratch is in use until these launches are done)
 }
 
 }  // extern "C"
