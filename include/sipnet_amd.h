@@ -1195,7 +1195,9 @@ int sipnet_batch_plane_quantiles(sipnet_batch *b, const void *d_series, int32_t 
  * rank[r][s] = {sum of w over x < y, sum of w over x == y}, exact; the PIT value is (rank[0] + u rank[1]) / S.
  * moments[r][s] = {mean, m2}: mean = (sum (double) w_j x_j) / (double) S, m2 = (sum (double) w_j (x_j - mean)^2) / (double) S,
  * two passes, every sum in one fixed order (a thread its elements in order, the threads by a fixed tree): a repeated call
- * gives the same bits; the two paths add in different orders and may differ by rounding.
+ * gives the same bits; the two paths add in different orders and may differ by rounding.  Every output of a cell depends on
+ * the cell's own values, weights and observation alone: not on the other sites, and not on where its row lies (n_sites, ld, the
+ * row's alignment) -- a site analysed alone gives the bits it gives among neighbours.
  * crps[r][s] (sort path only) = (1/S) sum w_i |d_(i)| - (1/S^2) sum w_i (C_(i-1) + C_i - S) d_(i), d = x - y in sorted order:
  * the weighted energy form; with w = 1 the unweighted call's (C_(i-1) + C_i - n = 2 i - n - 1).  The coefficient is
  * (double) w_i * (double)(C_(i-1) + C_i - S): both factors exact, the product rounded once.

@@ -77,15 +77,16 @@ __device__ __forceinline__ double quantileOf(double xlo, double xhi, double g) {
   return xlo + t;
 }
 
-// the cell's row, every element once: f(member, its value as a double, is it used), thread tid of 256
+// the cell's row, every element once: f(member, its value as a double, is it used), thread tid of 256.  Which members a thread
+// gets, and in which order, does not depend on the row's alignment (groups of 16 bytes' worth of members, then the tail one by
+// one): a floating-point sum that a caller forms thread by thread is the same bits wherever the row lies in its tensor.
 template <class T, class F>
 __device__ __forceinline__ void forRow(const T* __restrict__ row, int M, const double* __restrict__ st, bool siteLive, int tid, F&& f) {
   constexpr int kPer = 16 / (int)sizeof(T);
-  int done = 0;
+  const int nVec = M / kPer;
   if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
     typedef T vec_t __attribute__((ext_vector_type(kPer)));
     const vec_t* __restrict__ rv = reinterpret_cast<const vec_t*>(row);
-    const int nVec = M / kPer;
     for (int i = tid; i < nVec; i += 256) {
       const vec_t v = rv[i];
 #pragma unroll
@@ -94,9 +95,19 @@ __device__ __forceinline__ void forRow(const T* __restrict__ row, int M, const d
         f(m, (double)v[k], siteLive && (!st || st[m] == 0.0));
       }
     }
-    done = nVec * kPer;
+  } else {
+    for (int i = tid; i < nVec; i += 256) {
+      T v[kPer];
+#pragma unroll
+      for (int k = 0; k < kPer; k++) v[k] = row[i * kPer + k];
+#pragma unroll
+      for (int k = 0; k < kPer; k++) {
+        const int m = i * kPer + k;
+        f(m, (double)v[k], siteLive && (!st || st[m] == 0.0));
+      }
+    }
   }
-  for (int m = done + tid; m < M; m += 256) f(m, (double)row[m], siteLive && (!st || st[m] == 0.0));
+  for (int m = nVec * kPer + tid; m < M; m += 256) f(m, (double)row[m], siteLive && (!st || st[m] == 0.0));
 }
 
 // what a cell's workgroup knows before it reads a value

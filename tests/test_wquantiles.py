@@ -131,3 +131,88 @@ def test_the_batch_call_refuses_a_null_batch_without_a_device():
                                                         None, None, None, None)
     assert rc == _lib.ERR_BAD_ARGUMENT
     assert b"sipnet_batch_plane_quantiles_weighted" in sa.lib().sipnet_last_error()
+
+
+# ---- the reference on the edges of tests/test_gpu_wquantiles_edges.py ----------------------------------------------------------
+@pytest.mark.parametrize("M", [3, 257, 1000])
+def test_the_reference_cell_on_every_kind_of_observation(M):
+    """cell() against a loop over the members, and against what the contract says of each kind"""
+    rng = np.random.default_rng(600 + M)
+    w = rng.integers(1, 1 << 30, M)
+    w[1::4] = 0
+    x, y = wr.score_rows(rng, M, w > 0)
+    S = int(w.sum())
+    bare_quant = {}
+    for r, kind in enumerate(wr.OBS_KINDS):
+        quant, rank, nan = wr.cell(x[r], w, QS, y[r])
+        less = eq = 0
+        for j in range(M):
+            if w[j] > 0 and x[r, j] < y[r]:
+                less += int(w[j])
+            elif w[j] > 0 and x[r, j] == y[r]:
+                eq += int(w[j])
+        bare_quant[kind] = wr.cell(x[r], w, QS)[0]
+        if kind == "nan":
+            assert list(rank) == [-1, -1] and not nan
+            np.testing.assert_array_equal(quant, bare_quant[kind])           # the quantiles as without an observation
+        elif kind in ("+inf", "-inf"):
+            assert list(rank) == [-2, -2] and nan and np.isnan(quant).all()
+        else:
+            assert list(rank) == [less, eq] and not nan, kind
+            np.testing.assert_array_equal(quant, bare_quant[kind])
+        want = {"below": [0, 0], "above": [S, 0], "ties weight 0 only": [less, 0]}.get(kind)
+        if want is not None:
+            assert list(rank) == want, kind
+        if kind in ("tied", "+0 against -0"):
+            assert rank[1] > 0, kind
+        if kind in ("inside", "inside, mean 1e6"):
+            assert 0 < rank[0] < S, kind
+    # the codes go before the observation's
+    for yy in (0.0, np.nan, np.inf, -np.inf):
+        assert list(wr.cell(x[0], np.zeros(M, np.int64), QS, yy)[1]) == [0, 0]
+        assert list(wr.cell(x[0], w, QS, yy, code=-2)[1]) == [-2, -2]
+
+
+def test_the_reference_at_equal_weights_is_type_1_with_infinities_and_both_zeros():
+    rng = np.random.default_rng(31)
+    qs = [0.0, 1.0, 0.5] + [(j + 0.5) / 101 for j in range(0, 101, 9)]
+    x = rng.normal(size=101)
+    x[[3, 50]], x[[7, 90, 91]] = np.inf, -np.inf
+    zeros = np.where(rng.random(101) < 0.5, -0.0, 0.0)
+    mixed = np.round(rng.normal(size=101))
+    mixed[::5] = -0.0
+    for sample in (x, zeros, mixed):
+        got = wr.quantiles(sample, np.full(101, 1 << 30), qs)
+        np.testing.assert_array_equal(got, np.quantile(sample, qs, method="inverted_cdf"))
+    got = wr.quantiles(x, np.full(101, 1 << 30), [0.0, 1.0])
+    assert got[0] == -np.inf and got[1] == np.inf
+
+
+def test_the_denormal_allowance_and_the_large_means_bound_bite():
+    """rows 3 and 5 of special_rows at the sizes of the GPU test: the denormal row's relative bounds are 0 as doubles, and
+    the allowance that replaces them is a small fraction of the mean; the large-mean row's bound on m2 is a small fraction
+    of m2, and a one-pass second moment in doubles misses it by orders of magnitude"""
+    for M in (257, 1000):
+        rng = np.random.default_rng(700 + M)
+        w = rng.integers(1, 1 << 30, 3 * M)
+        w[rng.random(3 * M) < 0.1] = 0
+        x, y = wr.special_rows(rng, 3, M, False, w > 0)
+        assert not np.isnan(x[:8]).any() and np.isnan(x[8]).sum() == 1 and np.isinf(x[2, :M][w[:M] > 0]).sum() >= 2
+        xs, ws = x[3, :M], w[:M]
+        n = int((ws > 0).sum())
+        assert 0.0 < xs.min() and xs.max() < 2.0 ** -1022
+        b_mean, b_m2 = wr.moments_bounds(xs, ws)
+        assert b_mean == 0.0 and b_m2 == 0.0 and wr.crps_bound(xs, ws, y[3, 0]) == 0.0
+        mean, m2 = wr.moments(xs, ws)
+        assert float(m2) == 0.0 and 0.0 < wr.denormal_allowance(n) < 1e-7 * float(mean)
+        assert wr.denormal_allowance(n) == (2 * n + 8) * 2.0 ** -1074
+        xs = x[5, :M]
+        mean, m2 = wr.moments(xs, ws)
+        b_mean, b_m2 = wr.moments_bounds(xs, ws)
+        assert 1e-7 < float(m2) < 1e-5 and 0.0 < b_m2 < 1e-3 * float(m2)
+        wd, S = ws.astype(np.float64), float(ws.sum())
+        one_pass = (wd * xs * xs).sum() / S - ((wd * xs).sum() / S) ** 2
+        two_pass = (wd * (xs - (wd * xs).sum() / S) ** 2).sum() / S
+        print(f"M = {M}: m2 {float(m2):.3e}, its bound {b_m2:.3e}, one pass off by {abs(one_pass - float(m2)):.3e}, two passes by "
+              f"{abs(two_pass - float(m2)):.3e}")
+        assert abs(one_pass - float(m2)) > 100.0 * b_m2 and abs(two_pass - float(m2)) <= b_m2

@@ -1,5 +1,7 @@
 """The weighted order statistics of sipnet_batch_plane_quantiles_weighted, written plainly (include/sipnet_amd.h;
-tests/test_wquantiles.py pins this file, tests/test_gpu_wquantiles.py holds the kernels to it).  numpy only.
+tests/test_wquantiles.py pins this file; tests/test_gpu_wquantiles.py and tests/test_gpu_wquantiles_edges.py hold the kernels
+to it through tests/wquantile_gpu_common.py).  numpy only.  At its end: the inputs of the edge tests' special-value and
+observation rows, which the CPU pins and the GPU tests share.
 
 Everything here takes GIVEN integer weights w (int64, 0: the member is not in the sample): the sample of a cell is the values
 with w > 0, n their number, S = sum w.  Quantile q: sort by value, cumulative weights C in int64, T = max(1, ceil(q S)) with
@@ -130,6 +132,82 @@ def cell(x, w, q, y=None, code=0):
     if np.isnan(y):
         return quant, two(-1), False
     return quant, np.array([w[(x < y) & (w > 0)].sum(), w[(x == y) & (w > 0)].sum()], np.int64), False
+
+
+# ---- the inputs of the edge tests (tests/test_gpu_wquantiles_edges.py; pinned without a device in tests/test_wquantiles.py) --
+TINY = 2.0 ** -1074                                                      # the spacing of the denormal doubles
+SPECIAL_ROWS = ("zeros", "zeros among others", "infinities", "denormals", "float denormals", "large mean", "large magnitude",
+                "equal values", "nan")
+DENORMAL_ROWS = (3, 4)
+OBS_KINDS = ("below", "above", "tied", "ties weight 0 only", "+0 against -0", "nan", "+inf", "-inf", "inside", "inside, mean 1e6")
+
+
+def denormal_allowance(n):
+    """what the two denormal rows add to the mean's and the CRPS's bounds: the relative bounds count roundings of 2^-53 of
+    the result, but a result (or a partial sum) below 2^-1022 is rounded to a multiple of 2^-1074 instead: half a spacing for
+    each of the at most 2 n + 6 roundings of a sum of n terms and its quotients -- (2 n + 8) 2^-1074 with the margin"""
+    return (2 * n + 8) * TINY
+
+
+def special_rows(rng, n_sites, M, f32, weighs):
+    """the rows of SPECIAL_ROWS over n_sites x M members, weighs [n_sites M] bool: the members that will weigh something (every
+    site needs two) -> (x [9][n_sites M] as the device reads it through the element type, y [9][n_sites])"""
+    n = n_sites * M
+    first = [np.flatnonzero(weighs[s * M:(s + 1) * M])[:2] + s * M for s in range(n_sites)]
+    nobody = [np.flatnonzero(~weighs[s * M:(s + 1) * M])[:1] + s * M for s in range(n_sites)]
+    x = np.zeros((len(SPECIAL_ROWS), n))
+    y = np.zeros((len(SPECIAL_ROWS), n_sites))
+    x[0] = np.where(rng.random(n) < 0.5, -0.0, 0.0)
+    x[1] = np.round(rng.normal(size=n) * 2.0)
+    x[1, ::5], x[1, 1::5] = -0.0, 0.0
+    x[2] = rng.normal(size=n)
+    x[2, rng.random(n) < 0.02] = np.inf                                  # (site 0 has both for sure, and both with weight)
+    x[2, rng.random(n) < 0.02] = -np.inf
+    x[2, first[0]] = [np.inf, -np.inf]
+    for s in range(1, n_sites):                                          # the last site: infinities under weight 0 only;
+        inf_here = np.flatnonzero(np.isinf(x[2, s * M:(s + 1) * M])) + s * M                   # those between: only +inf under weight
+        if s == n_sites - 1:
+            x[2, inf_here[weighs[inf_here]]] = 0.5
+            x[2, nobody[s]] = -np.inf
+        else:
+            x[2, inf_here[weighs[inf_here] & (x[2, inf_here] < 0)]] = 0.5
+            x[2, first[s][0]] = np.inf
+    x[3] = rng.integers(1, 2 ** 39, n) * 5e-324
+    x[4] = rng.integers(1, 2 ** 22, n) * 2.0 ** -149
+    x[5] = 1e8 + 1e-3 * rng.normal(size=n)
+    x[6] = (1e30 if f32 else 1e140) * rng.normal(size=n)                 # (1e140 is no float)
+    x[7] = 0.1
+    x[8] = rng.normal(size=n)
+    x[8, first[1][0]] = np.nan                                           # under weight, in site 1 only
+    if f32:
+        x = x.astype(np.float32).astype(np.float64)
+    for r in (3, 4, 7):
+        y[r] = [x[r, first[s][1]] for s in range(n_sites)]               # a member's value
+    y[2], y[5], y[8] = 0.3, 1e8, 0.1
+    return x, y
+
+
+def score_rows(rng, M, weighs):
+    """ONE site's rows of OBS_KINDS: weighs [M] bool, the members that will weigh something (at least one; the rows that need
+    a member without weight are plain rows when there is none) -> (x [10][M], y [10])"""
+    pos, zero = np.flatnonzero(weighs), np.flatnonzero(~weighs)
+    x = np.round(rng.normal(size=(len(OBS_KINDS), M)) * 2.0, 1)
+    y = np.zeros(len(OBS_KINDS))
+    x[9] = 1e6 + rng.normal(size=M)
+    if zero.size:
+        x[0, zero[0]] = x[0, pos].min() - 5.0                            # below y, and weighs nothing
+        x[1, zero[0]] = x[1, pos].max() + 5.0
+        x[3, zero[0]] = 7.25                                             # (no multiple of 0.1: nobody else has it)
+    y[0], y[1] = x[0, pos].min() - 1.0, x[1, pos].max() + 1.0
+    y[2] = x[2, pos[0]]
+    y[3] = 7.25
+    x[4, pos[0]] = -0.0
+    x[4, pos[-1]] = -0.0
+    y[4] = 0.0
+    y[5], y[6], y[7] = np.nan, np.inf, -np.inf
+    y[8] = float(np.median(x[8, pos])) + 0.013
+    y[9] = 1e6 + 0.1
+    return x, y
 
 
 def plane(series, n_sites, M, w, q, obs=None, codes=None):
