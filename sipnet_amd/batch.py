@@ -311,6 +311,31 @@ class Batch:
         check(self.L.sipnet_batch_reduce_plane(self.h, *self._plane(plane), ptr(stats), self._stream()), "reduce_plane")
         return stats
 
+    def _quantile_series(self, what, series):
+        """the series of plane_quantiles and plane_quantiles_weighted, checked -> its plane arguments"""
+        t = self._torch
+        if (not t.is_tensor(series) or not series.is_cuda or series.dim() != 2 or series.dtype not in (t.float32, t.float64)
+                or not series.is_contiguous() or series.shape[1] < self.ncol):
+            raise ValueError(f"{what}: series must be a contiguous 2-D float32 / float64 device tensor [rows][ld >= {self.ncol}]")
+        return self._plane(series)
+
+    def _quantile_call(self, what, path_of, plane, q, obs, want_crps, want_rank, path):
+        """what the two calls marshal alike behind the series; path_of: the library's path rule of the call -> (the q array,
+        the path that will run (-1: the call refuses), obs on the device, want_crps, want_rank, the cells' shape)"""
+        t = self._torch
+        _, f32, rows, _ = plane
+        qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+        ran = int(path_of(self.n_members, f32, int(path)))      # (host only: the library's own rule)
+        if want_crps is None:
+            want_crps = obs is not None and ran == 1
+        if want_rank is None:
+            want_rank = obs is not None
+        if obs is not None:
+            obs = t.as_tensor(obs, dtype=t.float64).to(self.device).contiguous()
+            if obs.numel() != rows * self.n_sites:
+                raise ValueError(f"{what}: obs needs rows x n_sites = {rows * self.n_sites} values, got {obs.numel()}")
+        return qs, ran, obs, want_crps, want_rank, (rows, self.n_sites)
+
     def plane_quantiles(self, series, q, live_only=True, obs=None, want_crps=None, want_rank=None, path=0, out=None):
         """Per (row, site) order statistics of a series over each site's members (sipnet_batch_plane_quantiles): the type-7
         quantiles q (numpy's "linear"), the sample size, and against obs[rows][n_sites] the rank histogram's counts
@@ -324,22 +349,10 @@ class Batch:
         ran), tensors on the device.  The batch is not changed."""
         t = self._torch
         what = "plane_quantiles"
-        if (not t.is_tensor(series) or not series.is_cuda or series.dim() != 2 or series.dtype not in (t.float32, t.float64)
-                or not series.is_contiguous() or series.shape[1] < self.ncol):
-            raise ValueError(f"{what}: series must be a contiguous 2-D float32 / float64 device tensor [rows][ld >= {self.ncol}]")
-        plane = _, f32, rows, _ = self._plane(series)
-        qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+        plane = self._quantile_series(what, series)
+        qs, ran, obs, want_crps, want_rank, cells = self._quantile_call(what, self.L.sipnet_quantile_path, plane, q, obs, want_crps,
+                                                                         want_rank, path)
         n_q = int(qs.size)
-        ran = int(self.L.sipnet_quantile_path(self.n_members, f32, int(path)))      # (host only: the library's own rule; -1: the call refuses)
-        if want_crps is None:
-            want_crps = obs is not None and ran == 1
-        if want_rank is None:
-            want_rank = obs is not None
-        if obs is not None:
-            obs = t.as_tensor(obs, dtype=t.float64).to(self.device).contiguous()
-            if obs.numel() != rows * self.n_sites:
-                raise ValueError(f"{what}: obs needs rows x n_sites = {rows * self.n_sites} values, got {obs.numel()}")
-        cells = (rows, self.n_sites)
         parts = [None] * 4 if out is None else list(out)[:4]
 
         def part(k, wanted, shape, dtype, name):
@@ -375,24 +388,12 @@ class Batch:
         one that ran), tensors on the device.  The batch is not changed."""
         t = self._torch
         what = "plane_quantiles_weighted"
-        if (not t.is_tensor(series) or not series.is_cuda or series.dim() != 2 or series.dtype not in (t.float32, t.float64)
-                or not series.is_contiguous() or series.shape[1] < self.ncol):
-            raise ValueError(f"{what}: series must be a contiguous 2-D float32 / float64 device tensor [rows][ld >= {self.ncol}]")
+        plane = self._quantile_series(what, series)
         if not t.is_tensor(logw) or not _dense(logw, t.float64, self.ncol):
             raise ValueError(f"{what}: logw must be a contiguous float64 device tensor of {self.ncol} values")
-        plane = _, f32, rows, _ = self._plane(series)
-        qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+        qs, ran, obs, want_crps, want_rank, cells = self._quantile_call(what, self.L.sipnet_wquantile_path, plane, q, obs, want_crps,
+                                                                         want_rank, path)
         n_q = int(qs.size)
-        ran = int(self.L.sipnet_wquantile_path(self.n_members, f32, int(path)))     # (host only: the library's own rule; -1: the call refuses)
-        if want_crps is None:
-            want_crps = obs is not None and ran == 1
-        if want_rank is None:
-            want_rank = obs is not None
-        if obs is not None:
-            obs = t.as_tensor(obs, dtype=t.float64).to(self.device).contiguous()
-            if obs.numel() != rows * self.n_sites:
-                raise ValueError(f"{what}: obs needs rows x n_sites = {rows * self.n_sites} values, got {obs.numel()}")
-        cells = (rows, self.n_sites)
 
         def new(wanted, shape, dtype):
             return t.empty(shape, dtype=dtype, device=self.device) if wanted else None

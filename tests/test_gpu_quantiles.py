@@ -14,12 +14,11 @@ import sipnet_amd as sa
 from sipnet_amd import _lib, synth
 from tests import quantile_reference as qr
 from tests.enkf_gpu_common import ANALYSED, BASE, DEV, bits, carried_params, crafted, forecast, observe, operators, sites_batch
+from tests.wquantile_gpu_common import Q6, SELECT, SORT, bare, on_device, same, widened
 
 pytestmark = pytest.mark.gpu
 
 Q3 = [0.025, 0.5, 0.975]
-Q6 = [0.0, 1.0, 0.5, 0.025, 0.975, 1.0 / 3.0]
-SORT, SELECT = 1, 2
 
 
 @pytest.fixture(scope="module")
@@ -27,32 +26,9 @@ def base():
     return sa.read_params(BASE, sa.flags_from())[0]
 
 
-def bare(n_sites, M, prec=sa.F64):
-    """a batch that was created and nothing else: all that live_only = 0 needs"""
-    return sa.Batch(sa.flags_from(), n_sites, M, prec)
-
-
-def on_device(host, dtype=torch.float64, pad=0):
-    """host [rows][ncol] -> a device tensor [rows][ncol + pad] of dtype, the padding full of NaN"""
-    host = np.asarray(host, dtype=np.float64)
-    full = np.full((host.shape[0], host.shape[1] + pad), np.nan)
-    full[:, :host.shape[1]] = host
-    return torch.tensor(full, dtype=dtype, device=DEV)
-
-
-def widened(host, dtype):
-    """what the device reads of host through a tensor of dtype, as doubles"""
-    return np.asarray(host, dtype=np.float64).astype(np.float32 if dtype == torch.float32 else np.float64).astype(np.float64)
-
-
-def host_of(res):
+def host_of_plain(res):
+    """the unweighted call's four outputs as a plain tuple (wquantile_gpu_common.host_of: the weighted call's six, named)"""
     return tuple(None if x is None else x.cpu().numpy() for x in res[:4])
-
-
-def same(got, want, what=""):
-    """equal as values (a NaN equals a NaN, -0.0 equals +0.0)"""
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want, equal_nan=True), (what, got, want)
 
 
 def check_crps(got, series, n_sites, M, obs, used=None):
@@ -93,7 +69,7 @@ def test_quantiles_counts_and_ranks_are_the_references(M):
                     for path in (SORT, SELECT):
                         res = b.plane_quantiles(series, Q6, live_only=False, obs=obs, want_crps=False, path=path)
                         assert res.path == path and res.crps is None and b.pf_info()["fused"] == (1 if path == SORT else 0)
-                        got = host_of(res)
+                        got = host_of_plain(res)
                         what = (n_sites, rows, dtype, pad, path)
                         same(got[0], want[0], what)
                         same(got[1], want[1], what)
@@ -123,7 +99,7 @@ def test_live_members_only(base, prec):
     assert list(want[1][0]) == [M - 3, 0, 1, M]
     assert np.isnan(want[0][:, :, 1]).all() and np.array_equal(want[0][1, :, 2], x[:, 2 * M + 33])
     for path in (SORT, SELECT):
-        got = host_of(b.plane_quantiles(series, Q3, live_only=True, obs=obs, want_crps=path == SORT, path=path))
+        got = host_of_plain(b.plane_quantiles(series, Q3, live_only=True, obs=obs, want_crps=path == SORT, path=path))
         same(got[0], want[0], path)
         same(got[1], want[1], path)
         same(got[3], want[3], path)
@@ -133,7 +109,7 @@ def test_live_members_only(base, prec):
     want_all = qr.plane(x, n_sites, M, Q3, obs=obs)
     assert np.isnan(want_all[0][:, :, :3]).all() and (want_all[3][:, :3] == -1).all() and not np.isnan(want_all[0][:, :, 3]).any()
     for path in (SORT, SELECT):
-        got = host_of(b.plane_quantiles(series, Q3, live_only=False, obs=obs, want_crps=False, path=path))
+        got = host_of_plain(b.plane_quantiles(series, Q3, live_only=False, obs=obs, want_crps=False, path=path))
         same(got[0], want_all[0], path)
         assert (got[1] == M).all()
         same(got[3], want_all[3], path)
@@ -172,7 +148,7 @@ def test_special_values(dtype):
     b = bare(n_sites, M)
     series = on_device(host, dtype)
     for path in (SORT, SELECT):
-        got = host_of(b.plane_quantiles(series, Q6, live_only=False, obs=obs, want_crps=False, path=path))
+        got = host_of_plain(b.plane_quantiles(series, Q6, live_only=False, obs=obs, want_crps=False, path=path))
         for k, name in enumerate(names):
             same(got[0][:, k], want[0][:, k], (name, path))
             same(got[3][k], want[3][k], (name, path))
@@ -206,7 +182,7 @@ def test_scores(M):
     series = on_device(host)
     res = b.plane_quantiles(series, Q3, live_only=False, obs=obs)          # (want_crps, want_rank: whenever obs is given)
     assert res.path == SORT and res.crps is not None and res.rank is not None
-    got = host_of(res)
+    got = host_of_plain(res)
     same(got[0], want[0])
     same(got[1], want[1])
     same(got[3], want[3])
@@ -214,10 +190,10 @@ def test_scores(M):
     scored = np.isfinite(obs)
     assert (got[2][scored] >= 0).all()
     print(f"largest |crps - the reference's centred form| = {np.nanmax(np.abs(got[2] - want[2])):.3e}")
-    again = host_of(b.plane_quantiles(series, Q3, live_only=False, obs=obs, out=res))
+    again = host_of_plain(b.plane_quantiles(series, Q3, live_only=False, obs=obs, out=res))
     for k in range(4):
         np.testing.assert_array_equal(again[k].view(np.uint8), got[k].view(np.uint8))      # a repeated call: the same bits
-    sel = host_of(b.plane_quantiles(series, Q3, live_only=False, obs=obs, want_crps=False, path=SELECT))
+    sel = host_of_plain(b.plane_quantiles(series, Q3, live_only=False, obs=obs, want_crps=False, path=SELECT))
     same(sel[3], want[3])
     np.testing.assert_array_equal(bits(sel[0]), bits(got[0]))
     b.close()
@@ -247,7 +223,7 @@ def test_more_cells_than_one_row_of_the_grid():
     b = bare(1, 1)
     series = on_device(host)
     for path in (SORT, SELECT):
-        got = host_of(b.plane_quantiles(series, [0.0, 0.5], live_only=False, obs=obs, want_crps=path == SORT, path=path))
+        got = host_of_plain(b.plane_quantiles(series, [0.0, 0.5], live_only=False, obs=obs, want_crps=path == SORT, path=path))
         assert np.array_equal(got[0][0, :, 0], host[:, 0]) and np.array_equal(got[0][1, :, 0], host[:, 0]), path
         assert (got[1] == 1).all() and (got[3] == [1, 0]).all(), path
         if path == SORT:
@@ -268,12 +244,12 @@ def test_the_capacity_edge():
         res = b.plane_quantiles(series, Q3, live_only=False, obs=obs)
         assert res.path == auto and b.pf_info()["fused"] == (1 if auto == SORT else 0)
         assert (res.crps is not None) == (auto == SORT)
-        got = host_of(res)
+        got = host_of_plain(res)
         same(got[0], want[0], M)
         same(got[1], want[1], M)
         same(got[3], want[3], M)
         if auto == SORT:
-            sel = host_of(b.plane_quantiles(series, Q3, live_only=False, obs=obs, want_crps=False, path=SELECT))
+            sel = host_of_plain(b.plane_quantiles(series, Q3, live_only=False, obs=obs, want_crps=False, path=SELECT))
             np.testing.assert_array_equal(bits(sel[0]), bits(got[0]))
             same(sel[3], got[3])
         else:
@@ -295,13 +271,13 @@ def test_a_forecasts_planes_sums_and_smoothed_series(base, prec):
     nee = planes[0].cpu().numpy()
     obs = np.median(nee.astype(np.float64).reshape(steps, n_sites, M), axis=2) + 0.01
     want = qr.plane(nee, n_sites, M, Q3, used=used, obs=obs)
-    got = host_of(b.plane_quantiles(planes[0], Q3, obs=obs))
+    got = host_of_plain(b.plane_quantiles(planes[0], Q3, obs=obs))
     for k in (0, 1, 3):
         same(got[k], want[k], k)
     check_crps(got[2][::16], nee.astype(np.float64)[::16], n_sites, M, obs[::16], used)
     for v in range(3):
         want = qr.plane(sums[v].cpu().numpy(), n_sites, M, Q3, used=used)
-        got = host_of(b.plane_quantiles(sums[v], Q3))
+        got = host_of_plain(b.plane_quantiles(sums[v], Q3))
         same(got[0], want[0], v)
         same(got[1], want[1], v)
     # the smoother analyses the planes in place: the median of what it left
@@ -313,7 +289,7 @@ def test_a_forecasts_planes_sums_and_smoothed_series(base, prec):
     assert (smoothed != nee).any()
     used = b.get_state()[:, 29] == 0
     want = qr.plane(smoothed, n_sites, M, [0.5], used=used)
-    got = host_of(b.plane_quantiles(planes[0], [0.5]))
+    got = host_of_plain(b.plane_quantiles(planes[0], [0.5]))
     same(got[0], want[0])
     same(got[1], want[1])
     b.close()
