@@ -132,9 +132,10 @@ def test_hand_edits_against_the_oracle(flagset, family, prec, oracle):
         assert np.array_equal(died_g >= 0, died_o >= 0)
 
 
-# (the four-chunk layout and the two-chunk nitrogen-cycle layout have no full-state build: no record to ask for)
+# (the four-chunk layout has no full-state build: no record to ask for; the two-chunk nitrogen-cycle layout has one,
+# stepCoopNPairFullKernel)
 RECORDS = [("default", "strict", F64), ("default", "one_wave", F64), ("default", "coop_lds", F64), ("default", "coop_hbm", F32),
-           ("default", "coop_pair", F64), ("ncycle", "coop_ncycle", F64)]
+           ("default", "coop_pair", F64), ("ncycle", "coop_ncycle", F64), ("ncycle", "coop_ncycle_pair", F64), ("default", "coop_pair", F32)]
 
 
 @pytest.mark.parametrize("flagset,family,prec", RECORDS, ids=[ident(c) for c in RECORDS])
@@ -144,7 +145,8 @@ def test_records_at_the_edit_steps_against_the_oracles(flagset, family, prec, or
     within 5e-2 with fewer than 1e-4 of the values over 5e-3"""
     members, clim = forest(flagset)
     run = edited_run(flagset, family, prec, full=True)
-    assert all(family_ok(family, flagset, n) or (family == "coop_ncycle" and n.startswith("stepCoopNFullKernel<")) for n in run["names"]), run["names"]
+    full_n = {"coop_ncycle": "stepCoopNFullKernel<", "coop_ncycle_pair": "stepCoopNPairFullKernel<"}
+    assert all(family_ok(family, flagset, n) or (family in full_n and n.startswith(full_n[family])) for n in run["names"]), run["names"]
     steps = [c + k for c in se.CUTS for k in (0, 1)]
     worst, over, n = 0.0, 0, 0
     for m in range(se.M):
